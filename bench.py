@@ -5,10 +5,12 @@ Workload (BASELINE.json configs[1]): ResNet-50 DeepLabV3+ + memory, bs=8 per GPU
 batch, fp32, one step = train forward (memory read + non-detached write) -> 5-term loss -> backward -> SGD ->
 eval-mode second forward that commits the memory (all of it inside the timed region).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field). A plain run measures the headline figure only (set up, warm up, K timed
+steps, the line); --full adds everything else the line can carry (host enqueue time, roofline passes, side measurements, CPU baseline), whose fields are
+null otherwise. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -34,6 +36,13 @@ def parse():
     ap.add_argument('--size', type=int, default=768)
     ap.add_argument('--truncate-second-forward', action='store_true',
                     help='skip the decoder in the memory-commit forward (identical results; NOT the default measurement)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure, measure everything else of the default run: host enqueue time, the per-kernel roofline passes, the memory-path '
+                         'roofline, the side measurements (bf16 tier, hipGraph form, mldg on both tiers), the collective count of N > 1 and the CPU baseline. '
+                         'Off: set up, warm up, time --steps steps, dump the outputs (--dump-outputs) and print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): its losses, the committed memory, a fixed '
+                         'seeded sample of the updated parameters and the BatchNorm running moments (train workload only)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-side', action='store_true', help='skip the side.bf16 sub-measurement of the default (f32, one GPU) run')
     ap.add_argument('--launch-timeout', type=float, default=3600.0, help='--gpus N self-launch: seconds after which every rank is killed and the run fails')
@@ -57,7 +66,10 @@ def parse():
                          "measurement of the caller before training (train.py:1000-1042): class-prototype initialisation of the memory over --steps batches of "
                          "bs=8 768x768, eval forwards + the write kernel's soft-label accumulation. mldg = side measurement of the regime every pinmem script "
                          "runs (train.py:493-632, train_GS_pinmem_DR50V3P.sh:9-10): meta-train 4 + meta-test 4 images at 768x768, three weight sets, retain_graph")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload != 'train':
+        ap.error('--dump-outputs: the train workload only')
+    return a
 
 
 CONFIG5_GFLOP_PER_TILE = 2057.0        # R101-DeepLabV2 'D' forward on one 1x3x1024x1024 tile
@@ -535,6 +547,28 @@ def host_enqueue_ms(step_fn, tries=2):
     return round(best * 1e3, 3)
 
 
+DUMP_SAMPLE = 1 << 20          # elements of the seeded parameter sample written by --dump-outputs (4 MB)
+
+
+def dump_outputs(d, torch, net, losses, memory):
+    """--dump-outputs: what the last timed step left for its caller, as float32 .npy files under `d` -- its losses, the committed memory, a fixed seeded
+    sample of the updated parameters (the same positions for the same model) and every BatchNorm running moment. Returns {name: shape}."""
+    import numpy as np
+    m = net.module if hasattr(net, 'module') else net
+    arrays = {'loss_' + k: v for k, v in losses.items() if k != 'mem_t'}
+    arrays['memory'] = memory
+    flat = torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+    idx = torch.randint(flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(304)).sort().values
+    arrays['parameters_sample'] = flat[idx.to(flat.device)]
+    arrays['bn_running_moments'] = torch.cat([b.detach().reshape(-1).float() for n, b in m.named_buffers() if n.endswith(('running_mean', 'running_var'))])
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -615,6 +649,7 @@ def main():
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    torch.manual_seed(304 + rank)      # the random draws of the step (Gumbel noise of the memory reads, Dropout2d): the same from run to run
     local = int(os.environ.get('LOCAL_RANK', '0'))
     assert a.gpus == world, 'bench.py --gpus %d but the launcher environment says WORLD_SIZE=%d' % (a.gpus, world)
     assert torch.cuda.is_available(), 'bench.py needs a GPU: the HIP path has no CPU fallback'
@@ -677,7 +712,7 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    prof = not a.no_profile
+    prof = a.full and not a.no_profile
     from pinthememory_amd.hip import ops as _ops
     overlap_defaults = (_ops.OVERLAP_WGRAD, harness.COMMIT_OVERLAP)
     graphed = None
@@ -700,14 +735,22 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # host-side cost of one step (two extra untimed steps from an idle GPU). Skipped with --no-profile: the counter / trace passes of tools/gpu_round*_profiles.sh count the
-    # steps of the run (warm-up + timed) and must not see extra ones
-    host_ms = {'timed_form': None if a.no_profile else host_enqueue_ms(timed_step)}
+    dumped = None
+    if a.dump_outputs:      # before any further step: what the last timed step left
+        memory = graphed.committed_memory() if graphed is not None else None
+        if memory is None:
+            harness.finish_commit(net)      # collective with more than one rank: every rank calls it
+            memory = (net.module if hasattr(net, 'module') else net).memory.m_items
+        if rank == 0:
+            dumped = dump_outputs(a.dump_outputs, torch, net, losses, memory)
+    # host-side cost of one step (two extra untimed steps from an idle GPU), --full only. Skipped with --no-profile: the counter / trace passes of tools/gpu_round*_profiles.sh
+    # count the steps of the run (warm-up + timed) and must not see extra ones
+    host_ms = {'timed_form': host_enqueue_ms(timed_step) if prof else None}
     if graphed is not None:
         losses = {k: v.clone() for k, v in losses.items()}
         graphed.close()
         graphed = None
-        host_ms['eager'] = None if a.no_profile else host_enqueue_ms(step)
+        host_ms['eager'] = host_enqueue_ms(step) if prof else None
     per_rank_ms, ranks_seen = [round(dt / a.steps * 1e3, 3)], 1
     if multi:
         t = torch.zeros(world, device=dev, dtype=torch.float64)
@@ -723,7 +766,7 @@ def main():
     if multi:
         rccl_direct = comm is not None
         rccl_reason = ('direct ncclComm on the compute stream (pinthememory_amd/rccl.py), %d ranks' % ranks_seen) if rccl_direct else D.direct_fallback_reason(backend)
-        coll_per_step = D.count_collectives(lambda: step())
+        coll_per_step = D.count_collectives(lambda: step()) if a.full else None
     roof = None
     if prof:
         # Per-kernel timing brackets every conv launch with two HIP events, which costs ~1.7 ms per step (measured: 70.2 vs 68.5 ms),
@@ -786,7 +829,7 @@ def main():
                                          'timed_region_overlapped': {'achieved': round(ov_fl / (ov_ms * 1e-3) / 1e12, 2), 'ms_per_step': round(ov_ms / ov_steps, 3),
                                                                      'measured': '%d untimed steps with the stream overlaps of the timed region (fp32: weight gradients on a side stream; bf16: inline; commit forward of step t under the training forward of step t + 1)' % ov_steps}}}
     side = None
-    if a.dtype == 'f32' and not multi and not a.no_side and edge is None:
+    if a.full and a.dtype == 'f32' and not multi and not a.no_side and edge is None:
         # BASELINE configs[2] in the driver's own run: the SAME process, model and batch switched to the bf16 tier after the timed region -- a few untimed steps, a
         # few timed ones (barrier-free single GPU: synchronize on both sides), then two serialised steps for its dominant kernel. Never part of `value`.
         # Any failure in here is recorded in the line, never raised: the fp32 metric has been measured and must be printed.
@@ -898,6 +941,8 @@ def main():
                           'step_mfma_frac': round(gf_img * a.batch * world * a.steps / 1e3 / dt / (peak * world), 4),
                           'final_loss': round(float(losses['total']), 5)},
                'roofline': roof}
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         if side is not None:
             out['side'] = side
         if edge is not None:
@@ -922,7 +967,7 @@ def main():
                 roof['memory_read'] = memory_path_roofline(a.batch, a.size)
             except Exception as e:      # noqa: BLE001 -- the metric line must not depend on the side measurement
                 roof['memory_read'] = {'error': repr(e)}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(a.cpu_batch, a.size)
         else:
             out['cpu_baseline'] = None

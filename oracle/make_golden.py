@@ -1,6 +1,6 @@
 """Oracle tooling (test infrastructure): capture golden vectors FROM THE IMPORTED REFERENCE.
 
-Run in the build container only:  python -m oracle.make_golden
+Run in the build container only:  python -m oracle.make_golden  (python -m oracle.make_golden pairing: tests/golden/reference_pairing.npz only)
 Every expected value below is produced by /root/reference's own network.deepv3plus / network.deepv2 /
 network.memory classes (imported where they lie, oracle/import_reference.py), driven with the RNG-free
 weights and synthetic inputs of pinthememory_amd/synth.py. Only small arrays are written to tests/golden/.
@@ -130,5 +130,76 @@ def main():
     print('golden fixtures written to', OUT)
 
 
+def fingerprint(tensors, sample=64):
+    """Compact stand-in for a list of tensors too large to store: per tensor the float64 sum, sum of |x| and L2 norm, and the values at `sample`
+    positions drawn by a generator seeded with the tensor's size (the same positions for every tensor of that size, on every host)."""
+    sums, vals = [], []
+    for t in tensors:
+        f = t.detach().reshape(-1).to(torch.float64)
+        idx = torch.randint(f.numel(), (min(sample, f.numel()),), generator=torch.Generator().manual_seed(f.numel()))
+        sums.append([f.sum().item(), f.abs().sum().item(), f.norm().item()])
+        vals.append(f[idx])
+    return np.array(sums, dtype=np.float64).reshape(-1, 3), torch.cat(vals).numpy()
+
+
+def flat_outputs(out):
+    """The tensors of a network's (nested) output tuple, in order."""
+    if torch.is_tensor(out):
+        return [out]
+    return [t for o in out for t in flat_outputs(o)]
+
+
+def pairing():
+    """tests/golden/reference_pairing.npz: what tests/test_oracle_vs_reference.py pairs the oracle against -- the reference's own classes at seed 5
+    (state_dict keys and every tensor), their eval forward on 1x3x96x96 and one agg / one mldg train step on 96 x 96 batches (losses, memory,
+    gradients, post-step state)."""
+    import copy
+    torch.set_num_threads(8)
+    rv3, rv2, _ = IR.load()
+    crit = torch.nn.CrossEntropyLoss(reduction='mean', ignore_index=255)
+    args = synth.model_args()
+    fac = {'v3': rv3.DeepR50V3PlusD, 'v2': rv2.DeepR50V2D}
+    g = {}
+
+    def put(prefix, tensors):
+        g[prefix + '_sums'], g[prefix + '_sample'] = fingerprint(tensors)
+    for which in ('v3', 'v2'):
+        torch.manual_seed(5)
+        net = fac[which](args, 19, crit, crit)
+        sd = net.state_dict()
+        g['init_%s_keys' % which] = np.array(list(sd.keys()))
+        put('init_%s_state' % which, list(sd.values()))
+        g['init_%s_memory' % which] = net.memory.m_items.numpy()
+        net = synth.load_det_weights(fac[which](args, 19, crit, crit)).eval()
+        x, _ = synth.make_batch(1, 96)
+        with torch.no_grad():
+            put('eval_%s_out' % which, flat_outputs(net(x)))
+
+    def fresh():
+        net = synth.load_det_weights(rv3.DeepR50V3PlusD(args, 19, crit, crit))
+        net.dsn[3].p = 0.0
+        return net
+    net = fresh()
+    x, y = synth.make_batch(2, 96)
+    opt, _ = harness.make_optimizer(net)
+    losses = harness.agg_train_step(net, opt, x, y)
+    g['agg_loss_keys'] = np.array(list(losses.keys()))
+    g['agg_losses'] = np.array([losses[k].item() for k in losses], dtype=np.float32)
+    g['agg_memory'] = net.memory.m_items.numpy()
+    put('agg_grad', [p.grad for p in net.parameters()])
+    put('agg_state', list(net.state_dict().values()))
+    net = fresh()
+    x, y = synth.make_batch(4, 96)
+    u1, u2 = copy.deepcopy(net), copy.deepcopy(net)
+    opt, _ = harness.make_optimizer(net)
+    losses = harness.mldg_train_step(net, u1, u2, opt, x[:2], y[:2], x[2:], y[2:])
+    g['mldg_loss_keys'] = np.array(list(losses.keys()))
+    g['mldg_losses'] = np.array([float(losses[k]) for k in losses], dtype=np.float64)
+    g['mldg_memory'] = net.memory.m_items.numpy()
+    put('mldg_state', list(net.state_dict().values()))
+    np.savez_compressed(os.path.join(OUT, 'reference_pairing.npz'), **g)
+    print('reference pairing written to', OUT)
+
+
 if __name__ == '__main__':
-    main()
+    pairing() if sys.argv[1:] == ['pairing'] else main()

@@ -97,7 +97,7 @@ def test_bench_py_gpus_2_self_launch_on_the_gpu_box(tmp_path, dtype):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     env['PM_BENCH_BACKEND'] = 'gloo'
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--size', '256', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-                        '--dtype', dtype], env=env, capture_output=True, text=True, timeout=900)
+                        '--dtype', dtype, '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -113,3 +113,35 @@ def test_bench_py_gpus_2_self_launch_on_the_gpu_box(tmp_path, dtype):
     # each stage's first block (2 -> 1 per direction, four stages); what is left: 49 + 49 SyncBN exchanges, the gradient buckets, the memory-slot sum
     assert 100 <= c['collectives_per_step'] <= 128, c['collectives_per_step']
     assert c['host_enqueue_ms'] > 0 and c['step_form'] == 'eager launches'
+
+
+def test_dump_outputs_is_for_the_train_workload(tmp_path):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'config5', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and '--dump-outputs' in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): the headline fields only, the side measurements null or absent; --dump-outputs writes float32 arrays of the
+    last timed step, within 64 MB, and its total loss is the line's final_loss."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip('needs a GPU')
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--size', '256', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path / 'out')], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['ms_per_step'] > 0 and d['unit'] == 'imgs/sec' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert abs(d['value'] - 8 / (d['ms_per_step'] * 1e-3)) < 1e-2 * d['value']
+    assert d['roofline'] is None and d['cpu_baseline'] is None and 'side' not in d and d['config']['host_enqueue_ms'] is None
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / 'out'))
+    assert names == sorted(d['dumped_outputs']) and {'loss_total', 'memory', 'parameters_sample', 'bn_running_moments'} <= set(names)
+    arrays = {n: np.load(tmp_path / 'out' / (n + '.npy')) for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert round(float(arrays['loss_total'][0]), 5) == d['config']['final_loss']

@@ -1,85 +1,104 @@
-"""Pins the oracle against the reference ITSELF (imported from /root/reference; build container only).
-Skipped where the reference tree is absent (GPU box)."""
+"""Pins the oracle against the reference ITSELF: tests/golden/reference_pairing.npz holds what the reference's own classes produce at the same
+seeds, weights and inputs (captured by `python -m oracle.make_golden pairing`), so the pairing runs on every host. Tensors too large to store are
+compared through oracle.make_golden.fingerprint. The seeded initialisation is exact everywhere. Computed values are exact at the capturing thread
+count; on other hosts OpenMP / oneDNN / BLAS reduce in another order, which the tolerances absorb at about five times the spread measured over
+thread counts and instruction sets: 2e-5 (as tests/test_oracle_golden.py) for forward values and losses, 2e-3 of each tensor's scale for the
+post-step state, 5e-3 on the sums and norms of the gradients of the batch-2 step and 5e-2 of their scale on single values."""
+import copy
+import os
+
+import numpy as np
 import pytest
 import torch
 
-from oracle import import_reference as IR
+from oracle.make_golden import fingerprint, flat_outputs
 from oracle.ref_cpu import deeplab, harness
 from pinthememory_amd import synth
 
-pytestmark = pytest.mark.skipif(not IR.available(), reason='reference tree only exists in the build container')
 CRIT = torch.nn.CrossEntropyLoss(reduction='mean', ignore_index=255)
+TOL = 2e-5
+FAC = {'v3': deeplab.DeepR50V3PlusD, 'v2': deeplab.DeepR50V2D}
 
 
 @pytest.fixture(scope='module')
-def refmods():
-    return IR.load()
+def ref():
+    with np.load(os.path.join(os.path.dirname(__file__), 'golden', 'reference_pairing.npz'), allow_pickle=False) as g:
+        return dict(g)
 
 
-def _pair(refmods, which, seed=None):
-    rv3, rv2, _ = refmods
-    args = synth.model_args()
-    fac = {'v3': (rv3.DeepR50V3PlusD, deeplab.DeepR50V3PlusD), 'v2': (rv2.DeepR50V2D, deeplab.DeepR50V2D)}[which]
+def close(a, b, tol=TOL):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and (np.max(np.abs(a - b) / (1.0 + np.abs(b))) <= tol if a.size else True)
+
+
+def same(ref, prefix, tensors, rtol=TOL, sample_rtol=None, atol=0.0):
+    """Every tensor against its reference fingerprint, on the tensor's own scale: the sum within rtol x sum of |x|, sum of |x| and norm within rtol,
+    the sampled values within sample_rtol (default rtol) x the tensor's rms (+ atol: the gradient of a bias that a BatchNorm follows is rounding
+    noise around 0)."""
+    sample_rtol = rtol if sample_rtol is None else sample_rtol
+    sums, sample = fingerprint(tensors)
+    rs, rv = ref[prefix + '_sums'], ref[prefix + '_sample']
+    if sums.shape != rs.shape or sample.shape != rv.shape:
+        return False
+    n = np.array([t.numel() for t in tensors])
+    rms = np.repeat(rs[:, 2] / np.sqrt(n), np.minimum(n, 64))
+    return bool(np.all(np.abs(sums[:, 0] - rs[:, 0]) <= rtol * rs[:, 1] + atol) and np.all(np.abs(sums[:, 1:] - rs[:, 1:]) <= rtol * rs[:, 1:] + atol)
+                and np.all(np.abs(sample - rv) <= sample_rtol * rms + atol))
+
+
+def make(which, seed=None):
     if seed is not None:
         torch.manual_seed(seed)
-    ref = fac[0](args, 19, CRIT, CRIT)
-    if seed is not None:
-        torch.manual_seed(seed)
-    mine = fac[1](args, 19, CRIT, CRIT)
-    return ref, mine
+    return FAC[which](synth.model_args(), 19, CRIT, CRIT)
 
 
 @pytest.mark.parametrize('which', ['v3', 'v2'])
-def test_same_seed_same_init_and_keys(refmods, which):
-    ref, mine = _pair(refmods, which, seed=5)
-    sr, sm = ref.state_dict(), mine.state_dict()
-    assert list(sr.keys()) == list(sm.keys())
-    assert all(torch.equal(sr[k], sm[k]) for k in sr)
-    assert torch.equal(ref.memory.m_items, mine.memory.m_items)
+def test_same_seed_same_init_and_keys(ref, which):
+    mine = make(which, seed=5)
+    sm = mine.state_dict()
+    assert list(sm.keys()) == ref['init_%s_keys' % which].tolist()
+    sums, sample = fingerprint(list(sm.values()))
+    assert np.array_equal(sample, ref['init_%s_state_sample' % which])               # torch's seeded draws: the same bits on every host
+    assert close(sums, ref['init_%s_state_sums' % which], 1e-9)                      # float64 sums: only their summation order may differ
+    assert close(mine.memory.m_items.numpy(), ref['init_%s_memory' % which], 1e-6)   # F.normalize of the seeded draw
 
 
 @pytest.mark.parametrize('which', ['v3', 'v2'])
-def test_eval_forward_bit_equal(refmods, which):
-    ref, mine = _pair(refmods, which)
-    synth.load_det_weights(ref), synth.load_det_weights(mine)
-    ref.eval(), mine.eval()
+def test_eval_forward_bit_equal(ref, which):
+    mine = synth.load_det_weights(make(which)).eval()
     x, _ = synth.make_batch(1, 96)
     with torch.no_grad():
-        a, b = ref(x), mine(x)
-    assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[2])
-    assert all(torch.equal(u, v) for u, v in zip(a[1], b[1]))
+        out = flat_outputs(mine(x))
+    assert same(ref, 'eval_%s_out' % which, out)
 
 
-def test_agg_train_step_bit_equal(refmods):
-    ref, mine = _pair(refmods, 'v3')
-    synth.load_det_weights(ref), synth.load_det_weights(mine)
-    ref.dsn[3].p = mine.dsn[3].p = 0.0
+def _fresh():
+    net = synth.load_det_weights(make('v3'))
+    net.dsn[3].p = 0.0
+    return net
+
+
+def test_agg_train_step_bit_equal(ref):
+    mine = _fresh()
     x, y = synth.make_batch(2, 96)
-    o1, _ = harness.make_optimizer(ref)
-    o2, _ = harness.make_optimizer(mine)
-    l1, l2 = harness.agg_train_step(ref, o1, x, y), harness.agg_train_step(mine, o2, x, y)
-    assert all(torch.equal(l1[k], l2[k]) for k in l1)
-    assert torch.equal(ref.memory.m_items, mine.memory.m_items)
-    gr, gm = dict(ref.named_parameters()), dict(mine.named_parameters())
-    assert all(torch.equal(gr[k].grad, gm[k].grad) for k in gr)
-    sr, sm = ref.state_dict(), mine.state_dict()
-    assert all(torch.equal(sr[k], sm[k]) for k in sr)
+    opt, _ = harness.make_optimizer(mine)
+    losses = harness.agg_train_step(mine, opt, x, y)
+    assert list(losses.keys()) == ref['agg_loss_keys'].tolist()
+    assert close([losses[k].item() for k in losses], ref['agg_losses'])
+    assert close(mine.memory.m_items.numpy(), ref['agg_memory'])
+    assert same(ref, 'agg_grad', [p.grad for p in mine.parameters()], 5e-3, 5e-2, 1e-7)
+    assert same(ref, 'agg_state', list(mine.state_dict().values()), 2e-3)
 
 
-def test_mldg_train_step_bit_equal(refmods):
-    """train_memory_mldg semantics (train.py:493-632) restated in oracle.ref_cpu.harness, driven on the reference's own
-    model classes vs the oracle's: identical losses, memory, gradients and post-step parameters."""
-    import copy
-    ref, mine = _pair(refmods, 'v3')
-    synth.load_det_weights(ref), synth.load_det_weights(mine)
-    ref.dsn[3].p = mine.dsn[3].p = 0.0
+def test_mldg_train_step_bit_equal(ref):
+    """train_memory_mldg semantics (train.py:493-632) restated in oracle.ref_cpu.harness, against the same step driven on the reference's own
+    model classes: losses, memory and post-step parameters."""
+    mine = _fresh()
     x, y = synth.make_batch(4, 96)
-    res = []
-    for net in (ref, mine):
-        u1, u2 = copy.deepcopy(net), copy.deepcopy(net)
-        opt, _ = harness.make_optimizer(net)
-        res.append(harness.mldg_train_step(net, u1, u2, opt, x[:2], y[:2], x[2:], y[2:]))
-    assert all(torch.equal(res[0][k], res[1][k]) for k in res[0])
-    assert torch.equal(ref.memory.m_items, mine.memory.m_items)
-    sr, sm = ref.state_dict(), mine.state_dict()
-    assert all(torch.equal(sr[k], sm[k]) for k in sr)
+    u1, u2 = copy.deepcopy(mine), copy.deepcopy(mine)
+    opt, _ = harness.make_optimizer(mine)
+    losses = harness.mldg_train_step(mine, u1, u2, opt, x[:2], y[:2], x[2:], y[2:])
+    assert list(losses.keys()) == ref['mldg_loss_keys'].tolist()
+    assert close([float(losses[k]) for k in losses], ref['mldg_losses'])
+    assert close(mine.memory.m_items.numpy(), ref['mldg_memory'])
+    assert same(ref, 'mldg_state', list(mine.state_dict().values()), 2e-3)

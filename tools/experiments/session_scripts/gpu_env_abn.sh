@@ -5,6 +5,6 @@ REPS=$1; shift
 for rep in $(seq $REPS); do
   for E in "$@"; do
     if [ "$E" = "-" ]; then EV=""; else EV="$E"; fi
-    env $EV timeout 600 python bench.py --no-cpu-baseline --no-profile --steps 10 --warmup 3 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-52s' % '$E', d['ms_per_step'])"
+    env $EV timeout 600 python bench.py --full --no-cpu-baseline --no-profile --steps 10 --warmup 3 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-52s' % '$E', d['ms_per_step'])"
   done
 done

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace -d $O/kt -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-profile > $O/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace -d $O/kt -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-profile > $O/kt.log 2>&1
 DB=$(find $O/kt -name '*.db' | head -1)
 grep '^{' $O/kt.log | cut -c1-160
 python - $DB <<'PY' | tee $O/gaps.txt

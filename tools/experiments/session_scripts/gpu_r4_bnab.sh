@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q -k "act16 or bf16_activations or config3_bf16_mfma" > $O/pytest.log 2>&1; echo "pytest exit $?"; tail -5 $O/pytest.log
 for rep in 1 2; do for F in 0 1; do
-  PM_BN16_FIXED=$F timeout 600 python bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f${F}_$rep.log 2>&1
+  PM_BN16_FIXED=$F timeout 600 python bench.py --full --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f${F}_$rep.log 2>&1
   grep '^{' $O/bench_f${F}_$rep.log | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('fixed=$F rep $rep ms/step', d['ms_per_step'])"
 done; done
 for F in 0 1; do

@@ -9,4 +9,4 @@ echo "== conv16 everywhere"; PROBE_CONV16=2 timeout 300 python tools/conv16_prob
 echo "== default routing"; timeout 300 python tools/conv16_probe.py 2>&1 | grep -v amdgpu.ids
 } > $O/c16probe.txt 2>&1
 cat $O/c16probe.txt
-for i in 1 2; do timeout 600 python bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-side 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bf16 ms/step', d['ms_per_step'], 'dominant', d['roofline']['kernel'][:40], d['roofline']['achieved'], 'all conv', d['roofline']['all_conv_kernels']['achieved'])"; done
+for i in 1 2; do timeout 600 python bench.py --full --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-side 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bf16 ms/step', d['ms_per_step'], 'dominant', d['roofline']['kernel'][:40], d['roofline']['achieved'], 'all conv', d['roofline']['all_conv_kernels']['achieved'])"; done

@@ -6,7 +6,7 @@ O=gpurun_out/$1; mkdir -p $O
 K="$2"; shift 2
 if [ -n "$K" ]; then timeout 1500 python -m pytest tests -m gpu -x -q -k "$K" > $O/pytest.log 2>&1; echo "pytest exit $?"; tail -25 $O/pytest.log; fi
 for DT in "$@"; do
-  PM_PROFILE_DUMP=$O/prof_dump_$DT.txt timeout 600 python bench.py --dtype $DT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$DT.log 2>&1; echo "bench $DT exit $?"
+  PM_PROFILE_DUMP=$O/prof_dump_$DT.txt timeout 600 python bench.py --full --dtype $DT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$DT.log 2>&1; echo "bench $DT exit $?"
   grep '^{' $O/bench_$DT.log > $O/bench_$DT.json
   python - $O/bench_$DT.json <<'PY' || tail -30 $O/bench_$DT.log
 import sys, json

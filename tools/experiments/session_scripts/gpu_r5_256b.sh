@@ -6,6 +6,6 @@ timeout 900 python -m pytest tests/test_hip_kernels.py -x -q -m gpu -k "conv_bf1
 timeout 600 python -m pytest tests/test_model_parity.py -x -q -m gpu -k "bf16" > $O/pytest_model.log 2>&1; tail -4 $O/pytest_model.log
 echo "== default routing"; PROBE_CONV16=1 timeout 300 python tools/conv16_probe.py 2>&1 | grep -v amdgpu | tee $O/probe_route1.txt
 for i in 1 2 3; do
-  PM_C16W=0 timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('PM_C16W=0 (graph)', j['ms_per_step'])"
-  timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('default  (graph)', j['ms_per_step'])"
+  PM_C16W=0 timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('PM_C16W=0 (graph)', j['ms_per_step'])"
+  timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('default  (graph)', j['ms_per_step'])"
 done

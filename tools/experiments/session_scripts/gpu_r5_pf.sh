@@ -9,6 +9,6 @@ echo "== shipped"; PROBE_CONV16=1 timeout 300 python tools/conv16_probe.py 2>&1 
 echo "== prefetch"; PM_LIB=tools/ab/libpinmem_pf.so PROBE_CONV16=1 timeout 300 python tools/conv16_probe.py 2>&1 | grep "aspp 3x3 d12\|final1\|sum"
 done
 for i in 1 2 3; do
-  timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('shipped  (graph)', j['ms_per_step'])"
-  PM_LIB=tools/ab/libpinmem_pf.so timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('prefetch (graph)', j['ms_per_step'])"
+  timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('shipped  (graph)', j['ms_per_step'])"
+  PM_LIB=tools/ab/libpinmem_pf.so timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('prefetch (graph)', j['ms_per_step'])"
 done

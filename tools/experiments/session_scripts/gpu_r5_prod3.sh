@@ -9,6 +9,6 @@ echo "== previous build"; PM_LIB=tools/ab/libpinmem_prev.so PROBE_CONV16=1 timeo
 echo "== this build"; PROBE_CONV16=1 timeout 300 python tools/conv16_probe.py 2>&1 | grep -v amdgpu | tee $O/probe_new_$rep.txt
 done
 for i in 1 2 3; do
-  PM_LIB=tools/ab/libpinmem_prev.so timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('previous (graph)', j['ms_per_step'])"
-  timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('this     (graph)', j['ms_per_step'])"
+  PM_LIB=tools/ab/libpinmem_prev.so timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('previous (graph)', j['ms_per_step'])"
+  timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --graph --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('this     (graph)', j['ms_per_step'])"
 done

@@ -7,6 +7,6 @@ for r in 1 6 1 6; do
   echo "== PROBE_CONV16=$r (1 default: streaming 1x1 kernel on, 6: off)"; PROBE_CONV16=$r timeout 300 python tools/conv16_probe.py 2>&1 | grep "1x1" | tee -a $O/probe_route$r.txt
 done
 for i in 1 2; do
-  PM_PW16=0 timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('PM_PW16=0', j['ms_per_step'])"
-  timeout 600 python bench.py --no-cpu-baseline --dtype bf16 --no-profile --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('default ', j['ms_per_step'])"
+  PM_PW16=0 timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('PM_PW16=0', j['ms_per_step'])"
+  timeout 600 python bench.py --full --no-cpu-baseline --dtype bf16 --no-profile --steps 20 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('default ', j['ms_per_step'])"
 done

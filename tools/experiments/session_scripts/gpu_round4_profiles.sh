@@ -13,10 +13,10 @@ for DT in f32 bf16; do
 done
 bash tools/gpu_mem_path.sh $1/mem | tail -14
 cp $O/mem/mem_path_hbm_counters.json profiles/${P}_memory_path_hbm_counters.json
-PM_PROFILE_DUMP=$O/prof_dump.txt timeout 900 python bench.py > $O/bench.log 2>&1; grep '^{' $O/bench.log > $O/bench_1gpu_full.json; cut -c1-160 $O/bench_1gpu_full.json
+PM_PROFILE_DUMP=$O/prof_dump.txt timeout 900 python bench.py --full > $O/bench.log 2>&1; grep '^{' $O/bench.log > $O/bench_1gpu_full.json; cut -c1-160 $O/bench_1gpu_full.json
 python tools/conv_shapes.py $O/prof_dump.txt 2 200 > $O/conv_shapes.txt 2>&1; head -2 $O/conv_shapes.txt
 python tools/conv_shapes.py $O/prof_dump.txt.bf16 2 200 > $O/conv_shapes_bf16.txt 2>&1; head -2 $O/conv_shapes_bf16.txt
-timeout 600 python bench.py --dtype bf16 --no-cpu-baseline > $O/bench_bf16.log 2>&1; grep '^{' $O/bench_bf16.log > $O/bench_1gpu_bf16.json; cut -c1-160 $O/bench_1gpu_bf16.json
+timeout 600 python bench.py --full --dtype bf16 --no-cpu-baseline > $O/bench_bf16.log 2>&1; grep '^{' $O/bench_bf16.log > $O/bench_1gpu_bf16.json; cut -c1-160 $O/bench_1gpu_bf16.json
 for DT in f32 bf16; do
   timeout 600 rocprofv3 --kernel-trace -d $O/kt_$DT -- python bench.py --dtype $DT --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-side > $O/kt_$DT.log 2>&1
   python tools/rocpd_stats.py $(find $O/kt_$DT -name '*.db' | head -1) $O/kernel_stats_$DT.csv 4 | head -2
@@ -31,8 +31,8 @@ timeout 600 python bench.py --workload mldg --dtype bf16 --steps 5 --warmup 2 2>
 timeout 600 python bench.py --workload config5 --steps 5 --warmup 2 2>/dev/null | grep '^{' > $O/bench_config5.json; cut -c1-160 $O/bench_config5.json
 timeout 600 python bench.py --workload meminit --steps 5 --warmup 2 2>/dev/null | grep '^{' > $O/bench_meminit.json; cut -c1-160 $O/bench_meminit.json
 timeout 600 python bench.py --no-cpu-baseline --no-profile --input-edge 2>/dev/null | grep '^{' > $O/bench_input_edge.json; cut -c1-160 $O/bench_input_edge.json
-PM_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --size 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo.log 2>&1; grep '^{' $O/bench_2rank_gloo.log | cut -c1-200
+PM_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --size 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo.log 2>&1; grep '^{' $O/bench_2rank_gloo.log | cut -c1-200
 timeout 300 python tools/clock_probe_step.py bf16 10 2>&1 | grep -v amdgpu.ids > $O/clock_probe_step_bf16.txt; tail -4 $O/clock_probe_step_bf16.txt
 timeout 300 python tools/clock_probe_step.py f32 10 2>&1 | grep -v amdgpu.ids > $O/clock_probe_step_f32.txt; tail -3 $O/clock_probe_step_f32.txt
 timeout 600 python tools/soak.py 6 --deterministic 2>&1 | grep steps > $O/soak_f32.txt; timeout 600 python tools/soak.py 6 --deterministic --bf16 2>&1 | grep steps > $O/soak_bf16.txt; paste -d'\n' $O/soak_f32.txt $O/soak_bf16.txt | cut -c1-120
-timeout 900 python bench.py --steps 3 --warmup 1 --cpu-batch 8 --no-profile --no-side 2>/dev/null | grep '^{' > $O/bench_cpu_batch8.json; python -c "import json; print(json.load(open('$O/bench_cpu_batch8.json'))['cpu_baseline'])" | cut -c1-300
+timeout 900 python bench.py --full --steps 3 --warmup 1 --cpu-batch 8 --no-profile --no-side 2>/dev/null | grep '^{' > $O/bench_cpu_batch8.json; python -c "import json; print(json.load(open('$O/bench_cpu_batch8.json'))['cpu_baseline'])" | cut -c1-300

@@ -6,6 +6,6 @@ O=gpurun_out/$1; mkdir -p $O; shift
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg PM_PROFILE_DUMP=$O/shapes_$i.txt timeout 600 python bench.py --no-cpu-baseline --no-side > $O/bench_$i.json 2> $O/bench_$i.err
+  env $cfg PM_PROFILE_DUMP=$O/shapes_$i.txt timeout 600 python bench.py --full --no-cpu-baseline --no-side > $O/bench_$i.json 2> $O/bench_$i.err
   echo "[$i] $cfg: $(python -c "import json,sys; d=json.loads(open('$O/bench_$i.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], 'conv', d['roofline']['all_conv_kernels']['ms_per_step'])")"
 done

@@ -11,7 +11,7 @@ for g in 3 1; do
 done 2>&1 | tee $O/wgradxcd.log
 unset ONE_MODE
 timeout 600 python -m pytest tests/test_hip_kernels.py -m gpu -x -q -k "conv or wino or split or wgrad" 2>&1 | tail -2
-run() { tag=$1; shift; env "$@" timeout 600 python bench.py --no-cpu-baseline --no-side > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "$tag: $(python -c "import json,sys; d=json.loads(open('$O/bench_$tag.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], 'conv', d['roofline']['all_conv_kernels']['ms_per_step'])")"; }
+run() { tag=$1; shift; env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-side > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "$tag: $(python -c "import json,sys; d=json.loads(open('$O/bench_$tag.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], 'conv', d['roofline']['all_conv_kernels']['ms_per_step'])")"; }
 run b3 PM_BATCH_XCD=3
 run b1 PM_BATCH_XCD=1
 run b3b PM_BATCH_XCD=3
