@@ -126,7 +126,8 @@ int pm_conv_bwd_weight(const pm_tensor* x, const pm_tensor* dy, float* dw_krsc, 
                        void* ws, size_t ws_bytes, void* stream);
 
 /* ---- ROUTING (round 6): the library's ONLY mutable global state is one pm_routing value -- which kernel takes a call; never WHAT is computed (every route is parity-tested
- * against the same oracle). It is initialised from the PM_* environment when the library is loaded (the defaults below) and replaced as a whole by pm_routing_set: a
+ * against the same oracle). It is initialised when the library is loaded from exactly six environment variables (PM_WINO_FUSED, PM_CONV16, PM_C16W, PM_C16P, PM_WGRAD16,
+ * PM_SPLIT: the defaults below), and the library reads no other environment, then or later. pm_routing_set replaces it as a whole: a
  * production caller sets it once before the first pm_conv_* call, or never, and the library is then re-entrant with an immutable kernel table. The pm_set_*
  * entry points further down are thin wrappers that change ONE field -- for kernel tests that must reach a specific kernel and same-box A/B runs. Contract for both: call from
  * one thread while no other thread is inside a pm_conv_* entry point; repeat size queries (pm_conv_workspace, pm_conv_wxf_bytes, ...) after a change. */

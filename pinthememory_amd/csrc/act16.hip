@@ -616,8 +616,7 @@ int pm16_bn_apply_mask(const pm_tensor* x, const float* mean, const float* invst
   const pm_bf16 *px = (const pm_bf16*)x->ptr, *pr = res ? (const pm_bf16*)res->ptr : nullptr;
   pm_bf16* py = (pm_bf16*)y->ptr;
   const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, cq = x->c >> 3;
-  static const int fixed_on = getenv("PM_BN16_FIXED") ? atoi(getenv("PM_BN16_FIXED")) : 1;      // A/B knob
-  if (fixed_on && fixed_ok(x->c) && pm_pixels(x) > 0) {
+  if (fixed_ok(x->c) && pm_pixels(x) > 0) {
     const long P = pm_pixels(x);
     const dim3 grid(fixed_grid(P, x->c));
     const int cg = x->c / V;
@@ -715,8 +714,7 @@ int pm16_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* 
   const int C = x->c;
   const bool dev_count = !(count > 0.f);
   const float host_inv_n = dev_count ? 0.f : 1.f / count;
-  static const int fixed_on = getenv("PM_BN16_FIXED") ? atoi(getenv("PM_BN16_FIXED")) : 1;
-  if (fixed_on && fixed_ok(C) && pm_pixels(x) > 0) {
+  if (fixed_ok(C) && pm_pixels(x) > 0) {
     const long P = pm_pixels(x);
     const dim3 grid(fixed_grid(P, C));
     const int cg = C / V;

@@ -298,11 +298,8 @@ template <int BM, int BN, int WM, int WN, int NST, bool STATS>
 void launch_tile_s(const pm_conv16& k, dim3 grid, hipStream_t st) {
   constexpr size_t stage_bytes = (size_t)NST * (BM + BN) * BKB, ep_bytes = (size_t)4 * 32 * (BN / WN + 4) * sizeof(float);
   constexpr size_t smem = stage_bytes > ep_bytes ? stage_bytes : ep_bytes;
-  static const bool attr_set = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16_kernel<BM, BN, WM, WN, NST, STATS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();
-  (void)attr_set;
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&conv16_kernel<BM, BN, WM, WN, NST, STATS>), 160 * 1024);
   hipLaunchKernelGGL((conv16_kernel<BM, BN, WM, WN, NST, STATS>), grid, dim3(256), smem, st, k);
 }
 template <int BM, int BN, int WM, int WN, int NST>
@@ -325,21 +322,19 @@ struct WidePick {
   double cost;      // in units of one wide K-step on a full chip
 };
 WidePick wide_pick(const pm_conv16* k, int only_cfg = -1) {
-  static const int force_ks = getenv("PM_C16W_KS") ? atoi(getenv("PM_C16W_KS")) : 0;
-  static const double ovh = getenv("PM_C16W_OVH") ? atof(getenv("PM_C16W_OVH")) : 10.0;      // prologue + epilogue of a block, in K-steps
+  constexpr double OVH = 10.0;      // prologue + epilogue of a block, in K-steps
   WidePick best{false, 0, 0, 0, 1e30};
   const bool forced = pm_route.conv16_wide >= 2;      // kernel tests: every shape the kernel can express, ragged rows / columns and single K-steps included
   if (!forced && (k->Nn < 128 || k->M < 2048 || k->ksteps < 4)) return best;
-  static const int env_cfg = getenv("PM_C16W_CFG") ? atoi(getenv("PM_C16W_CFG")) : -1;      // 0: 256 x 128, 1: 128 x 256, 2: 256 x 256 (two LDS stages)
-  const int force_cfg = only_cfg >= 0 ? only_cfg : (pm_route.conv16_wide == 3 ? 2 : env_cfg);            // pm_set_conv16(7): the 256 x 256 tile on every shape (kernel tests)
+  // cfg 0: 256 x 128, 1: 128 x 256, 2: 256 x 256 (two LDS stages)
+  const int force_cfg = only_cfg >= 0 ? only_cfg : (pm_route.conv16_wide == 3 ? 2 : -1);            // pm_set_conv16(7): the 256 x 256 tile on every shape (kernel tests)
   for (int cfg = 0; cfg < 3; ++cfg) {
     if (force_cfg >= 0 && cfg != force_cfg) continue;
     const int bm = cfg == 1 ? 128 : 256, bn = cfg == 0 ? 128 : 256;
-    if (cfg == 2 && force_cfg != 2) continue;      // 256 x 256 only where asked for (the planner's rule below, PM_C16W_CFG, pm_set_conv16(7))
+    if (cfg == 2 && force_cfg != 2) continue;      // 256 x 256 only where asked for (the planner's rule below, pm_set_conv16(7))
     const long tiles = (long)pm_cdiv(k->M, bm) * pm_cdiv(k->Nn, bn);
     const double fill = ((double)k->M * k->Nn) / ((double)tiles * bm * bn);      // padded rows / columns are wasted work
     for (int ks = 1; ks <= 16; ++ks) {
-      if (force_ks && ks != force_ks) continue;
       if (ks > 1 && k->ksteps / ks < (forced ? 2 : 8)) break;
       const int per = pm_cdiv(k->ksteps, ks);
       const int kse = pm_cdiv(k->ksteps, per);
@@ -348,7 +343,7 @@ WidePick wide_pick(const pm_conv16* k, int only_cfg = -1) {
       // split-K slabs: fp32 partial tiles written and read back by the reduce (bytes / ~4 TB/s, in wide K-steps of ~1.1 us measured on this kernel)
       const double slab = kse > 1 ? (double)kse * k->M * k->Nn * 8.0 / 4e12 / 1.1e-6 : 0.0;
       // a 256 x 256 step covers twice the area of a 256 x 128 one at ~1.3 x its rate (128 vs 85 FLOP per staged byte)
-      const double cost = (double)rounds * (per + ovh) / fill * (cfg == 1 ? 1.03 : (cfg == 2 ? 1.5 : 1.0)) + slab;
+      const double cost = (double)rounds * (per + OVH) / fill * (cfg == 1 ? 1.03 : (cfg == 2 ? 1.5 : 1.0)) + slab;
       if (cost < best.cost) best = WidePick{true, bm, bn, kse, cost};
     }
   }
@@ -356,8 +351,6 @@ WidePick wide_pick(const pm_conv16* k, int only_cfg = -1) {
 }
 }  // namespace
 void pm_conv16_plan(pm_conv16* k) {
-  static const int force_bm = getenv("PM_C16_BM") ? atoi(getenv("PM_C16_BM")) : 0;
-  static const int force_ks = getenv("PM_C16_KS") ? atoi(getenv("PM_C16_KS")) : 0;
   k->wide = 0;
   k->bn = k->Nn > 64 ? 128 : 64;
   k->tiles_n = pm_cdiv(k->Nn, k->bn);
@@ -365,26 +358,18 @@ void pm_conv16_plan(pm_conv16* k) {
   // rounds of the 256 CUs x 2 resident blocks: take 64-row tiles when 128-row tiles would leave the last round under half full or not fill the chip once
   auto waste = [](long tiles) { const long r = (tiles + 511) / 512; return (double)(r * 512) / (double)tiles; };
   k->bm = (t128 < 512 || waste(t128) > 1.25 * waste(t64)) ? 64 : 128;
-  if (force_bm) k->bm = force_bm;
   k->tiles_m = pm_cdiv(k->M, k->bm);
   const long tiles = (long)k->tiles_m * k->tiles_n;
   int ks = 1;
   if (tiles < 256 && k->ksteps >= 16) ks = (int)std::min<long>(std::min<long>(8, k->ksteps / 8), (512 + tiles - 1) / tiles);
-  if (force_ks) ks = std::min(force_ks, k->ksteps);
   k->ksteps_per = pm_cdiv(k->ksteps, ks);
   k->ksplit = pm_cdiv(k->ksteps, k->ksteps_per);
   k->c_split = (long)k->M * k->Nn;
-  // Round 5, measured and left OFF (PM_C16_FULLN=1 | 2 enables it for A/B runs): a 64 x 256 "full-N" tile for the HBM-bound 1x1 convolutions with a short reduction and a
+  // Round 5, measured and left out: a 64 x 256 "full-N" tile for the HBM-bound 1x1 convolutions with a short reduction and a
   // wide output (64 -> 256 on the 192 x 192 maps, 128 -> 512 on 96 x 96, 256 -> 1024 on 48 x 48), so that the activation rows are fetched once per 256 output channels.
   // tools/conv16_probe.py, same box, alternated: 64 -> 256 253-260 -> 243-252 TF, 128 -> 512 288-297 -> 259-260, 256 -> 1024 360-369 -> 343-347: the second fetch of
   // the rows comes from L2 and was never the bound -- standalone the 64 -> 256 launch already moves its 189 MB in 37 us (5.1 TB/s: the output write), and the wider
   // tile only takes resident blocks away (80 KB of LDS stages per block instead of 48). The in-step figure of that shape (60 us) is not a tiling problem.
-  static const int fulln = getenv("PM_C16_FULLN") ? atoi(getenv("PM_C16_FULLN")) : 0;
-  if (!force_bm && k->Nn >= 256 && k->Nn % 256 == 0 && ((fulln == 1 && k->ksteps <= 4 && k->kh * k->kw == 1) || fulln >= 2) && ks == 1) {
-    k->bm = 64, k->bn = 256;
-    k->tiles_m = pm_cdiv(k->M, 64), k->tiles_n = k->Nn / 256;
-    k->ksteps_per = k->ksteps, k->ksplit = 1;
-  }
   if (pm_route.conv16_wide > 0) {
     // Where the wide tiles win (tools/conv16_probe.py on an MI355X, round 5, profiles/r05_conv16w_probe.txt), all with the 256 x 256 two-stage form (128 FLOP per staged
     // byte, full-N for the 256-channel outputs): the DEEP reductions -- the ASPP 3x3 2048 -> 256 on the 48 x 48 maps (288 K-steps: 690 TF narrow, 764 with skipped filter
@@ -438,8 +423,7 @@ int pm_conv16_launch(const pm_conv16* k0, hipStream_t st) {
   pm_conv16 k = *k0;
   dim3 grid(k.tiles_m * k.tiles_n, 1, k.ksplit);
   const bool one = k.ksteps_per == 1;      // a single K-step per block: one LDS stage, four blocks per CU
-  if (k.bm == 64 && k.bn == 256) one ? launch_tile<64, 256, 1, 4, 1>(k, grid, st) : launch_tile<64, 256, 1, 4, 2>(k, grid, st);      // full-N tile of the short 1x1 reductions
-  else if (k.bm == 128 && k.bn == 128) one ? launch_tile<128, 128, 2, 2, 1>(k, grid, st) : launch_tile<128, 128, 2, 2, 2>(k, grid, st);
+  if (k.bm == 128 && k.bn == 128) one ? launch_tile<128, 128, 2, 2, 1>(k, grid, st) : launch_tile<128, 128, 2, 2, 2>(k, grid, st);
   else if (k.bm == 64 && k.bn == 128) one ? launch_tile<64, 128, 2, 2, 1>(k, grid, st) : launch_tile<64, 128, 2, 2, 2>(k, grid, st);
   else if (k.bm == 128 && k.bn == 64) one ? launch_tile<128, 64, 2, 2, 1>(k, grid, st) : launch_tile<128, 64, 2, 2, 2>(k, grid, st);
   else if (k.bm == 64 && k.bn == 64) one ? launch_tile<64, 64, 2, 2, 1>(k, grid, st) : launch_tile<64, 64, 2, 2, 2>(k, grid, st);

@@ -3,7 +3,7 @@
 //     of step k and fly under its 32 MFMAs per wave. THE FORM THE PLANNER USES: the deep reductions (ASPP 3x3 2048 -> 256 on the 48 x 48 maps: 690 TF on the 64 x 128 tiles,
 //     764 with skipped filter rows, 834-866 here; the auxiliary head's 3x3 1024 -> 512: 660 -> 780) and very wide outputs of a medium reduction (256 -> 2048: 697 -> 780);
 //   * 256 x 128 / 128 x 256, a three-stage LDS ring filled with COUNTED waits (s_waitcnt vmcnt(N) + a bare s_barrier: the fetches of K-steps k + 1 and k + 2 stay in flight
-//     while step k is multiplied; 85 FLOP per staged byte): 733-769 TF on the same shapes, level with the narrow tiles elsewhere -- kept for A/B (PM_C16W_CFG) and the tests.
+//     while step k is multiplied; 85 FLOP per staged byte): 733-769 TF on the same shapes, level with the narrow tiles elsewhere -- kept for one-block-per-tile runs (PM_C16P=0, pm_set_conv16(8)) and the tests.
 // Why big tiles: every kernel of this family moves ~20-30 bytes per clock and CU from L2 into LDS whatever its tile (DESIGN section 7 "Round 5"), so TFLOP/s ~ FLOP per
 // staged byte x that; the 64 x 128 / 128 x 128 tiles of conv16.hip stage 43 / 64. Why not everywhere: with one block per CU the tile count has to be balanced against the
 // 256 CUs (split-K by the planner's cost model, conv16.hip pm_conv16_plan); the 48 x 48 maps give 72 x N / 256 tiles of 256 x 256.
@@ -658,9 +658,8 @@ template <int BM, int BN, int WM, int WN, int NP>
 void launch_persistent(const pm_conv16& k, hipStream_t st) {
   constexpr size_t smem = (size_t)3 * (BM + BN) * BKB;
   static_assert(smem <= 160 * 1024, "LDS budget");
-  const int ncu = pm_device_once([] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16p_kernel<BM, BN, WM, WN, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  static pm_lds_optin optin;
+  const int ncu = optin(reinterpret_cast<const void*>(&conv16p_kernel<BM, BN, WM, WN, NP>), 160 * 1024);
   const int total = k.tiles_m * k.tiles_n * k.ksplit;
   hipLaunchKernelGGL((conv16p_kernel<BM, BN, WM, WN, NP>), dim3(std::min(total, ncu)), dim3((8 + NP) * 64), smem, st, k);
 }
@@ -670,9 +669,8 @@ void launch_wide(const pm_conv16& k, dim3 grid, hipStream_t st) {
   constexpr size_t stage_bytes = (size_t)NST * (BM + BN) * BKB, ep_bytes = (size_t)8 * 32 * (BN / WN + 4) * sizeof(float);
   constexpr size_t smem = stage_bytes > ep_bytes ? stage_bytes : ep_bytes;
   static_assert(smem <= 160 * 1024, "LDS budget");
-  (void)pm_device_once([] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16w_kernel<BM, BN, WM, WN, NST>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&conv16w_kernel<BM, BN, WM, WN, NST>), 160 * 1024);
   hipLaunchKernelGGL((conv16w_kernel<BM, BN, WM, WN, NST>), grid, dim3(NT), smem, st, k);
 }
 

@@ -267,36 +267,29 @@ struct Plan {
 // It fills the 256 CUs when a problem has few output tiles (wgrad: Cout x taps*Cin) without paying for partial slabs
 // when the tile count alone already does.
 // ---- PREC 5 routing (round 6): which fp32 launches run as split-operand bf16 MFMA (conv_split.hip). pm_route.split: 0 never, 1 every eligible launch (default).
-int g_split_nst = getenv("PM_SPLIT_NST") ? atoi(getenv("PM_SPLIT_NST")) : 1;
-int g_split_min_k = getenv("PM_SPLIT_MIN_K") ? atoi(getenv("PM_SPLIT_MIN_K")) : 129;      // shorter forward / data-gradient reductions (64 -> 256 @192^2, 128 -> 512 @96^2) are bound by their
-inline bool split_k_ok(int mode, long K) { return mode == MODE_WGRAD || K >= g_split_min_k; }      // output stream, not by the matrix pipe: measured slower on the split path (58 vs 70 TF)
-int g_split_tile = getenv("PM_SPLIT_TILE") ? atoi(getenv("PM_SPLIT_TILE")) : 1;      // 1: the split path prefers the 128 x 128 tile (3.7 VALU per MFMA; 64 x 64: 7.3), 0: the fp32 kernel's tile choice
+constexpr long SPLIT_MIN_K = 129;      // shorter forward / data-gradient reductions (64 -> 256 @192^2, 128 -> 512 @96^2) are bound by their
+inline bool split_k_ok(int mode, long K) { return mode == MODE_WGRAD || K >= SPLIT_MIN_K; }      // output stream, not by the matrix pipe: measured slower on the split path (58 vs 70 TF)
 Plan make_plan(int mode, long M, long Nn, long K, bool bf16 = false) {
   Plan best_p{};
   double best = 1e30;
-  static const int force_bm = getenv("PM_FORCE_BM") ? atoi(getenv("PM_FORCE_BM")) : 0;   // tuning runs only
-  static const int force_bn = getenv("PM_FORCE_BN") ? atoi(getenv("PM_FORCE_BN")) : 0;
   // column tile: weight gradients keep 128-wide tiles; forward / data gradient run best as many small blocks (64 x 64: 70 VGPRs,
   // 18 KB single-stage LDS -> 7-8 resident per CU): -1.4 ms/step of kernel time against 64 x 128 in the per-shape A/B
-  // (tools/conv_compare.py), within +-3 % on the few N >= 1024 shapes that preferred the wider tile. PM_WIDE_BN=1 restores 128.
-  static const int wide_bn = getenv("PM_WIDE_BN") ? atoi(getenv("PM_WIDE_BN")) : 0;
+  // (tools/conv_compare.py), within +-3 % on the few N >= 1024 shapes that preferred the wider tile.
   int bn = Nn > 64 ? 128 : ((Nn > 32 || bf16) ? 64 : 32);      // no bf16-operand instantiation of the 128 x 32 tile: narrow outputs (19 classes) pad to 64
   // bf16 operands (configs[2], direct algorithm everywhere): the MFMA phase is 16x shorter, the kernel is bound by staging its
   // operands through L2 / LDS, so the 128 x 128 tile (half the operand traffic per FLOP of 64 x 64) wins: 73.1 -> see DESIGN
-  const bool big = bf16 || (pm_route.split && g_split_tile && split_k_ok(mode, K));
-  if (mode != MODE_WGRAD && !wide_bn && !big && bn == 128) bn = 64;
-  if (force_bn && mode != MODE_WGRAD) bn = force_bn;
+  // the split path as well: 3.7 split instructions per MFMA on the 128 x 128 tile, 7.3 on 64 x 64
+  const bool big = bf16 || (pm_route.split && split_k_ok(mode, K));
+  if (mode != MODE_WGRAD && !big && bn == 128) bn = 64;
   const long ksteps = (K + BK - 1) / BK;
   // candidate row tiles: 128 always; 64 halves the tile so that problems with few / awkward tile counts (the 48x48 maps: 144
   // row tiles of 128) spread evenly over the 256 CUs; a 64-row tile is ~8 % less efficient per FLOP (half the MFMAs per
   // fragment read and per barrier).
   for (int bm = 128; bm >= 64; bm -= 64) {
     if (bm == 64 && bn < 64) continue;                            // no 64x32 instantiation (4 waves need >= 2 tiles)
-    if (force_bm && mode != MODE_WGRAD && bm != force_bm && !(force_bm == 64 && bn < 64)) continue;
     // forward / data gradient: 64-row blocks (64 x 128: 114 VGPRs, 27.6 KB single-stage LDS -> four per CU) beat 128-row ones (three
-    // per CU) on the whole step by ~0.9 ms (same-box A/B), so the larger tile is not a candidate (PM_PREFER_BM64=0 restores it)
-    static const int prefer64 = getenv("PM_PREFER_BM64") ? atoi(getenv("PM_PREFER_BM64")) : 1;
-    if (prefer64 && !big && !force_bm && mode != MODE_WGRAD && bn >= 64 && bm == 128) continue;
+    // per CU) on the whole step by ~0.9 ms (same-box A/B), so the larger tile is not a candidate
+    if (!big && mode != MODE_WGRAD && bn >= 64 && bm == 128) continue;
     if (bm == 64 && mode == MODE_WGRAD && M > 64) continue;       // wgrad: 64 rows only for Cout <= 64
     if (bm == 128 && mode == MODE_WGRAD && M <= 64 && bn >= 64) continue;
     const int tiles_m = pm_cdiv(M, bm), tiles_n = pm_cdiv(Nn, bn);
@@ -305,9 +298,7 @@ Plan make_plan(int mode, long M, long Nn, long K, bool bf16 = false) {
     //  r04c vs r04a, the side-stream weight gradients want the parallelism more than they mind the slabs -- so the unit is the same for both types)
     const double unit_us = 2.0 * (bm / 128.0) * (bn / 128.0) * (bm == 64 ? 1.08 : 1.0);
     const long ks_max = std::max<long>(1, std::min<long>(ksteps / 4, 512));
-    static const int force_ks = getenv("PM_FORCE_KS") ? atoi(getenv("PM_FORCE_KS")) : 0;
     for (long ks = 1; ks <= ks_max; ++ks) {
-      if (force_ks && mode != MODE_WGRAD && ks != force_ks && force_ks <= ks_max) continue;
       const long steps_per = (ksteps + ks - 1) / ks;
       if ((ksteps + steps_per - 1) / steps_per != ks) continue;
       const long blocks = tiles * ks;
@@ -327,48 +318,27 @@ Plan make_plan(int mode, long M, long Nn, long K, bool bf16 = false) {
 
 template <int MODE, int BM, int BN, int WM, int WN, int KM, int PREC, int NST>
 void launch_nst(const ConvK& k, dim3 grid, size_t smem, hipStream_t st) {
-  static const bool attr_set = [] {  // > 64 KB of dynamic LDS needs an explicit opt-in, once per kernel
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();
-  (void)attr_set;
   const size_t ep_bytes = (size_t)4 * 32 * (BN / WN + 4) * sizeof(float);      // staged epilogue: four wave slabs
   if constexpr (MODE == MODE_FWD && PREC != 1 && BN >= 64) {
     if (k.stats) {
-      static const bool attr_set2 = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return true;
-      }();
-      (void)attr_set2;
+      static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs an explicit opt-in
+      (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>), 160 * 1024);
       hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>), grid, dim3(256), std::max(smem / (NST == 1 ? 2 : 1), ep_bytes), st, k);
       return;
     }
   }
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>), 160 * 1024);
   hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>), grid, dim3(256), std::max(smem / (NST == 1 ? 2 : 1), ep_bytes), st, k);
 }
-// longest reduction (in K-steps per block) that takes the single-stage variant; PM_NST1_STEPS overrides it for tuning runs
-inline int nst1_max_steps() {
-  static const int v = [] {
-    const char* e = getenv("PM_NST1_STEPS");
-    return e ? atoi(e) : 64;
-  }();
-  return v;
-}
-// native-bf16 weight gradient on ONE LDS stage (PM_WGRAD_NST1=1, tuning): 40 instead of 80 KB per 128 x 128 block -> three resident blocks per CU instead of two
-inline bool wgrad_nst1() {
-  static const bool v = [] { const char* e = getenv("PM_WGRAD_NST1"); return e && e[0] == '1'; }();
-  return v;
-}
+// LDS stages of the tile kernel: the single-stage variant only where it is used -- fast-path fwd / dgrad with a short reduction per block
+constexpr int NST1_MAX_STEPS = 64;      // longest reduction (in K-steps per block) that takes the single-stage variant
+constexpr bool has_nst1(int mode, int kmode, int bn) { return mode != MODE_WGRAD && kmode == K_FAST && bn >= 64; }
+inline int lds_stages(int mode, int kmode, int bn, int kper) { return has_nst1(mode, kmode, bn) && kper <= NST1_MAX_STEPS * BK ? 1 : 2; }
 template <int MODE, int BM, int BN, int WM, int WN, int KM, int PREC>
 void launch_prec(const ConvK& k, dim3 grid, size_t smem, hipStream_t st) {
-  // single-stage variant only where it is used: fast-path fwd / dgrad with a short reduction per block
-  if constexpr (KM == K_FAST && MODE != MODE_WGRAD && BN >= 64) {
-    if (k.kper <= nst1_max_steps() * BK) return launch_nst<MODE, BM, BN, WM, WN, KM, PREC, 1>(k, grid, smem, st);
-  }
-  if constexpr (MODE == MODE_WGRAD && PREC == 4) {
-    if (wgrad_nst1()) return launch_nst<MODE, BM, BN, WM, WN, KM, PREC, 1>(k, grid, smem, st);
+  if constexpr (has_nst1(MODE, KM, BN)) {
+    if (lds_stages(MODE, KM, BN, k.kper) == 1) return launch_nst<MODE, BM, BN, WM, WN, KM, PREC, 1>(k, grid, smem, st);
   }
   launch_nst<MODE, BM, BN, WM, WN, KM, PREC, 2>(k, grid, smem, st);
 }
@@ -403,11 +373,7 @@ bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
 
 inline bool split_takes(int mode, const Plan& p, const ConvK& k, int batch) {      // batched launches (the Winograd point products: their output stays in L2) at every K
-  static const int modes = getenv("PM_SPLIT_MODES") ? atoi(getenv("PM_SPLIT_MODES")) : 7;      // bisecting knob: bit 0 forward form, 1 data gradient, 2 weight gradient
-  static const int bsel = getenv("PM_SPLIT_BATCH") ? atoi(getenv("PM_SPLIT_BATCH")) : 0;      // bisecting knob: 1 only batched launches, 2 only unbatched ones
-  static const int maxm = getenv("PM_SPLIT_MIN_M") ? atoi(getenv("PM_SPLIT_MIN_M")) : 0;
-  if ((bsel == 1 && batch <= 1) || (bsel == 2 && batch > 1) || k.M < maxm) return false;
-  return pm_route.split != 0 && ((modes >> mode) & 1) && p.bn >= 64 && !k.io16 && (batch > 1 || split_k_ok(mode, k.K));
+  return pm_route.split != 0 && p.bn >= 64 && !k.io16 && (batch > 1 || split_k_ok(mode, k.K));
 }
 
 template <int MODE>
@@ -419,19 +385,17 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   k.kper = p.kper;
   dim3 grid(p.tiles_m * p.tiles_n, batch, p.ksplit);
   // staged epilogue: in situ +3 ... +6 % on the convolutions whose output streams to HBM (every unbatched launch), -2 ... -4 % on the
-  // batched Winograd GEMMs whose product M[p] stays in L2 / Infinity Cache for the output transform (tools/gpu_env_ab2.sh PM_STAGE_EP)
-  if (batch != 1 && !getenv("PM_STAGE_EP")) k.stage_ep = 0;
+  // batched Winograd GEMMs whose product M[p] stays in L2 / Infinity Cache for the output transform (tools/gpu_env_ab2.sh)
+  if (batch != 1) k.stage_ep = 0;
   if (k.prec == 0 && split_takes(MODE, p, k, batch)) k.prec = 5;
   {      // whole (batch, K-slice) units per XCD (conv_igemm_kernel.h): the unit count's remainder mod 8 must cut evenly into runs of tiles
-    static const int batch_xcd = getenv("PM_BATCH_XCD") ? atoi(getenv("PM_BATCH_XCD")) : 3;      // bit 0: batched launches, bit 1: split-K launches
     const int units = batch * p.ksplit, rem = units & 7, ntile = p.tiles_m * p.tiles_n;
-    const bool want = p.ksplit > 1 ? (batch_xcd & 2) != 0 : (batch_xcd & 1) != 0;
-    k.batch_xcd = want && units >= 8 && (rem == 0 || ((rem == 1 || rem == 2 || rem == 4) && ntile % (8 / rem) == 0));
+    k.batch_xcd = units >= 8 && (rem == 0 || ((rem == 1 || rem == 2 || rem == 4) && ntile % (8 / rem) == 0));
   }
   ProfRec rec{};
   if (g_prof_on) {
     (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-    rec.mode = MODE, rec.bm = p.bm, rec.bn = p.bn, rec.km = (MODE == MODE_WGRAD && k.kmode == K_FAST) ? K_MID : ((k.prec == 5 && MODE != MODE_WGRAD && k.kmode == K_FAST && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) ? K_PW : k.kmode), rec.prec = k.prec, rec.nst = (MODE != MODE_WGRAD && k.kmode == K_FAST && p.bn >= 64 && k.kper <= nst1_max_steps() * BK) ? 1 : 2, rec.M = k.M, rec.Nn = k.Nn, rec.K = k.K, rec.batch = batch, rec.ksplit = p.ksplit, rec.flops = flops >= 0.0 ? flops : 2.0 * (double)k.M * (double)k.Nn * (double)k.K * batch;
+    rec.mode = MODE, rec.bm = p.bm, rec.bn = p.bn, rec.km = (MODE == MODE_WGRAD && k.kmode == K_FAST) ? K_MID : ((k.prec == 5 && MODE != MODE_WGRAD && k.kmode == K_FAST && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) ? K_PW : k.kmode), rec.prec = k.prec, rec.nst = lds_stages(MODE, k.kmode, p.bn, k.kper), rec.M = k.M, rec.Nn = k.Nn, rec.K = k.K, rec.batch = batch, rec.ksplit = p.ksplit, rec.flops = flops >= 0.0 ? flops : 2.0 * (double)k.M * (double)k.Nn * (double)k.K * batch;
     rec.bytes = (double)batch * ((double)k.a_bytes + (double)k.b_bytes + ((k.io16 && p.ksplit == 1) ? 2.0 : 4.0) * (double)k.M * (double)k.Nn * (double)p.ksplit);
     (void)hipEventRecord(rec.a, st);
   }
@@ -455,11 +419,9 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   }
   constexpr bool akc = MODE != MODE_WGRAD, bkc = MODE == MODE_FWD;
   if (k.prec == 5) {      // fp32 operands, three-way bf16 split, six products on the bf16 matrix pipe (conv_split.hip)
-    const size_t stage = pm_conv_split_stage_bytes(MODE, p.bm, p.bn);
-    const bool nst1 = g_split_nst != 2 || 2 * stage > 160 * 1024;
-    if (int e = pm_conv_split_launch(MODE, p.bm, p.bn, k, grid.x, grid.y, grid.z, stage, nst1, st)) return e;
+    if (int e = pm_conv_split_launch(MODE, p.bm, p.bn, k, grid.x, grid.y, grid.z, pm_conv_split_stage_bytes(MODE, p.bm, p.bn), st)) return e;
     if (g_prof_on) {
-      rec.nst = nst1 ? 1 : 2;
+      rec.nst = 1;
       (void)hipEventRecord(rec.b, st);
       g_prof.push_back(rec);
     }
@@ -519,12 +481,9 @@ void fill_geom(ConvK& k, const pm_tensor* x, const pm_tensor* y, const pm_conv_p
   k.sub = k.sub_cy = k.sub_cx = 0, k.Hc = x->h, k.Wc = x->w;
   k.bias = k.scale = k.shift = k.residual = nullptr;
   k.res_pitch = 0, k.relu = 0, k.stats = nullptr, k.io16 = 0;
-  static const int stage_ep = getenv("PM_STAGE_EP") ? atoi(getenv("PM_STAGE_EP")) : 1;
-  k.stage_ep = stage_ep;
-  static const int spl_prio = getenv("PM_SPLIT_PRIO") ? atoi(getenv("PM_SPLIT_PRIO")) : 1;
-  k.spl_prio = spl_prio;
-  static const int n_group = getenv("PM_N_GROUP") ? atoi(getenv("PM_N_GROUP")) : 8;
-  k.n_group = n_group;
+  k.stage_ep = 1;      // staged epilogue; launch() turns it off for batched launches
+  k.spl_prio = 1;      // PREC 5: the odd hardware wave slot at a raised priority (measured level; DESIGN.md, the split path)
+  k.n_group = 8;       // N tiles walked in groups of eight columns (tile order: L2-miss traffic down, time level)
   k.batch_xcd = 0;
   k.a_bs = k.b_bs = k.c_bs = 0;
 }
@@ -566,17 +525,15 @@ WinoPlan wino_plan(const pm_tensor* xin, int cout, const pm_conv_params* p, bool
   wp.v_bytes = pm_align_up((size_t)wp.P * wp.g.tiles * wp.Kp * sizeof(float), 256);
   wp.m_bytes = pm_align_up((size_t)wp.P * wp.g.tiles * cout * sizeof(float), 256);
   wp.u_bytes = pm_align_up((size_t)wp.P * cout * wp.Kp * sizeof(float), 256);
-  static const int wino_bm = getenv("PM_WINO_BM") ? atoi(getenv("PM_WINO_BM")) : 128;
-  static const int wino_bn = getenv("PM_WINO_BN") ? atoi(getenv("PM_WINO_BN")) : 128;
-  wp.pl.bm = wino_bm, wp.pl.bn = wino_bn;
+  wp.pl.bm = 128, wp.pl.bn = 128;
   // column tile: 64 wide where 128-wide tiles would pad the channel extent by more than 12 % (final1's 304-channel data gradient:
   // 3 x 128 = 384 columns of MFMA work for 304 real ones, 5 x 64 = 320)
-  if (wp.pl.bn == 128 && pm_cdiv(cout, 128) * 128 > cout * 1.12 && pm_cdiv(cout, 64) * 64 < pm_cdiv(cout, 128) * 128) wp.pl.bn = 64;
+  if (pm_cdiv(cout, 128) * 128 > cout * 1.12 && pm_cdiv(cout, 64) * 64 < pm_cdiv(cout, 128) * 128) wp.pl.bn = 64;
   // few transform tiles (the 48 x 48 maps with dilation: 1152 ... 4608 rows per GEMM): 128-row blocks leave the last round of the 256 CUs
   // half empty; 64 x 128 blocks measured -0.25 ms/step over those layers in situ (tools/gpu_tile_ab2.sh), nothing gained above
   // (the split path keeps 128 rows: 3.7 instead of 5.5 split instructions per MFMA outweigh the half-empty last round -- same box: 52.2 -> 51.7 ms/step, the deep ASPP
   //  products 160-178 -> 188-200 TF)
-  if (wp.pl.bm == 128 && wp.g.tiles <= 4608 && !getenv("PM_WINO_BM") && !(pm_route.split && g_split_tile)) wp.pl.bm = 64;
+  if (wp.g.tiles <= 4608 && !pm_route.split) wp.pl.bm = 64;
   wp.pl.tiles_m = pm_cdiv(wp.g.tiles, wp.pl.bm), wp.pl.tiles_n = pm_cdiv(cout, wp.pl.bn);
   wp.pl.ksplit = 1, wp.pl.kper = wp.Kp, wp.pl.ws_bytes = 0;
   wp.use = true;
@@ -702,10 +659,9 @@ Bf16Plan bf16_plan(const pm_tensor* xin, const pm_tensor* yout, const pm_conv_pa
   if (b.pl.bn < 64) return b;                                     // no bf16 instantiation of the 128 x 32 tile
   b.use = true;
   // round 4: the LDS-DMA kernel for everything but tiny row counts (the image-pooling branch: M = batch) -- PM_CONV16=0 keeps the register-staged kernel (A/B runs)
-  const int c16_on = pm_route.conv16;
-  static const int c16_min_m = getenv("PM_CONV16_MIN_M") ? atoi(getenv("PM_CONV16_MIN_M")) : 256;
+  constexpr long C16_MIN_M = 256;
   b.c16 = false;
-  if (c16_on && b.M >= c16_min_m && p->stride >= 1) {
+  if (pm_route.conv16 && b.M >= C16_MIN_M && p->stride >= 1) {
     pm_conv16& k = b.k16;
     k = pm_conv16{};
     k.N = xin->n, k.H = xin->h, k.W = xin->w, k.Ho = yout->h, k.Wo = yout->w;
@@ -719,7 +675,7 @@ Bf16Plan bf16_plan(const pm_tensor* xin, const pm_tensor* yout, const pm_conv_pa
     // decoder's 3x3): those stay there. PM_CONV16=2 forces the LDS-DMA kernel everywhere.
     // (second form of the kernel, buffer-descriptor fetches: it also takes the long reductions the register-staged planner would run on 64-row tiles -- the
     //  3x3 512 -> 1024-wide data gradients at 48 x 48: 596 -> 877 TF on 128 x 128 -- while the short 1x1 reductions stay with the single-stage register-staged form)
-    b.c16 = c16_on == 2 || k.wide || k.bm == 64 || k.ksteps_per == 1 || (b.pl.bm == 64 && k.ksteps >= 16);
+    b.c16 = pm_route.conv16 == 2 || k.wide || k.bm == 64 || k.ksteps_per == 1 || (b.pl.bm == 64 && k.ksteps >= 16);
   }
   return b;
 }
@@ -845,8 +801,7 @@ struct S2Native {
 };
 S2Native s2_native_plan(const pm_tensor* dy, const pm_tensor* dx, const pm_conv_params* p) {
   S2Native s{};
-  static const int on = getenv("PM_S2_NATIVE16") ? atoi(getenv("PM_S2_NATIVE16")) : 1;
-  if (!on || !pm_route.conv16 || p->stride != 2 || p->dil != 1 || !pm_is_bf16(dy) || !pm_is_bf16(dx) || !pm_vec8(dy) || !pm_vec8(dx) || dy->c % 64 || dx->c % 8) return s;
+  if (!pm_route.conv16 || p->stride != 2 || p->dil != 1 || !pm_is_bf16(dy) || !pm_is_bf16(dx) || !pm_vec8(dy) || !pm_vec8(dx) || dy->c % 64 || dx->c % 8) return s;
   size_t off = 0, out_bytes = 0, slab = 0;
   for (int cls = 0; cls < 4; ++cls) {
     const S2Class c = s2_class(cls, dx, p);
@@ -970,19 +925,24 @@ void gemm_dims(int which, const pm_tensor* x, const pm_tensor* y, const pm_conv_
 
 }  // namespace
 
-// ---- the library's routing state: ONE struct (include/pinmem_hip.h pm_routing), initialised from the PM_* environment at load, replaced as a whole by pm_routing_set.
-// The pm_set_* entry points below are thin wrappers that change one field (kernel tests, A/B runs).
-pm_routing pm_route = {
-    (int32_t)sizeof(pm_routing),
-    4,                                                                  // winograd: prefer F(4x4,3x3)
-    getenv("PM_WINO_FUSED") ? atoi(getenv("PM_WINO_FUSED")) : 0,        // winograd_fused
-    getenv("PM_CONV16") ? atoi(getenv("PM_CONV16")) : 1,                // conv16
-    getenv("PM_C16W") ? atoi(getenv("PM_C16W")) : 1,                    // conv16_wide
-    getenv("PM_C16P") ? atoi(getenv("PM_C16P")) : 1,                    // conv16_persistent
-    getenv("PM_WGRAD16") ? atoi(getenv("PM_WGRAD16")) : 1,              // wgrad16
-    0,                                                                  // bf16_wgrad
-    getenv("PM_SPLIT") ? atoi(getenv("PM_SPLIT")) : 1,                  // split
-};
+// ---- the library's routing state: ONE struct (include/pinmem_hip.h pm_routing), initialised at load from the six PM_* variables below -- the only place the library
+// reads its environment -- and replaced as a whole by pm_routing_set. The pm_set_* entry points below are thin wrappers that change one field (kernel tests, A/B runs).
+static pm_routing routing_from_env() {
+  auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  return pm_routing{
+      (int32_t)sizeof(pm_routing),
+      4,                            // winograd: prefer F(4x4,3x3)
+      env("PM_WINO_FUSED", 0),      // winograd_fused
+      env("PM_CONV16", 1),          // conv16
+      env("PM_C16W", 1),            // conv16_wide
+      env("PM_C16P", 1),            // conv16_persistent
+      env("PM_WGRAD16", 1),         // wgrad16
+      0,                            // bf16_wgrad
+      env("PM_SPLIT", 1),           // split
+  };
+}
+const pm_routing pm_route_defaults = routing_from_env();
+pm_routing pm_route = pm_route_defaults;
 extern "C" int pm_routing_get(pm_routing* out) {
   PM_REQUIRE(out && out->struct_size == (int32_t)sizeof(pm_routing), PM_EINVAL, "pm_routing_get: struct_size %d != %zu (library ABI %d)", out ? out->struct_size : -1,
              sizeof(pm_routing), PM_ABI_VERSION);
@@ -1006,10 +966,9 @@ extern "C" int pm_set_conv16(int on) {
   PM_REQUIRE(on >= 0 && on <= 8, PM_EINVAL, "pm_set_conv16: %d (0 register-staged, 1 per shape, 2 LDS-DMA everywhere / narrow tiles only, 3 LDS-DMA everywhere / wide tiles "
              "wherever the shape allows, 4 per shape without the wide kernel, 5 / 6 = 1 (the streaming 1x1 kernel left the library in round 6), 7 as 3 with the 256 x 256 tile, "
              "8 as 3 with one block per tile instead of the persistent ring)", on);
-  static const pm_routing defaults = pm_route;      // the environment's defaults, as read at load
   pm_route.conv16 = (on == 3 || on == 7 || on == 8) ? 2 : ((on == 4 || on == 5 || on == 6) ? 1 : on);
-  pm_route.conv16_wide = (on == 3 || on == 8) ? 2 : (on == 7 ? 3 : ((on == 2 || on == 4) ? 0 : defaults.conv16_wide));
-  pm_route.conv16_persistent = on == 8 ? 0 : (on == 3 ? 1 : defaults.conv16_persistent);
+  pm_route.conv16_wide = (on == 3 || on == 8) ? 2 : (on == 7 ? 3 : ((on == 2 || on == 4) ? 0 : pm_route_defaults.conv16_wide));
+  pm_route.conv16_persistent = on == 8 ? 0 : (on == 3 ? 1 : pm_route_defaults.conv16_persistent);
   return PM_OK;
 }
 extern "C" int pm_set_winograd_fused(int on) {
@@ -1146,9 +1105,6 @@ extern "C" size_t pm_conv_wxf_bytes_dgrad(const pm_tensor* dy, const pm_tensor* 
 // split and a 16-byte-aligned output takes the staged epilogue; everything else (Winograd route, split-K, the 19-class heads) answers 0.
 static bool bn_partials_route(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p) {
   if (!x || !y || !p || check_common(x, y, p) != PM_OK) return false;
-  static const int on = getenv("PM_BN_EPILOGUE") ? atoi(getenv("PM_BN_EPILOGUE")) : 1;
-  static const int stage_ep = getenv("PM_STAGE_EP") ? atoi(getenv("PM_STAGE_EP")) : 1;
-  if (!on || !stage_ep) return false;
   if (pm_is_bf16(y)) {      // bf16 tier: both bf16 kernels carry the statistics in their 8-column staged epilogue (one K split, whole 16-byte groups)
     if (!pm_vec8(y)) return false;
     const Bf16Plan b = bf16_plan(x, y, p);
@@ -1442,9 +1398,8 @@ extern "C" int pm_conv_bwd_weight(const pm_tensor* x0, const pm_tensor* dy0, flo
   ConvK k;
   fill_geom(k, x, dy, p);
   // configs[2]: the weight gradient gathers the fp32 rows as before, rounds them to bf16 on the way into LDS and reads its fragments through the
-  // transpose read (PREC 3): no transposed / per-tap copies of x in HBM. PM_BF16_WGRAD_TR=0 keeps the staged-fp32 form (A/B runs).
-  static const int tr_on = getenv("PM_BF16_WGRAD_TR") ? atoi(getenv("PM_BF16_WGRAD_TR")) : 1;
-  if (p->prec == 2 && tr_on) k.prec = 3;
+  // transpose read (PREC 3): no transposed / per-tap copies of x in HBM.
+  if (p->prec == 2) k.prec = 3;
   if (native16) {
     PM_REQUIRE(x->c % 8 == 0 && dy->c % 8 == 0 && pl.bn >= 64, PM_EUNSUPPORTED, "conv_bwd_weight(bf16): channels %% 8 != 0 or a tile narrower than 64");
     k.prec = 4;

@@ -40,15 +40,15 @@ struct ConvK {
   int relu;
   float* stats;               // train-mode BN statistics of the output: (mean, M2) per 32-row slab and channel, or null
   int io16;                   // the bf16 tier: C and `residual` are bf16 tensors (pitches in elements); accumulation and the epilogue arithmetic stay fp32
-  int stage_ep;               // 1: epilogue staged through LDS (16-byte row stores); 0: per-element stores (PM_STAGE_EP=0, A/B)
+  int stage_ep;               // 1: epilogue staged through LDS (16-byte row stores); 0: per-element stores (batched launches)
   int n_group;                // > 0: N tiles are walked in groups of n_group columns (tile order inside a group: M outer, N inner), so that one XCD's co-resident
                               // blocks cover a squarer patch of the output and the weight columns of the group stay in that XCD's L2 over the whole sweep of M
   int batch_xcd;              // 1: gridDim.y >= 8 batches are dealt to the XCDs whole (see the kernel); set by the launcher when the counts divide
   int spl_prio;               // PREC 5: 1 = waves in odd hardware wave slots run at s_setprio 2 (see the kernel), 0 = all equal
 };
 
-// conv_split.hip: launches the PREC 5 instantiation of the tile (bm x bn) / K-state mode of `k`; NST = 1 (one LDS stage) when nst1, else two
-int pm_conv_split_launch(int mode, int bm, int bn, const ConvK& k, unsigned gx, unsigned gy, unsigned gz, size_t smem, bool nst1, hipStream_t st);
+// conv_split.hip: launches the PREC 5 instantiation of the tile (bm x bn) / K-state mode of `k`, on one LDS stage of smem bytes
+int pm_conv_split_launch(int mode, int bm, int bn, const ConvK& k, unsigned gx, unsigned gy, unsigned gz, size_t smem, hipStream_t st);
 size_t pm_conv_split_stage_bytes(int mode, int bm, int bn);
 
 namespace {

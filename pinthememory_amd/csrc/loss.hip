@@ -496,34 +496,26 @@ struct Rows2Plan {
   size_t lds;
 };
 inline Rows2Plan rows2_plan(const CEGeom& g) {
-  static const bool off = [] { const char* e = getenv("PM_CE_ROWS2"); return e && e[0] == '0'; }();      // PM_CE_ROWS2=0: the one-row-per-hi-res-row field (A/B)
+  constexpr int SEG_COLS = 96;
+  constexpr int MAX_THREADS = 256;      // measured best (gpu_r6_ce.sh)
   Rows2Plan p{};
   const int ratio = std::max(1, g.W / std::max(1, g.w));
-  static const int seg_cols = [] { const char* e = getenv("PM_CE_ROWS2_SEG"); const int v = e ? atoi(e) : 96; return std::max(16, v); }();
-  p.nseg = std::max(1, (g.w + seg_cols - 1) / seg_cols);      // column segments per interval (<= 96 columns each: 31 KB of LDS at 19 classes)
+  p.nseg = std::max(1, (g.w + SEG_COLS - 1) / SEG_COLS);      // column segments per interval (<= 96 columns each: 31 KB of LDS at 19 classes)
   p.ws = (g.w + p.nseg - 1) / p.nseg;
   p.nseg = (g.w + p.ws - 1) / p.ws;
   p.tpr = std::min(320, (p.ws + (p.nseg > 1 ? 1 : 0) + 63) / 64 * 64);      // + the left-neighbour lane when there are segments
-  static const int max_threads = [] { const char* e = getenv("PM_CE_ROWS2_THREADS"); const int v = e ? atoi(e) : 256; return std::min(1024, std::max(128, v)); }();      // 256: measured best (gpu_r6_ce.sh)
-  p.rg = std::max(1, std::min(ce2_rows_per_interval(g.h, g.H), max_threads / std::max(64, p.tpr)));
+  p.rg = std::max(1, std::min(ce2_rows_per_interval(g.h, g.H), MAX_THREADS / std::max(64, p.tpr)));
   p.lds = ((size_t)2 * (p.ws + 2) * (g.C | 1) + (size_t)2 * p.ws * g.C + (size_t)p.rg * (p.tpr / 64) * MAXC) * sizeof(float) + (size_t)p.rg * ((g.W + 15) & ~15);
   // one lane per low-res column (modest up-sampling ratios; the 16-fold read loss keeps the PARTS form: its field is small), up-sampling only (block count <= hi-res rows:
   // the partial workspace is sized for those), everything in 64 KB of dynamic LDS
-  p.ok = !off && g.C == 19 && g.w <= 256 && ratio < 8 && g.H >= g.h && g.h >= 1 && p.lds <= ROWS2_MAX_LDS && (long)g.n * g.h * p.nseg <= (1l << 30) && p.nseg <= 2 * std::max(1, g.H / std::max(1, g.h)) ;      // 19 classes: the
+  p.ok = g.C == 19 && g.w <= 256 && ratio < 8 && g.H >= g.h && g.h >= 1 && p.lds <= ROWS2_MAX_LDS && (long)g.n * g.h * p.nseg <= (1l << 30) && p.nseg <= 2 * std::max(1, g.H / std::max(1, g.h)) ;      // 19 classes: the
   // specialised instantiation (2 x 19 accumulators + 3 x 19 working registers sit at the 128-register budget of a 1 024-thread block; 32 classes would not)
   return p;
 }
 
 inline void rows2_launch(const CEGeom& g, const Rows2Plan& r, float* part, float* field, hipStream_t st) {
-  static bool attr_set[64] = {};      // > 64 KB of dynamic LDS needs the opt-in, once per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS2_MAX_LDS) != hipSuccess)
-      (void)hipGetLastError();        // the launch then fails with its own error for plans beyond 64 KB
-    else
-      attr_set[dev] = true;
-  }
+  static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs the opt-in, once per device
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19>), (int)ROWS2_MAX_LDS);
   const long half = (long)g.n * g.h * g.w * g.C;
   hipLaunchKernelGGL(ce_fused_rows2_kernel<19>, dim3(g.n * g.h * r.nseg), dim3(r.tpr * r.rg), r.lds, st, g, part, field, field + half, r.tpr, r.rg, r.nseg, r.ws);
 }
@@ -586,17 +578,9 @@ inline FusedPlan fused_plan(const CEGeom& g) {
 constexpr size_t FUSED_MAX_LDS = 159 * 1024;   // dynamic part; the kernel also declares 160 B of static LDS
 template <int CC, int PP, bool WITH_T>
 void fused_launch_one(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
-  // > 64 KB of dynamic LDS (logit rows wider than ~420 pixels x 19 classes) needs an explicit opt-in, once per kernel AND device (the guard
-  // used to cover the first device of a multi-device process only, and dropped the call's status)
-  static bool attr_set[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, WITH_T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_MAX_LDS) != hipSuccess)
-      (void)hipGetLastError();      // the launch below then fails with its own error for rows beyond 64 KB
-    else
-      attr_set[dev] = true;
-  }
+  // > 64 KB of dynamic LDS (logit rows wider than ~420 pixels x 19 classes) needs an explicit opt-in, once per kernel AND device
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, WITH_T>), (int)FUSED_MAX_LDS);
   hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, WITH_T>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
 }
 template <bool WITH_T>

@@ -801,10 +801,6 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
 inline int row_blocks(long rows) { return (int)std::min<long>((rows + 3) / 4, 256 * 8); }
 inline int accum_blocks(long rows) { return (int)std::min<long>((rows + 15) / 16, 256); }   // slab kernel: one block (4 wave slabs in LDS) per CU
 inline int accum_mfma_blocks(long rows) { return (int)std::min<long>((rows + AM_ROWS - 1) / AM_ROWS, 512); }   // MFMA kernel: two resident blocks per CU (141 + 68 registers)
-inline bool accum_slab() {   // PM_MEM_ACCUM_SLAB=1: the round-2 LDS-slab kernel (A/B)
-  static const bool v = [] { const char* e = getenv("PM_MEM_ACCUM_SLAB"); return e && e[0] == '1'; }();
-  return v;
-}
 
 }  // namespace
 
@@ -890,7 +886,7 @@ extern "C" int pm_mem_read_bwd(const pm_tensor* x, const float* mem, int m, cons
                          (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch, (float*)ws);
     const long n = (long)m * D;
     launch_reduce_partials((const float*)ws, nb, n, dmem, st);
-  } else if (getenv("PM_MEM_BWD_ROWS") == nullptr) {
+  } else {
     const int nt = (int)std::min<long>((rows + 31) / 32, 256 * 3 * 4);
     const size_t lds = (size_t)(32 * MR_LDK + 4 * MR_SP) * sizeof(float);
     if (m == 19)
@@ -899,13 +895,6 @@ extern "C" int pm_mem_read_bwd(const pm_tensor* x, const float* mem, int m, cons
     else
       hipLaunchKernelGGL(mem_read_bwd_mfma_kernel<0>, dim3(nt), dim3(256), lds, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
                          (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch);
-  } else {
-    if (m == 19)
-      hipLaunchKernelGGL((mem_read_bwd_kernel<19, false>), dim3(nb), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
-                         (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch, (float*)nullptr);
-    else
-      hipLaunchKernelGGL((mem_read_bwd_kernel<0, false>), dim3(nb), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
-                         (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch, (float*)nullptr);
   }
   return pm_check_launch("mem_read_bwd");
 }
@@ -923,7 +912,7 @@ extern "C" int pm_mem_write_accum(const pm_tensor* z, const int64_t* labels, int
   const long rows = pm_pixels(z);
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)(m + 1) * (D + 1);
-  if (!accum_slab() && rows < (1l << 31)) {
+  if (rows < (1l << 31)) {      // beyond that: the round-2 LDS-slab kernel
     const int nb = accum_mfma_blocks(rows);
     hipLaunchKernelGGL(mem_write_accum_mfma_kernel, dim3(nb), dim3(256), 0, st, (const float*)z->ptr, (long)z->pitch, z->n, z->h, z->w, labels, H, W, m, normalize,
                        pm_ac_scale(H, z->h), pm_ac_scale(W, z->w), (float*)ws);
@@ -932,11 +921,8 @@ extern "C" int pm_mem_write_accum(const pm_tensor* z, const int64_t* labels, int
   }
   const int nb = accum_blocks(rows);
   const size_t lds = (size_t)ACC_W * ((m + 1) * D + MAXM) * sizeof(float);
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mem_write_accum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();
-  (void)attr;
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&mem_write_accum_kernel), 160 * 1024);
   hipLaunchKernelGGL(mem_write_accum_kernel, dim3(nb), dim3(256), lds, st, (const float*)z->ptr, (long)z->pitch, z->n, z->h, z->w, labels, H, W, m, normalize,
                      pm_ac_scale(H, z->h), pm_ac_scale(W, z->w), (float*)ws);
   launch_reduce_partials((const float*)ws, nb, n, nomden, st);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -151,22 +152,33 @@ struct pm_gemm_pw {
 bool pm_pwstream_ok(const pm_gemm_pw* g);
 int pm_pwstream_launch(const pm_gemm_pw* g, hipStream_t st);
 
-// One-time setup per DEVICE of a kernel that needs it (the > 64 KB dynamic-LDS opt-in) and the CU count of the current device (persistent kernels size their grid by
-// it). ADVICE r5: a `static` per process served the device that happened to be current at the first call -- a later launch on another device asked for 144 KB of LDS
-// without the attribute and sized its grid by device 0. The static lives in this template, i.e. once per call site (each passes its own lambda type).
-template <typename F>
-inline int pm_device_once(F&& setup) {
-  static int ncu[32] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-  if (!ncu[dev]) {
-    setup();
-    int n = 256;
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    ncu[dev] = n > 0 ? n : 256;
-  }
-  return ncu[dev];
+// The > 64 KB dynamic-LDS opt-in of ONE kernel, made once per device, and the CU count of the current device (persistent kernels size their grid by it). Declare it
+// `static` inside the kernel's (per-instantiation) launch template, one object per kernel: many kernels share one function-pointer type, so nothing keyed on that type
+// would do. ADVICE r5: a per-process flag served the device that happened to be current at the first call. Safe from several threads: a device is marked done only
+// after hipFuncSetAttribute succeeded; a failed call is cleared and retried at the next launch, which meanwhile reports its own error for a plan beyond 64 KB.
+constexpr int PM_MAX_DEVICES = 64;
+inline int pm_device_cus(int dev) {
+  static std::atomic<int> cached[PM_MAX_DEVICES];
+  const bool keep = dev >= 0 && dev < PM_MAX_DEVICES;
+  int n = keep ? cached[dev].load(std::memory_order_relaxed) : 0;
+  if (n > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (keep) cached[dev].store(n, std::memory_order_relaxed);
+  return n;
 }
+struct pm_lds_optin {
+  std::atomic<bool> done[PM_MAX_DEVICES] = {};
+  int operator()(const void* kernel, int lds_bytes) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const bool keep = dev >= 0 && dev < PM_MAX_DEVICES;
+    if (!keep || !done[dev].load(std::memory_order_acquire)) {
+      if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) (void)hipGetLastError();
+      else if (keep) done[dev].store(true, std::memory_order_release);
+    }
+    return pm_device_cus(dev);
+  }
+};
 
 // the library's routing state (conv_igemm.hip): one struct, see include/pinmem_hip.h pm_routing
 extern pm_routing pm_route;

@@ -181,7 +181,8 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
 template <int KG, int NB>
 void pws_launch(const PwsK& k, int grid, hipStream_t st) {
   const size_t smem = (size_t)KG * 2 * 3 * 1024 + 3 * 64 * sizeof(float) + 4 * 32 * 144;      // weight planes | epilogue constants | one staging patch per wave
-  pm_device_once([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pwstream_kernel<KG, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); });      // K = 128: 67 KB
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&pwstream_kernel<KG, NB>), 80 * 1024);      // K = 128: 67 KB
   hipLaunchKernelGGL((pwstream_kernel<KG, NB>), dim3(grid), dim3(256), smem, st, k);
 }
 
@@ -190,12 +191,11 @@ void pws_launch(const PwsK& k, int grid, hipStream_t st) {
 // Does this pointwise GEMM take the streaming kernel? K = 64 / 128 floats per (contiguous, 16-byte aligned) row, N a multiple of 64 with N / 64 in {1, 2, 4, 8}, enough rows
 // to give every wave of the 512 blocks a few tiles, 32-bit byte offsets.
 bool pm_pwstream_ok(const pm_gemm_pw* g) {
-  static const int on = getenv("PM_PWSTREAM") ? atoi(getenv("PM_PWSTREAM")) : 1;
-  static const long min_rows = getenv("PM_PWSTREAM_MIN_ROWS") ? atol(getenv("PM_PWSTREAM_MIN_ROWS")) : 65536;
-  if (!on || (g->K != 64 && g->K != 128)) return false;
+  constexpr long MIN_ROWS = 65536;
+  if (g->K != 64 && g->K != 128) return false;
   const int slabs = g->Nn / 64;
   if (g->Nn % 64 || (slabs != 1 && slabs != 2 && slabs != 4 && slabs != 8)) return false;
-  if (g->M < min_rows || (g->a_pitch & 3) || ((uintptr_t)g->A & 15) || (g->c_pitch & 3) || ((uintptr_t)g->C & 15)) return false;
+  if (g->M < MIN_ROWS || (g->a_pitch & 3) || ((uintptr_t)g->A & 15) || (g->c_pitch & 3) || ((uintptr_t)g->C & 15)) return false;
   if (g->residual && ((g->res_pitch & 3) || ((uintptr_t)g->residual & 15))) return false;
   if ((double)g->M * (double)g->a_pitch * 4.0 >= 4.0e9 || (double)g->M * (double)g->c_pitch * 4.0 >= 4.0e9) return false;
   if (g->residual && (double)g->M * (double)g->res_pitch * 4.0 >= 4.0e9) return false;

@@ -618,11 +618,8 @@ int pm_wino_dw_xf(const float* slab, int ks, int Cout, int Cin, int Kp, int m, f
 // GEMMs + output transform in one kernel (F(4x4) only): V [36][tiles][Kp] x U [36][Cout][Kp] -> y with the fused epilogue.
 int pm_wino_fused_f4(const float* V, const float* U, int Cout, int Kp, const pm_wino_geom& g, float* y, long ypitch, const float* bias, const float* scale,
                      const float* shift, const float* residual, long res_pitch, int relu, hipStream_t st) {
-  static const bool attr_set = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_fused_f4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WF_LDS);
-    return true;
-  }();
-  (void)attr_set;
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(&wino_fused_f4_kernel), (int)WF_LDS);
   WinoFusedArgs a;
   a.V = V, a.U = U, a.y = y, a.yp = ypitch, a.Cout = Cout, a.Kp = Kp, a.g = g;
   a.bias = bias, a.scale = scale, a.shift = shift, a.residual = residual, a.rp = res_pitch, a.relu = relu;

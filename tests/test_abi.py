@@ -2,6 +2,8 @@
 (no compute calls here -- there is no GPU in the build container)."""
 import os
 import re
+import subprocess
+import sys
 
 from pinthememory_amd import build
 from pinthememory_amd.hip import lib as L
@@ -85,3 +87,24 @@ def test_routing_is_one_struct_with_single_field_wrappers():
             setattr(r, k, v)
         assert lib.pm_routing_set(byref(r)) == 0
     assert lib.pm_routing_get(byref(r)) == 0 and {k: getattr(r, k) for k, _ in L.PmRouting._fields_} == before
+
+
+def test_set_conv16_restores_the_routing_read_at_load():
+    """pm_set_conv16(1) puts conv16_wide / conv16_persistent back to the values the library read from its environment when it was loaded, not to whatever
+    the routing held at the first pm_set_conv16 call. A fresh process with no PM_* variable set (the library is loaded once per process): both defaults are 1."""
+    L.load()
+    code = '''
+import ctypes, sys
+from ctypes import byref
+from pinthememory_amd.hip.lib import PmRouting
+lib = ctypes.CDLL(sys.argv[1])
+r = PmRouting(ctypes.sizeof(PmRouting))
+assert lib.pm_routing_get(byref(r)) == 0
+r.conv16_wide = r.conv16_persistent = 0
+assert lib.pm_routing_set(byref(r)) == 0 and lib.pm_set_conv16(1) == 0 and lib.pm_routing_get(byref(r)) == 0
+print(r.conv16_wide, r.conv16_persistent)
+'''
+    env = {k: v for k, v in os.environ.items() if not k.startswith('PM_')}
+    out = subprocess.run([sys.executable, '-c', code, L.LIB_PATH], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == ['1', '1']
