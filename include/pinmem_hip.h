@@ -89,7 +89,10 @@ int pm_version(void);
  * dtypes: all PM_F32 = the parity path. The bf16 tier (BASELINE configs[2]) is entered by prec = 2 or by any PM_BF16 tensor: x / y / dy / dx / add may each be
  * bf16 (c % 8 == 0, pitch % 8 == 0) or fp32 (the image in, the class logits and their gradient out); weights, dw, dbias, bias / scale / shift stay fp32,
  * every product is accumulated in fp32 and rounded once on the way out. A bf16 input whose channel count is not a multiple of 64 is gathered in place
- * only with PM_TF_ZERO_PAD64, else it is copied to a zero-padded workspace buffer first. */
+ * only with PM_TF_ZERO_PAD64, else it is copied to a zero-padded workspace buffer first.
+ * Size queries: a query and the call it sizes resolve ONE plan (same tensors, parameters and routing state -> same route, same buffer layout), so an entry point
+ * requires exactly the bytes pm_conv_workspace answers for it -- PM_EWORKSPACE with one byte less -- and writes nothing behind them. The other queries read the
+ * same plan: what a caller may keep between calls (Winograd V, transformed filter) and whether the forward call can emit bn_partials. */
 size_t pm_conv_workspace(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p, int which /*0 fwd,1 dgrad,2 wgrad*/);
 size_t pm_conv_winograd_v_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p);
 size_t pm_conv_wxf_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p);   /* 0: pm_conv_fwd keeps no transformed filter for this call */

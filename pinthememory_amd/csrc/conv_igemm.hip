@@ -255,6 +255,15 @@ inline S2Class s2_class(int cls, const pm_tensor* dx, const pm_conv_params* p) {
   c.M = (long)dx->n * c.Hc * c.Wc;
   return c;
 }
+// both stride-2 routes end here: compact fp32 class buffers (class_stride floats apart) -> dx, plus the fused skip gradient (`add`: dx's type)
+int s2_interleave(const float* tmp, long class_stride, const bool* valid, const pm_tensor* dx, const pm_tensor* add, hipStream_t st, const char* what) {
+  const int valid_mask = valid[0] | (valid[1] << 1) | (valid[2] << 2) | (valid[3] << 3);
+  const long total = pm_pixels(dx) * (dx->c / 4);
+  auto kernel = pm_is_bf16(dx) ? dgrad_s2_interleave_kernel<true> : dgrad_s2_interleave_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, tmp, class_stride, valid_mask, (float*)dx->ptr, (long)dx->pitch,
+                     dx->n, dx->h, dx->w, dx->c, add ? (const float*)add->ptr : nullptr, add ? (long)add->pitch : 0l);
+  return pm_check_launch(what);
+}
 
 struct Plan {
   int bm, bn;    // block tile: bm 128 / 64, bn 128 / 64 / 32
@@ -371,6 +380,24 @@ struct ProfRec {
 };
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
+// One launch's record: the constructor fills it and records `a` on the stream, done() records `b` and files it (after a launch that was enqueued; a caller
+// may adjust `rec` in between). Nothing is created or recorded while profiling is off.
+struct ProfScope {
+  ProfRec rec{};
+  hipStream_t st;
+  ProfScope(hipStream_t st_, int mode, int bm, int bn, int km, int prec, int nst, long M, long Nn, long K, int batch, int ksplit, double flops, double bytes = 0.0) : st(st_) {
+    if (!g_prof_on) return;
+    (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
+    rec.mode = mode, rec.bm = bm, rec.bn = bn, rec.km = km, rec.prec = prec, rec.nst = nst, rec.M = (int)M, rec.Nn = (int)Nn, rec.K = (int)K, rec.batch = batch, rec.ksplit = ksplit;
+    rec.flops = flops, rec.bytes = bytes;
+    (void)hipEventRecord(rec.a, st);
+  }
+  void done() {
+    if (!g_prof_on) return;
+    (void)hipEventRecord(rec.b, st);
+    g_prof.push_back(rec);
+  }
+};
 
 inline bool split_takes(int mode, const Plan& p, const ConvK& k, int batch) {      // batched launches (the Winograd point products: their output stays in L2) at every K
   return pm_route.split != 0 && p.bn >= 64 && !k.io16 && (batch > 1 || split_k_ok(mode, k.K));
@@ -392,13 +419,10 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
     const int units = batch * p.ksplit, rem = units & 7, ntile = p.tiles_m * p.tiles_n;
     k.batch_xcd = units >= 8 && (rem == 0 || ((rem == 1 || rem == 2 || rem == 4) && ntile % (8 / rem) == 0));
   }
-  ProfRec rec{};
-  if (g_prof_on) {
-    (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-    rec.mode = MODE, rec.bm = p.bm, rec.bn = p.bn, rec.km = (MODE == MODE_WGRAD && k.kmode == K_FAST) ? K_MID : ((k.prec == 5 && MODE != MODE_WGRAD && k.kmode == K_FAST && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) ? K_PW : k.kmode), rec.prec = k.prec, rec.nst = lds_stages(MODE, k.kmode, p.bn, k.kper), rec.M = k.M, rec.Nn = k.Nn, rec.K = k.K, rec.batch = batch, rec.ksplit = p.ksplit, rec.flops = flops >= 0.0 ? flops : 2.0 * (double)k.M * (double)k.Nn * (double)k.K * batch;
-    rec.bytes = (double)batch * ((double)k.a_bytes + (double)k.b_bytes + ((k.io16 && p.ksplit == 1) ? 2.0 : 4.0) * (double)k.M * (double)k.Nn * (double)p.ksplit);
-    (void)hipEventRecord(rec.a, st);
-  }
+  const int km = (MODE == MODE_WGRAD && k.kmode == K_FAST) ? K_MID : ((k.prec == 5 && MODE != MODE_WGRAD && k.kmode == K_FAST && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) ? K_PW : k.kmode);
+  ProfScope prof(st, MODE, p.bm, p.bn, km, k.prec, lds_stages(MODE, k.kmode, p.bn, k.kper), k.M, k.Nn, k.K, batch, p.ksplit,
+                 flops >= 0.0 ? flops : 2.0 * (double)k.M * (double)k.Nn * (double)k.K * batch,
+                 (double)batch * ((double)k.a_bytes + (double)k.b_bytes + ((k.io16 && p.ksplit == 1) ? 2.0 : 4.0) * (double)k.M * (double)k.Nn * (double)p.ksplit));
   if constexpr (MODE != MODE_WGRAD) {      // short pointwise reductions of the fp32 tier stream wave by wave (pwstream.hip): the split path's arithmetic, no tiles
     if (pm_route.split && (k.prec == 0 || k.prec == 5) && !k.io16 && batch == 1 && p.ksplit == 1 && !k.stats && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) {      // fp32 operands only (prec 1 / 2: bf16-operand forms of the older tier)
       pm_gemm_pw g;
@@ -407,12 +431,9 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
       g.b_sn = MODE == MODE_FWD ? k.K : 1, g.b_sk = MODE == MODE_FWD ? 1 : k.Nn;
       g.M = k.M, g.Nn = k.Nn, g.K = k.K, g.relu = k.relu;
       if (pm_pwstream_ok(&g)) {
-        if (g_prof_on) rec.bm = 32, rec.bn = 64, rec.km = 4, rec.prec = 5, rec.nst = 0;
+        prof.rec.bm = 32, prof.rec.bn = 64, prof.rec.km = 4, prof.rec.prec = 5, prof.rec.nst = 0;
         const int e = pm_pwstream_launch(&g, st);
-        if (g_prof_on) {
-          (void)hipEventRecord(rec.b, st);
-          g_prof.push_back(rec);
-        }
+        prof.done();
         return e;
       }
     }
@@ -420,11 +441,8 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   constexpr bool akc = MODE != MODE_WGRAD, bkc = MODE == MODE_FWD;
   if (k.prec == 5) {      // fp32 operands, three-way bf16 split, six products on the bf16 matrix pipe (conv_split.hip)
     if (int e = pm_conv_split_launch(MODE, p.bm, p.bn, k, grid.x, grid.y, grid.z, pm_conv_split_stage_bytes(MODE, p.bm, p.bn), st)) return e;
-    if (g_prof_on) {
-      rec.nst = 1;
-      (void)hipEventRecord(rec.b, st);
-      g_prof.push_back(rec);
-    }
+    prof.rec.nst = 1;
+    prof.done();
     return pm_check_launch("conv_split");
   }
   const bool tr = MODE == MODE_WGRAD && (k.prec == 3 || k.prec == 4) && p.bn >= 64;      // bf16 [k][m + 32] tiles: 2 bytes per element
@@ -442,10 +460,7 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   } else {
     launch_one<MODE, 128, 32, 4, 1>(k, grid, smem(128, 32), st);
   }
-  if (g_prof_on) {
-    (void)hipEventRecord(rec.b, st);
-    g_prof.push_back(rec);
-  }
+  prof.done();
   return pm_check_launch("conv_igemm");
 }
 
@@ -501,9 +516,10 @@ struct WinoPlan {
   size_t v_bytes, m_bytes, u_bytes;
   Plan pl;
 };
+inline bool wino_wgrad_pays(int cin, int cout) { return (long)cin * cout >= 256 * 256; }   // two transforms + slabs per GEMM: pays from 256 x 256 channels up
 WinoPlan wino_plan(const pm_tensor* xin, int cout, const pm_conv_params* p, bool wgrad = false) {
   WinoPlan wp{};
-  if (wgrad && (long)xin->c * cout < 256 * 256) return wp;   // two transforms + slabs per GEMM: pays from 256 x 256 channels up
+  if (wgrad && !wino_wgrad_pays(xin->c, cout)) return wp;
   if (pm_route.winograd == 0 || p->kh != 3 || p->kw != 3 || p->stride != 1 || p->pad != p->dil || p->prec != 0) return wp;
   const int cin = xin->c;
   if (cin < 128 || cout < 128 || (cout & 3) || (cin & 3)) return wp;
@@ -567,18 +583,9 @@ int wino_conv(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
   // 4600 MFMA cycles. Bounds measured on the unfused path: a GEMM that never stores M -3.3 ms/step, no output-transform pass either -5.6 ms/step.
   // Kept as an opt-in (PM_WINO_FUSED=1) with its tests; the default is the batched GEMM + wino_output_kernel.
   if (pm_route.winograd_fused && wp.g.m == 4 && wp.Kp % 16 == 0) {
-    ProfRec rec{};
-    if (g_prof_on) {
-      (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-      rec.mode = 3, rec.bm = 32, rec.bn = 32, rec.km = 0, rec.prec = 0, rec.nst = 1, rec.M = (int)wp.g.tiles, rec.Nn = cout, rec.K = wp.Kp, rec.batch = wp.P, rec.ksplit = 1;
-      rec.flops = 2.0 * wp.P * (double)wp.g.tiles * cout * xin->c;
-      (void)hipEventRecord(rec.a, st);
-    }
+    ProfScope prof(st, 3, 32, 32, 0, 0, 1, wp.g.tiles, cout, wp.Kp, wp.P, 1, 2.0 * wp.P * (double)wp.g.tiles * cout * xin->c);
     const int e = pm_wino_fused_f4(V, U, cout, wp.Kp, wp.g, (float*)yout->ptr, yout->pitch, ep.bias, ep.scale, ep.shift, ep.residual, ep.residual_pitch, ep.relu, st);
-    if (g_prof_on) {
-      (void)hipEventRecord(rec.b, st);
-      g_prof.push_back(rec);
-    }
+    prof.done();
     return e;
   }
   if (int e = launch<MODE_FWD>(k, wp.pl, st, wp.P, 2.0 * wp.P * (double)wp.g.tiles * cout * xin->c)) return e;
@@ -702,7 +709,6 @@ int conv_bf16(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
   const long xpitch16 = b.inplace ? xin->pitch : b.Cp;                       // bf16 elements between pixels
   if (b.c16) {
     const bool o16 = pm_is_bf16(yout);
-    const bool ep_any = e0.bias || e0.scale || e0.residual || e0.relu;
     // what the kernel's two epilogues cover: bf16 rows of whole 16-byte groups with the full fused epilogue, or fp32 rows with at most a bias; no statistics
     const bool ok = (!e0.bn_partials || o16) &&
                     (o16 ? ((yout->c | yout->pitch | (e0.residual ? e0.residual_pitch : 0)) & 7) == 0 && pm_aligned16(yout->ptr) && pm_aligned16(e0.residual)
@@ -712,13 +718,7 @@ int conv_bf16(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
       k.A = (const pm_bf16*)xb, k.B = (const pm_bf16*)wb;
       // EXECUTED FLOPs: the K-steps of filter rows that no row of a tile can see are skipped by the kernel (dilated ASPP branches) and are not counted
       const double fl = 2.0 * (double)b.M * (double)b.Nn * (double)T * (double)xin->c * (g_prof_on ? pm_conv16_executed_fraction(&k) : 1.0);
-      ProfRec rec{};
-      if (g_prof_on) {
-        (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-        rec.mode = k.wide ? 5 : 4, rec.bm = k.bm, rec.bn = k.bn, rec.km = pm_conv16w_persistent(&k), rec.prec = 5, rec.nst = k.wide ? 3 : (k.ksteps_per == 1 ? 1 : 2), rec.M = k.M, rec.Nn = k.Nn, rec.K = k.K / 2, rec.batch = 1,
-        rec.ksplit = k.ksplit, rec.flops = fl;
-        (void)hipEventRecord(rec.a, st);
-      }
+      ProfScope prof(st, k.wide ? 5 : 4, k.bm, k.bn, pm_conv16w_persistent(&k), 5, k.wide ? 3 : (k.ksteps_per == 1 ? 1 : 2), k.M, k.Nn, k.K / 2, 1, k.ksplit, fl);
       int e;
       if (k.ksplit > 1) {
         k.C = slab;
@@ -729,15 +729,11 @@ int conv_bf16(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
         k.stats = o16 ? e0.bn_partials : nullptr;
         e = pm_conv16_launch(&k, st);
       }
-      if (g_prof_on) {
-        (void)hipEventRecord(rec.b, st);
-        g_prof.push_back(rec);
-      }
+      prof.done();
       if (e) return e;
       if (k.ksplit > 1)
         return splitk_reduce(slab, k.ksplit, b.M, b.Nn, (float*)yout->ptr, (long)yout->pitch, e0.bias, e0.scale, e0.shift, e0.residual, (long)e0.residual_pitch, e0.relu,
                              st, o16);
-      (void)ep_any;
       return PM_OK;
     }
   }
@@ -832,38 +828,25 @@ S2Native s2_native_plan(const pm_tensor* dy, const pm_tensor* dx, const pm_conv_
   s.ok = true;
   return s;
 }
-int dgrad_s2_bf16(const pm_tensor* dy, const float* w, const pm_tensor* dx, const pm_conv_params* p, const pm_tensor* add, S2Native& s, void* ws, hipStream_t st) {
-  for (int cls = 0; cls < 4; ++cls) s.cl.out[cls] = (char*)ws + s.wb_off[cls];
-  if (int e = pm_bf16_cast_weights_s2(w, dy->c, p->kh, p->kw, dx->c, dy->c, &s.cl, st)) return e;
+int dgrad_s2_bf16(const pm_tensor* dy, const float* w, const pm_tensor* dx, const pm_conv_params* p, const pm_tensor* add, const S2Native& s, void* ws, hipStream_t st) {
+  PmS2Classes cl = s.cl;
+  for (int cls = 0; cls < 4; ++cls) cl.out[cls] = (char*)ws + s.wb_off[cls];
+  if (int e = pm_bf16_cast_weights_s2(w, dy->c, p->kh, p->kw, dx->c, dy->c, &cl, st)) return e;
   float* slab = (float*)((char*)ws + s.slab_off);
   for (int cls = 0; cls < 4; ++cls) {
     if (!s.valid[cls]) continue;
     pm_conv16 k = s.k[cls];
     k.A = (const pm_bf16*)dy->ptr, k.B = (const pm_bf16*)((char*)ws + s.wb_off[cls]);
     void* out = (char*)ws + s.out_off[cls];
-    ProfRec rec{};
-    if (g_prof_on) {
-      (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-      rec.mode = 4, rec.bm = k.bm, rec.bn = k.bn, rec.km = 0, rec.prec = 5, rec.nst = k.ksteps_per == 1 ? 1 : 2, rec.M = k.M, rec.Nn = k.Nn, rec.K = k.K / 2, rec.batch = 1,
-      rec.ksplit = k.ksplit, rec.flops = 2.0 * (double)k.M * (double)k.Nn * (double)k.K;
-      (void)hipEventRecord(rec.a, st);
-    }
+    ProfScope prof(st, 4, k.bm, k.bn, 0, 5, k.ksteps_per == 1 ? 1 : 2, k.M, k.Nn, k.K / 2, 1, k.ksplit, 2.0 * (double)k.M * (double)k.Nn * (double)k.K);
     k.C = k.ksplit > 1 ? (void*)slab : out;
     const int e = pm_conv16_launch(&k, st);
-    if (g_prof_on) {
-      (void)hipEventRecord(rec.b, st);
-      g_prof.push_back(rec);
-    }
+    prof.done();
     if (e) return e;
     if (k.ksplit > 1)
       if (int e2 = splitk_reduce(slab, k.ksplit, k.M, k.Nn, (float*)out, (long)dx->c, nullptr, nullptr, nullptr, nullptr, 0l, 0, st, false)) return e2;
   }
-  const int valid_mask = s.valid[0] | (s.valid[1] << 1) | (s.valid[2] << 2) | (s.valid[3] << 3);
-  const long total = pm_pixels(dx) * (dx->c / 4);
-  hipLaunchKernelGGL(dgrad_s2_interleave_kernel<true>, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, (const float*)((char*)ws + s.out_off[0]),
-                     s.class_stride, valid_mask, (float*)dx->ptr, (long)dx->pitch, dx->n, dx->h, dx->w, dx->c, add ? (const float*)add->ptr : nullptr,
-                     add ? (long)add->pitch : 0l);
-  return pm_check_launch("dgrad_s2_interleave(native bf16 classes)");
+  return s2_interleave((const float*)((char*)ws + s.out_off[0]), s.class_stride, s.valid, dx, add, st, "dgrad_s2_interleave(native bf16 classes)");
 }
 
 struct Bf16WgradPlan {
@@ -923,10 +906,259 @@ void gemm_dims(int which, const pm_tensor* x, const pm_tensor* y, const pm_conv_
   else M = y->c, Nn = T * x->c, K = pm_pixels(y);
 }
 
+// stride-2 data gradient, fp32 rows. Only taps with (iy + pad - ky*dil) even reach an output pixel: the input pixels are split into their four parity classes,
+// a dense dgrad runs over each class with its matching tap subset (1/4 of the MFMA work of the masked formulation), the compact results are interleaved into dx.
+struct S2ParityPlan {
+  S2Class c[4];
+  Plan pl[4];
+  bool valid[4];
+  size_t tmp_bytes, slab_bytes;      // one compact class buffer; the largest split-K slab set of the four
+};
+S2ParityPlan s2_parity_plan(const pm_tensor* dy, const pm_tensor* dx, const pm_conv_params* p) {
+  S2ParityPlan s{};
+  for (int cls = 0; cls < 4; ++cls) {
+    const S2Class& c = s.c[cls] = s2_class(cls, dx, p);
+    s.tmp_bytes = std::max(s.tmp_bytes, (size_t)c.M * dx->c * sizeof(float));
+    s.valid[cls] = c.M > 0 && c.nky * c.nkx > 0;
+    if (!s.valid[cls]) continue;
+    s.pl[cls] = make_plan(MODE_DGRAD, c.M, dx->c, (long)c.nky * c.nkx * dy->c, p->prec != 0);
+    s.slab_bytes = std::max(s.slab_bytes, s.pl[cls].ws_bytes);
+  }
+  s.tmp_bytes = pm_align_up(s.tmp_bytes, 256);
+  return s;
+}
+
+// round 5, second session: both operands bf16 and Cin a multiple of the 128-channel block -> the LDS-DMA persistent ring of wgrad16.hip. Its units are
+// (256 x 128 tile, pixel range): the split is re-planned for one block per CU within the slab count the workspace was sized for (max_ksplit).
+struct W16Plan {
+  bool use;
+  pm_wgrad16 k;      // geometry, tile and split; the output pointer is filled at launch
+};
+W16Plan wgrad16_plan(const pm_tensor* x, const pm_tensor* dy, const pm_conv_params* p, long M, long Nn, long K, int max_ksplit) {
+  W16Plan q{};
+  pm_wgrad16& w16 = q.k;
+  w16.X = (const pm_bf16*)x->ptr, w16.DY = (const pm_bf16*)dy->ptr;
+  w16.N = x->n, w16.H = x->h, w16.W = x->w, w16.Ho = dy->h, w16.Wo = dy->w;
+  w16.x_pitch = x->pitch, w16.dy_pitch = dy->pitch, w16.Cin = x->c, w16.Cout = dy->c;
+  w16.kh = p->kh, w16.kw = p->kw, w16.stride = p->stride, w16.pad = p->pad, w16.dil = p->dil;
+  w16.M = (int)M, w16.Nn = (int)Nn, w16.P = (int)K, w16.kper = 64, w16.c_split = M * Nn;
+  q.use = K < (1l << 30) && pm_wgrad16_plan(&w16);
+  if (!q.use) return q;
+  const long tiles = (long)w16.tiles_m * w16.tiles_n, steps = (K + 63) / 64;
+  int best_ks = 1;
+  double best = 1e30;
+  for (int ks = 1; ks <= max_ksplit; ++ks) {
+    const long per = (steps + ks - 1) / ks, kse = (steps + per - 1) / per;
+    const long rounds = (tiles * kse + 255) / 256;
+    // a unit costs its K-steps + ~6 steps of epilogue / hand-over; slabs: written and read back by the reduce (bytes / ~4 TB/s in K-steps of ~1 us)
+    const double cost = (double)rounds * (per + 6) + (kse > 1 ? (double)kse * M * Nn * 8.0 / 4e12 / 1.0e-6 : 0.0);
+    if (cost < best) best = cost, best_ks = (int)kse;
+  }
+  const long per = (steps + best_ks - 1) / best_ks;
+  w16.kper = (int)per * 64, w16.ksplit = (int)((steps + per - 1) / per);
+  return q;
+}
+
+// ---- the route of one convolution call -------------------------------------------------------------------------------------------------------------------------
+// Which kernel family takes a call, the plan it runs with, where its buffers lie in the workspace and every size the caller may ask for are decided ONCE, in
+// route_conv. The size queries (pm_conv_workspace, pm_conv_winograd_v_bytes, pm_conv_wxf_bytes, pm_conv_wxf_bytes_dgrad, pm_conv_bn_partials_bytes) are field reads
+// of its result; the entry points validate their arguments, resolve the route, require exactly ws_bytes and switch on `kind` into a worker that takes its plan and
+// its offsets from the route. What depends on the epilogue and not on the shape is still decided at launch: conv_bf16's test of the LDS-DMA kernel's epilogue,
+// launch()'s pwstream and split tests.
+// A sub-plan lays out its own buffers from offset 0 (WinoPlan: V | M | U; Bf16Plan: padded x | bf16 w | slabs; S2Native: its *_off fields; Bf16WgradPlan: dyt | xt | slabs;
+// the direct GEMM: slabs); the route adds the regions that follow and the total.
+enum RouteKind {
+  R_DIRECT,            // the implicit-GEMM kernel on fp32 rows (forward / stride-1 data gradient), split-K slabs at offset 0
+  R_WINO,              // Winograd forward / data gradient (`wino`)
+  R_BF16,              // bf16 operands in forward form (`b16`, geometry `pe`): forward, and the stride-1 data gradient via dgrad_as_fwd
+  R_S2_NATIVE,         // stride-2 data gradient, bf16 classes on the LDS-DMA kernel (`s2n`)
+  R_S2_PARITY,         // stride-2 data gradient, fp32 parity classes (`s2p`); a bf16 dy is widened at dy32_off
+  R_WINO_WGRAD,        // Winograd weight gradient (`wino`, `wino_w`)
+  R_BF16_WGRAD,        // transposed-bf16 weight gradient (`b16w`)
+  R_DIRECT_WGRAD,      // the implicit-GEMM weight gradient (`pl`), or the wgrad16 ring where `w16.use`
+};
+struct ConvRoute {
+  RouteKind kind;
+  Plan pl;
+  WinoPlan wino;
+  WinoWgradPlan wino_w;
+  Bf16Plan b16;
+  pm_conv_params pe;
+  S2Native s2n;
+  S2ParityPlan s2p;
+  Bf16WgradPlan b16w;
+  W16Plan w16;
+  bool native16;                   // weight gradient with both operands bf16 and Cout >= 32: gathered as bf16 (PREC 4), no fp32 copies
+  size_t ws_bytes;                 // what pm_conv_workspace answers and the entry point requires
+  size_t class_off, slab_off;      // R_S2_PARITY: four class buffers of s2p.tmp_bytes, then the slabs
+  size_t bias_off;                 // weight gradient: the bias-gradient partials, behind the route's own buffers
+  size_t x32_off, dy32_off;        // fp32 copies of a bf16 x / dy at the tail (the mixed-type call sites)
+  size_t v_keep_bytes;             // forward: Winograd V worth keeping (forward and weight gradient both on the route, with the same m)
+  size_t wxf_bytes;                // transformed filter the caller may keep: Winograd U (forward) or the bf16 copy (forward / data-gradient flavour)
+  size_t bn_bytes;                 // forward: bn_partials this call can emit (0: it cannot), for a call that passes check_common
+};
+
+// x, y: input and output tensor of the convolution for every `which` (the data gradient reads y = dy and writes x = dx); p: after tier_params.
+ConvRoute route_conv(int which, const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p) {
+  ConvRoute r{};
+  long M, Nn, K;
+  gemm_dims(which, x, y, p, M, Nn, K);
+  if (which == MODE_FWD) {
+    if ((r.wino = wino_plan(x, y->c, p)).use) {
+      r.kind = R_WINO, r.ws_bytes = wino_ws(r.wino), r.wxf_bytes = r.wino.u_bytes;
+      r.v_keep_bytes = wino_wgrad_pays(x->c, y->c) ? r.wino.v_bytes : 0;      // (the weight gradient's plan differs from the forward's by that test only)
+    } else if (p->prec == 2 && (r.b16 = bf16_plan(x, y, p)).use) {
+      r.kind = R_BF16, r.pe = *p, r.ws_bytes = bf16_ws(r.b16), r.wxf_bytes = r.b16.wb_bytes;
+    } else {      // what is left gathers fp32 rows: fp32 convolutions, and on the bf16 tier the 4-channel stem (fp32 image in, bf16 out)
+      r.kind = R_DIRECT, r.pl = make_plan(MODE_FWD, M, Nn, K, p->prec != 0), r.ws_bytes = pm_align_up(r.pl.ws_bytes, 256);
+    }
+    // Can this call hand the BatchNorm statistics of its output out of its own epilogue? bf16 tier: both bf16 kernels carry them in their 8-column staged epilogue
+    // (one K split, whole 16-byte groups). fp32: only the unbatched direct GEMM with one K split and a 16-byte-aligned output takes the staged epilogue; everything
+    // else (Winograd route, split-K, the 19-class heads, the staged-fp32 bf16 form: no statistics instantiation) answers 0.
+    bool bn;
+    if (pm_is_bf16(y)) bn = pm_vec8(y) && r.kind == R_BF16 && (r.b16.c16 ? (r.b16.k16.ksplit == 1 && !r.b16.k16.wide) : r.b16.pl.ksplit == 1);
+    else if (pm_is_bf16(x) || (y->c & 3) || (y->pitch & 3) || !pm_aligned16(y->ptr)) bn = false;
+    else bn = r.kind == R_BF16 ? r.b16.pl.ksplit == 1 : (r.kind == R_DIRECT && p->prec == 0 && r.pl.ksplit == 1 && r.pl.bn >= 64);
+    r.bn_bytes = bn ? pm_align_up((size_t)pm_cdiv(pm_pixels(y), 32) * y->c * 2 * sizeof(float), 256) : 0;
+  } else if (which == MODE_DGRAD) {
+    if (p->stride == 2) {   // four parity classes: compact results + the largest split-K slab set
+      if ((r.s2n = s2_native_plan(y, x, p)).ok) {
+        r.kind = R_S2_NATIVE, r.ws_bytes = r.s2n.total;
+      } else {      // bf16 tier, shapes the native form does not take: the parity-class gather reads fp32 rows -- dy (a quarter of dx's pixels) is widened once, at the end of the workspace
+        r.kind = R_S2_PARITY, r.s2p = s2_parity_plan(y, x, p);
+        r.class_off = 0, r.slab_off = 4 * r.s2p.tmp_bytes;
+        r.dy32_off = pm_align_up(r.slab_off + r.s2p.slab_bytes + 256, 256);
+        r.ws_bytes = r.dy32_off + upcast_bytes(y);
+      }
+    } else if (dgrad_bf16_ok(p) && (r.pe = dgrad_as_fwd(p), r.b16 = bf16_plan(y, x, &r.pe)).use) {   // data gradient of a stride-1 convolution = forward convolution of dy with the rotated / transposed filter
+      r.kind = R_BF16, r.ws_bytes = bf16_ws(r.b16), r.wxf_bytes = r.b16.wb_bytes;
+    } else if ((r.wino = wino_plan(y, x->c, p)).use) {
+      r.kind = R_WINO, r.ws_bytes = wino_ws(r.wino);
+    } else {
+      r.kind = R_DIRECT, r.pl = make_plan(MODE_DGRAD, M, Nn, K, p->prec != 0), r.ws_bytes = pm_align_up(r.pl.ws_bytes, 256);
+    }
+  } else {
+    // bf16 tier. Both operands bf16: the gather moves 16 bytes = eight channels per lane straight into the bf16 LDS tiles of the transpose-read form (PREC 4).
+    // Mixed types (fp32 image x bf16 dy: the stem; bf16 x x fp32 dy: the 19-class heads) and a bias gradient over a bf16 dy: the bf16 side is widened to a
+    // dense fp32 copy at the end of the workspace and the call proceeds as the fp32-gather form (PREC 3) -- small tensors, once per step.
+    const bool tier = pm_is_bf16(x) || pm_is_bf16(y);
+    r.native16 = pm_is_bf16(x) && pm_is_bf16(y) && y->c >= 32;
+    size_t own;      // the route's own buffers; the bias partials follow them
+    if (!tier && (r.b16w = bf16_wgrad_plan(x, y, p)).use) {
+      r.kind = R_BF16_WGRAD, own = bf16_wgrad_ws(r.b16w);
+    } else if (!tier && (r.wino = wino_plan(x, y->c, p, true)).use) {
+      r.kind = R_WINO_WGRAD, r.wino_w = wino_wgrad_plan(r.wino, y->c), own = wino_wgrad_ws(r.wino, r.wino_w);
+    } else {
+      r.kind = R_DIRECT_WGRAD, r.pl = make_plan(MODE_WGRAD, M, Nn, K, p->prec != 0), own = r.pl.ws_bytes;
+      if (r.native16) {
+        // the PREC 4 kernel steps 64 pixels at a time: the K range of a split must be a multiple of that (the slab count can only shrink, the workspace was sized for more)
+        r.pl.kper = (r.pl.kper + 63) / 64 * 64;
+        r.pl.ksplit = (int)((K + r.pl.kper - 1) / r.pl.kper);
+        r.w16 = wgrad16_plan(x, y, p, M, Nn, K, r.pl.ksplit);
+      }
+    }
+    r.bias_off = pm_align_up(own, 256);
+    r.ws_bytes = r.bias_off + pm_align_up((size_t)pm_cdiv(pm_pixels(y), colsum_rows(pm_pixels(y), y->c)) * y->c * sizeof(float), 256) + upcast_bytes(x) + upcast_bytes(y);
+    r.x32_off = r.dy32_off = r.ws_bytes;
+    if (!r.native16) r.x32_off -= upcast_bytes(x);
+    r.dy32_off = r.x32_off - upcast_bytes(y);
+  }
+  return r;
+}
+
+int dgrad_s2_parity(const pm_tensor* dy0, const float* w, const pm_tensor* dx, const pm_conv_params* p, const pm_tensor* add, const ConvRoute& r, void* ws, hipStream_t st) {
+  pm_tensor dy32;
+  if (int e = upcast(dy0, (char*)ws + r.dy32_off, &dy32, st)) return e;
+  const pm_tensor* dy = &dy32;
+  float* tmp = (float*)((char*)ws + r.class_off);
+  float* slab = (float*)((char*)ws + r.slab_off);
+  for (int cls = 0; cls < 4; ++cls) {
+    if (!r.s2p.valid[cls]) continue;
+    const S2Class& c = r.s2p.c[cls];
+    const Plan& pl = r.s2p.pl[cls];
+    ConvK k;
+    fill_geom(k, dx, dy, p);
+    k.A = (const float*)dy->ptr, k.B = w;
+    k.M = (int)c.M, k.Nn = dx->c, k.K = c.nky * c.nkx * dy->c;
+    k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * 4), k.b_bytes = (unsigned)((long)dy->c * p->kh * p->kw * dx->c * 4);
+    k.kmode = dy->c >= BK ? K_MID : K_SMALL;
+    k.T_eff = c.nky * c.nkx, k.tk_w = c.nkx, k.ky0 = c.ky0, k.kx0 = c.kx0, k.ksy = c.ksy, k.ksx = c.ksx;
+    k.sub = 1, k.sub_cy = c.cy, k.sub_cx = c.cx, k.Hc = c.Hc, k.Wc = c.Wc;
+    float* out = (float*)((char*)tmp + cls * r.s2p.tmp_bytes);
+    if (pl.ksplit > 1) {
+      k.C = slab, k.c_pitch = dx->c, k.c_split = c.M * dx->c;
+      if (int e = launch<MODE_DGRAD>(k, pl, st)) return e;
+      if (int e = splitk_reduce(slab, pl.ksplit, c.M, dx->c, out, (long)dx->c, nullptr, nullptr, nullptr, nullptr, 0l, 0, st)) return e;
+    } else {
+      k.C = out, k.c_pitch = dx->c, k.c_split = 0;
+      if (int e = launch<MODE_DGRAD>(k, pl, st)) return e;
+    }
+  }
+  return s2_interleave(tmp, (long)(r.s2p.tmp_bytes / sizeof(float)), r.s2p.valid, dx, add, st, "dgrad_s2_interleave");
+}
+
+// the implicit-GEMM kernel on fp32 rows, forward (MODE_FWD: xin = x, out = y) and stride-1 data gradient (MODE_DGRAD: xin = dy, out = dx; only e.residual is set)
+template <int MODE>
+int conv_direct(const pm_tensor* x, const pm_tensor* y, const float* w, const pm_conv_params* p, const Plan& pl, const pm_conv_epilogue& e, void* ws, hipStream_t st) {
+  const pm_tensor *xin = MODE == MODE_FWD ? x : y, *out = MODE == MODE_FWD ? y : x;
+  long M, Nn, K;
+  gemm_dims(MODE, x, y, p, M, Nn, K);
+  ConvK k;
+  fill_geom(k, x, y, p);
+  k.io16 = pm_is_bf16(out) ? 1 : 0;
+  k.A = (const float*)xin->ptr, k.B = w;
+  k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
+  k.a_bytes = (unsigned)(pm_pixels(xin) * xin->pitch * 4), k.b_bytes = (unsigned)((long)y->c * p->kh * p->kw * x->c * 4);
+  k.kmode = (xin->c % BK == 0 && (MODE == MODE_FWD || p->stride == 1)) ? 0 : (xin->c >= BK ? 1 : 2);
+  if (pl.ksplit > 1) {
+    k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
+    if (int err = launch<MODE>(k, pl, st)) return err;
+    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)out->ptr, (long)out->pitch, e.bias, e.scale, e.shift, e.residual, (long)e.residual_pitch, e.relu, st, k.io16 != 0);
+  }
+  k.C = (float*)out->ptr, k.c_pitch = out->pitch, k.c_split = 0;
+  k.bias = e.bias, k.scale = e.scale, k.shift = e.shift, k.residual = e.residual, k.res_pitch = e.residual_pitch, k.relu = e.relu;
+  k.stats = e.bn_partials;
+  return launch<MODE>(k, pl, st);
+}
+
+// R_DIRECT_WGRAD. x / dy: the operands as gathered (bf16 where r.native16, else fp32 -- the caller's tensor or its widened copy)
+int conv_wgrad_direct(const pm_tensor* x, const pm_tensor* dy, float* dw, const pm_conv_params* p, const ConvRoute& r, void* ws, hipStream_t st) {
+  long M, Nn, K;
+  gemm_dims(MODE_WGRAD, x, dy, p, M, Nn, K);
+  if (r.w16.use) {
+    pm_wgrad16 w16 = r.w16.k;
+    w16.C = w16.ksplit > 1 ? (float*)ws : dw;
+    ProfScope prof(st, MODE_WGRAD, w16.bm, w16.bn, 2, 4, 3, M, Nn, K, 1, w16.ksplit, 2.0 * (double)M * (double)Nn * (double)K);
+    const int e = pm_wgrad16_launch(&w16, st);
+    prof.done();
+    if (e || w16.ksplit == 1) return e;
+    return splitk_reduce((const float*)ws, w16.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st);
+  }
+  ConvK k;
+  fill_geom(k, x, dy, p);
+  // configs[2]: the weight gradient gathers the fp32 rows as before, rounds them to bf16 on the way into LDS and reads its fragments through the
+  // transpose read (PREC 3): no transposed / per-tap copies of x in HBM.
+  if (p->prec == 2) k.prec = 3;
+  if (r.native16) {
+    PM_REQUIRE(x->c % 8 == 0 && dy->c % 8 == 0 && r.pl.bn >= 64, PM_EUNSUPPORTED, "conv_bwd_weight(bf16): channels %% 8 != 0 or a tile narrower than 64");
+    k.prec = 4;
+  }
+  const int esz = r.native16 ? 2 : 4;
+  k.A = (const float*)dy->ptr, k.B = (const float*)x->ptr;
+  k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
+  k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * esz), k.b_bytes = (unsigned)(pm_pixels(x) * x->pitch * esz), k.kmode = dy->w >= (r.native16 ? 2 * BK : BK) ? 1 : 2;
+  k.C = r.pl.ksplit > 1 ? (float*)ws : dw, k.c_pitch = Nn, k.c_split = r.pl.ksplit > 1 ? M * Nn : 0;
+  if (int e = launch<MODE_WGRAD>(k, r.pl, st)) return e;
+  if (r.pl.ksplit == 1) return PM_OK;
+  return splitk_reduce((const float*)ws, r.pl.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st);
+}
+
 }  // namespace
 
 // ---- the library's routing state: ONE struct (include/pinmem_hip.h pm_routing), initialised at load from the six PM_* variables below -- the only place the library
 // reads its environment -- and replaced as a whole by pm_routing_set. The pm_set_* entry points below are thin wrappers that change one field (kernel tests, A/B runs).
+// It is consulted in one place per call: route_conv above and the planners it calls (plus the launch-time tests of launch() and conv_bf16, which depend on the epilogue). A size
+// query and the entry point it sizes therefore see the same state as long as the caller keeps the header's contract (no change between the query and the call).
 static pm_routing routing_from_env() {
   auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
   return pm_routing{
@@ -1048,25 +1280,31 @@ extern "C" int pm_profile_dump(const char* path) {
   return PM_OK;
 }
 
+// ---- size queries: field reads of the route the matching entry point will resolve (same arguments, same routing state -> same plan) ----------------------------
+extern "C" size_t pm_conv_workspace(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p0, int which) {
+  const pm_conv_params tp = tier_params(p0, x, y);
+  return route_conv(which, x, y, &tp).ws_bytes;
+}
 extern "C" size_t pm_conv_winograd_v_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p0) {
   if (!x || !y || !p0) return 0;
   const pm_conv_params tp = tier_params(p0, x, y);
-  const pm_conv_params* p = &tp;
-  const WinoPlan f = wino_plan(x, y->c, p), g = wino_plan(x, y->c, p, true);   // forward and weight gradient both on the route
-  return (f.use && g.use && f.g.m == g.g.m) ? f.v_bytes : 0;
+  return route_conv(MODE_FWD, x, y, &tp).v_keep_bytes;
 }
-
 extern "C" size_t pm_conv_wxf_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p0) {
   if (!x || !y || !p0) return 0;
   const pm_conv_params tp = tier_params(p0, x, y);
-  const pm_conv_params* p = &tp;
-  const WinoPlan f = wino_plan(x, y->c, p);
-  if (f.use) return f.u_bytes;
-  if (p->prec == 2) {
-    const Bf16Plan b = bf16_plan(x, y, p);
-    if (b.use) return b.wb_bytes;
-  }
-  return 0;
+  return route_conv(MODE_FWD, x, y, &tp).wxf_bytes;
+}
+// the same for pm_conv_bwd_data: bytes of the rotated / transposed bf16 filter a stride-1 data gradient of the bf16 tier derives from w (0: none)
+extern "C" size_t pm_conv_wxf_bytes_dgrad(const pm_tensor* dy, const pm_tensor* dx, const pm_conv_params* p0) {
+  if (!dy || !dx || !p0) return 0;
+  const pm_conv_params tp = tier_params(p0, dy, dx);
+  return route_conv(MODE_DGRAD, dx, dy, &tp).wxf_bytes;
+}
+extern "C" size_t pm_conv_bn_partials_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p0) {
+  if (!x || !y || !p0 || check_common(x, y, p0) != PM_OK) return 0;
+  const pm_conv_params tp = tier_params(p0, x, y);
+  return route_conv(MODE_FWD, x, y, &tp).bn_bytes;
 }
 
 // fp32 tier: every kept Winograd forward transform U = G g Gt (what pm_conv_fwd writes into pm_conv_params.wxf when wxf_valid == 0) rewritten in one launch per 48
@@ -1091,93 +1329,6 @@ extern "C" int pm_conv_wxf_refresh_f32(const pm_wxf_job* jobs, int n, void* stre
   return pm_wino_filter_xf_multi(w.data(), U.data(), cout.data(), cin.data(), kp.data(), m.data(), n, (hipStream_t)stream);
 }
 
-// the same for pm_conv_bwd_data: bytes of the rotated / transposed bf16 filter a stride-1 data gradient of the bf16 tier derives from w (0: none)
-extern "C" size_t pm_conv_wxf_bytes_dgrad(const pm_tensor* dy, const pm_tensor* dx, const pm_conv_params* p0) {
-  if (!dy || !dx || !p0) return 0;
-  const pm_conv_params tp = tier_params(p0, dy, dx);
-  if (!dgrad_bf16_ok(&tp)) return 0;
-  const pm_conv_params q = dgrad_as_fwd(&tp);
-  const Bf16Plan b = bf16_plan(dy, dx, &q);
-  return b.use ? b.wb_bytes : 0;
-}
-
-// Can this forward call hand the BatchNorm statistics of its output out of its own epilogue? Only the unbatched direct GEMM with one K
-// split and a 16-byte-aligned output takes the staged epilogue; everything else (Winograd route, split-K, the 19-class heads) answers 0.
-static bool bn_partials_route(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p) {
-  if (!x || !y || !p || check_common(x, y, p) != PM_OK) return false;
-  if (pm_is_bf16(y)) {      // bf16 tier: both bf16 kernels carry the statistics in their 8-column staged epilogue (one K split, whole 16-byte groups)
-    if (!pm_vec8(y)) return false;
-    const Bf16Plan b = bf16_plan(x, y, p);
-    return b.use && (b.c16 ? (b.k16.ksplit == 1 && !b.k16.wide) : b.pl.ksplit == 1);
-  }
-  if (pm_is_bf16(x)) return false;
-  if ((y->c & 3) || (y->pitch & 3) || !pm_aligned16(y->ptr)) return false;
-  if (p->prec == 2) {
-    const Bf16Plan b = bf16_plan(x, y, p);
-    if (b.use) return b.pl.ksplit == 1;
-  }
-  if (wino_plan(x, y->c, p).use) return false;
-  if (p->prec != 0) return false;                 // staged-fp32 bf16 form: no statistics instantiation
-  long M, Nn, K;
-  gemm_dims(MODE_FWD, x, y, p, M, Nn, K);
-  const Plan pl = make_plan(MODE_FWD, M, Nn, K, false);
-  return pl.ksplit == 1 && pl.bn >= 64;
-}
-extern "C" size_t pm_conv_bn_partials_bytes(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p) {
-  if (!bn_partials_route(x, y, p)) return 0;
-  return pm_align_up((size_t)pm_cdiv(pm_pixels(y), 32) * y->c * 2 * sizeof(float), 256);
-}
-
-extern "C" size_t pm_conv_workspace(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p0, int which) {
-  const pm_conv_params tp = tier_params(p0, x, y);
-  const pm_conv_params* p = &tp;
-  if (which == MODE_DGRAD && p->stride == 2) {   // four parity classes: compact results + the largest split-K slab set
-    {
-      const S2Native s = s2_native_plan(y, x, p);      // (x = dx, y = dy in this query)
-      if (s.ok) return s.total;
-    }
-    size_t slab = 0, tmp = 0;      // (+ the fp32 copy of a bf16 dy below: on the bf16 tier the stride-2 data gradient still gathers fp32 rows)
-    for (int cls = 0; cls < 4; ++cls) {
-      const S2Class c = s2_class(cls, x, p);
-      tmp = std::max(tmp, (size_t)c.M * x->c * sizeof(float));
-      if (c.M > 0 && c.nky * c.nkx > 0) slab = std::max(slab, make_plan(MODE_DGRAD, c.M, x->c, (long)c.nky * c.nkx * y->c, p->prec != 0).ws_bytes);
-    }
-    return pm_align_up(4 * pm_align_up(tmp, 256) + slab + 256, 256) + upcast_bytes(y);
-  }
-  if (which == MODE_FWD && p->prec == 2) {
-    const Bf16Plan b = bf16_plan(x, y, p);
-    if (b.use) return bf16_ws(b);
-  }
-  if (which == MODE_DGRAD && dgrad_bf16_ok(p)) {
-    const pm_conv_params q = dgrad_as_fwd(p);
-    const Bf16Plan b = bf16_plan(y, x, &q);
-    if (b.use) return bf16_ws(b);
-  }
-  if (which == MODE_FWD || which == MODE_DGRAD) {
-    const WinoPlan wp = which == MODE_FWD ? wino_plan(x, y->c, p) : wino_plan(y, x->c, p);
-    if (wp.use) return wino_ws(wp);
-  }
-  const size_t bias_part = pm_align_up((size_t)pm_cdiv(pm_pixels(y), colsum_rows(pm_pixels(y), y->c)) * y->c * sizeof(float), 256);
-  if (which == MODE_WGRAD && (pm_is_bf16(x) || pm_is_bf16(y))) {      // bf16 tier: split-K slabs + bias partials + the fp32 copies of the mixed-type call sites
-    long M, Nn, K;
-    gemm_dims(which, x, y, p, M, Nn, K);
-    return pm_align_up(make_plan(which, M, Nn, K, true).ws_bytes, 256) + bias_part + upcast_bytes(x) + upcast_bytes(y);
-  }
-  if (which == MODE_WGRAD && p->prec == 2) {
-    const Bf16WgradPlan b = bf16_wgrad_plan(x, y, p);
-    if (b.use) return pm_align_up(bf16_wgrad_ws(b), 256) + bias_part;
-  }
-  if (which == MODE_WGRAD) {
-    const WinoPlan wp = wino_plan(x, y->c, p, true);
-    if (wp.use) return pm_align_up(wino_wgrad_ws(wp, wino_wgrad_plan(wp, y->c)), 256) + bias_part;
-  }
-  long M, Nn, K;
-  gemm_dims(which, x, y, p, M, Nn, K);
-  size_t b = make_plan(which, M, Nn, K, p->prec != 0).ws_bytes;
-  if (which == MODE_WGRAD) b += bias_part;
-  return pm_align_up(b, 256);
-}
-
 extern "C" int pm_conv_fwd(const pm_tensor* x, const float* w, const pm_tensor* y, const pm_conv_params* p0,
                            const pm_conv_epilogue* ep, void* ws, size_t ws_bytes, void* stream) {
   if (int e = check_common(x, y, p0)) return e;
@@ -1186,169 +1337,58 @@ extern "C" int pm_conv_fwd(const pm_tensor* x, const float* w, const pm_tensor* 
   PM_REQUIRE(!ep || ep->struct_size == (int64_t)sizeof(pm_conv_epilogue), PM_EINVAL,
              "conv_fwd: pm_conv_epilogue.struct_size %ld != %zu -- caller built against another pinmem_hip.h (library ABI %d)", ep ? (long)ep->struct_size : 0l,
              sizeof(pm_conv_epilogue), PM_ABI_VERSION);
-  if (ep && ep->bn_partials) {
-    PM_REQUIRE(!ep->relu && !ep->residual, PM_EINVAL, "conv_fwd: bn_partials are the statistics of the convolution output (no residual / ReLU)");
-    const size_t need = pm_conv_bn_partials_bytes(x, y, p);
-    PM_REQUIRE(need != 0 && (size_t)ep->bn_partials_bytes >= need, PM_EINVAL, "conv_fwd: this call cannot emit bn_partials (ask pm_conv_bn_partials_bytes): %zu needed", need);
-  }
   PM_REQUIRE(w && pm_aligned16(w), PM_EINVAL, "conv_fwd: weight null or unaligned");
-  {
-    pm_conv_epilogue e1 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (ep) e1 = *ep;
-    PM_REQUIRE((e1.scale == nullptr) == (e1.shift == nullptr), PM_EINVAL, "conv_fwd: scale and shift go together");
-    const WinoPlan wp = wino_plan(x, y->c, p);
-    if (wp.use) {
-      PM_REQUIRE(ws && ws_bytes >= wino_ws(wp), PM_EWORKSPACE, "conv_fwd(winograd): workspace %zu < %zu", ws_bytes, wino_ws(wp));
-      float* keep = (p->wino_v && (size_t)p->wino_v_bytes >= wp.v_bytes) ? (float*)p->wino_v : nullptr;
-      float* uext = (p->wxf && (size_t)p->wxf_bytes >= wp.u_bytes) ? (float*)p->wxf : nullptr;
-      return wino_conv(x, w, y->c, x->c, false, y, wp, e1, ws, (hipStream_t)stream, keep, uext, p->wxf_valid != 0);
-    }
-  }
-  if (p->prec == 2) {
-    const Bf16Plan b = bf16_plan(x, y, p);
-    if (b.use) {
-      pm_conv_epilogue e2 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, nullptr, 0, 0};
-      if (ep) e2 = *ep;
-      PM_REQUIRE((e2.scale == nullptr) == (e2.shift == nullptr), PM_EINVAL, "conv_fwd: scale and shift go together");
-      PM_REQUIRE(ws && ws_bytes >= bf16_ws(b), PM_EWORKSPACE, "conv_fwd(bf16): workspace %zu < %zu", ws_bytes, bf16_ws(b));
-      char* wext = (p->wxf && (size_t)p->wxf_bytes >= b.wb_bytes) ? (char*)p->wxf : nullptr;
-      return conv_bf16(x, w, y->c, x->c, false, y, p, b, e2, ws, (hipStream_t)stream, wext, p->wxf_valid != 0);
-    }
-  }
-  // what is left gathers fp32 rows: fp32 convolutions, and on the bf16 tier the 4-channel stem (fp32 image in, bf16 out)
-  PM_REQUIRE(pm_is_f32(x), PM_EUNSUPPORTED, "conv_fwd: a bf16 input needs at least 32 channels (got %d)", x->c);
-  long M, Nn, K;
-  gemm_dims(MODE_FWD, x, y, p, M, Nn, K);
-  Plan pl = make_plan(MODE_FWD, M, Nn, K, p->prec != 0);
-  PM_REQUIRE(pl.ws_bytes <= ws_bytes && (pl.ws_bytes == 0 || ws), PM_EWORKSPACE, "conv_fwd: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
-  ConvK k;
-  fill_geom(k, x, y, p);
-  k.io16 = pm_is_bf16(y) ? 1 : 0;
-  k.A = (const float*)x->ptr, k.B = w;
-  k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
-  k.a_bytes = (unsigned)(pm_pixels(x) * x->pitch * 4), k.b_bytes = (unsigned)((long)y->c * K * 4), k.kmode = x->c % BK == 0 ? 0 : (x->c >= BK ? 1 : 2);
   pm_conv_epilogue e0 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, nullptr, 0, 0};
   if (ep) e0 = *ep;
   PM_REQUIRE((e0.scale == nullptr) == (e0.shift == nullptr), PM_EINVAL, "conv_fwd: scale and shift go together");
-  hipStream_t st = (hipStream_t)stream;
-  if (pl.ksplit > 1) {
-    k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
-    if (int e = launch<MODE_FWD>(k, pl, st)) return e;
-    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)y->ptr, (long)y->pitch, e0.bias, e0.scale, e0.shift, e0.residual,
-                         (long)e0.residual_pitch, e0.relu, st, k.io16 != 0);
+  const ConvRoute r = route_conv(MODE_FWD, x, y, p);
+  if (e0.bn_partials) {
+    PM_REQUIRE(!e0.relu && !e0.residual, PM_EINVAL, "conv_fwd: bn_partials are the statistics of the convolution output (no residual / ReLU)");
+    PM_REQUIRE(r.bn_bytes != 0 && (size_t)e0.bn_partials_bytes >= r.bn_bytes, PM_EINVAL, "conv_fwd: this call cannot emit bn_partials (ask pm_conv_bn_partials_bytes): %zu needed", r.bn_bytes);
   }
-  k.C = (float*)y->ptr, k.c_pitch = y->pitch, k.c_split = 0;
-  k.bias = e0.bias, k.scale = e0.scale, k.shift = e0.shift, k.residual = e0.residual, k.res_pitch = e0.residual_pitch, k.relu = e0.relu;
-  k.stats = e0.bn_partials;
-  return launch<MODE_FWD>(k, pl, st);
+  PM_REQUIRE(ws_bytes >= r.ws_bytes && (ws || r.ws_bytes == 0), PM_EWORKSPACE, "conv_fwd: workspace %zu < %zu", ws_bytes, r.ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  switch (r.kind) {
+    case R_WINO: {
+      float* keep = (p->wino_v && (size_t)p->wino_v_bytes >= r.wino.v_bytes) ? (float*)p->wino_v : nullptr;
+      float* uext = (p->wxf && (size_t)p->wxf_bytes >= r.wino.u_bytes) ? (float*)p->wxf : nullptr;
+      return wino_conv(x, w, y->c, x->c, false, y, r.wino, e0, ws, st, keep, uext, p->wxf_valid != 0);
+    }
+    case R_BF16: {
+      char* wext = (p->wxf && (size_t)p->wxf_bytes >= r.b16.wb_bytes) ? (char*)p->wxf : nullptr;
+      return conv_bf16(x, w, y->c, x->c, false, y, &r.pe, r.b16, e0, ws, st, wext, p->wxf_valid != 0);
+    }
+    default:
+      PM_REQUIRE(pm_is_f32(x), PM_EUNSUPPORTED, "conv_fwd: a bf16 input needs at least 32 channels (got %d)", x->c);
+      return conv_direct<MODE_FWD>(x, y, w, p, r.pl, e0, ws, st);
+  }
 }
 
-extern "C" int pm_conv_bwd_data(const pm_tensor* dy0, const float* w, const pm_tensor* dx, const pm_conv_params* p0, const pm_tensor* add,
+extern "C" int pm_conv_bwd_data(const pm_tensor* dy, const float* w, const pm_tensor* dx, const pm_conv_params* p0, const pm_tensor* add,
                                 void* ws, size_t ws_bytes, void* stream) {
-  if (int e = check_common(dx, dy0, p0)) return e;
-  const pm_conv_params tp = tier_params(p0, dy0, dx);
+  if (int e = check_common(dx, dy, p0)) return e;
+  const pm_conv_params tp = tier_params(p0, dy, dx);
   const pm_conv_params* p = &tp;
-  const pm_tensor* dy = dy0;
-  pm_tensor dy32;
   PM_REQUIRE(!add || (add->ptr && pm_same_shape(add, dx) && add->dtype == dx->dtype), PM_EINVAL, "conv_bwd_data: `add` must match dx (shape and dtype)");
   PM_REQUIRE(!add || !pm_is_bf16(add) || pm_vec8(add), PM_EINVAL, "conv_bwd_data: bf16 `add` must be 16B aligned with pitch %% 8 == 0");
-  const float* addp = add ? (const float*)add->ptr : nullptr;
-  const long add_pitch = add ? add->pitch : 0;
   PM_REQUIRE(w && pm_aligned16(w), PM_EINVAL, "conv_bwd_data: weight null or unaligned");
-  hipStream_t st0 = (hipStream_t)stream;
-  if (p->stride == 2) {
-    // Only taps with (iy + pad - ky*dil) even reach an output pixel: split the input pixels into their four parity classes,
-    // run a dense dgrad over each class with its matching tap subset (1/4 of the MFMA work of the masked formulation),
-    // then interleave the compact results into dx.
-    const size_t need = pm_conv_workspace(dx, dy, p, MODE_DGRAD);
-    PM_REQUIRE(ws && ws_bytes >= need, PM_EWORKSPACE, "conv_bwd_data(stride 2): workspace %zu < %zu", ws_bytes, need);
-    PM_REQUIRE(dx->c % 4 == 0, PM_EUNSUPPORTED, "conv_bwd_data(stride 2): Cin %% 4 != 0");
-    {
-      S2Native s = s2_native_plan(dy, dx, p);
-      if (s.ok) return dgrad_s2_bf16(dy, w, dx, p, add, s, ws, st0);
-    }
-    if (pm_is_bf16(dy)) {      // bf16 tier, shapes the native form does not take: the parity-class gather reads fp32 rows -- dy (a quarter of dx's pixels) is widened once, at the end of the workspace
-      if (int e = upcast(dy0, (char*)ws + need - upcast_bytes(dy0), &dy32, st0)) return e;
-      dy = &dy32;
-    }
-    size_t tmp_bytes = 0;
-    for (int cls = 0; cls < 4; ++cls) tmp_bytes = std::max(tmp_bytes, (size_t)s2_class(cls, dx, p).M * dx->c * sizeof(float));
-    tmp_bytes = pm_align_up(tmp_bytes, 256);
-    float* tmp = (float*)ws;
-    float* slab = (float*)((char*)ws + 4 * tmp_bytes);
-    unsigned char valid[4];
-    for (int cls = 0; cls < 4; ++cls) {
-      const S2Class c = s2_class(cls, dx, p);
-      valid[cls] = c.M > 0 && c.nky * c.nkx > 0;
-      if (!valid[cls]) continue;
-      const long Kc = (long)c.nky * c.nkx * dy->c;
-      const Plan pl = make_plan(MODE_DGRAD, c.M, dx->c, Kc, p->prec != 0);
-      ConvK k;
-      fill_geom(k, dx, dy, p);
-      k.A = (const float*)dy->ptr, k.B = w;
-      k.M = (int)c.M, k.Nn = dx->c, k.K = (int)Kc;
-      k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * 4), k.b_bytes = (unsigned)((long)dy->c * p->kh * p->kw * dx->c * 4);
-      k.kmode = dy->c >= BK ? K_MID : K_SMALL;
-      k.T_eff = c.nky * c.nkx, k.tk_w = c.nkx, k.ky0 = c.ky0, k.kx0 = c.kx0, k.ksy = c.ksy, k.ksx = c.ksx;
-      k.sub = 1, k.sub_cy = c.cy, k.sub_cx = c.cx, k.Hc = c.Hc, k.Wc = c.Wc;
-      float* out = (float*)((char*)tmp + cls * tmp_bytes);
-      if (pl.ksplit > 1) {
-        k.C = slab, k.c_pitch = dx->c, k.c_split = c.M * dx->c;
-        if (int e = launch<MODE_DGRAD>(k, pl, st0)) return e;
-        if (int e = splitk_reduce(slab, pl.ksplit, c.M, dx->c, out, (long)dx->c, nullptr, nullptr, nullptr, nullptr, 0l, 0, st0)) return e;
-      } else {
-        k.C = out, k.c_pitch = dx->c, k.c_split = 0;
-        if (int e = launch<MODE_DGRAD>(k, pl, st0)) return e;
-      }
-    }
-    const int valid_mask = valid[0] | (valid[1] << 1) | (valid[2] << 2) | (valid[3] << 3);
-    const long total = pm_pixels(dx) * (dx->c / 4);
-    if (pm_is_bf16(dx))
-      hipLaunchKernelGGL(dgrad_s2_interleave_kernel<true>, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st0, (const float*)tmp,
-                         (long)(tmp_bytes / sizeof(float)), valid_mask, (float*)dx->ptr, (long)dx->pitch, dx->n, dx->h, dx->w, dx->c, addp, add_pitch);
-    else
-      hipLaunchKernelGGL(dgrad_s2_interleave_kernel<false>, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st0, (const float*)tmp,
-                         (long)(tmp_bytes / sizeof(float)), valid_mask, (float*)dx->ptr, (long)dx->pitch, dx->n, dx->h, dx->w, dx->c, addp, add_pitch);
-    return pm_check_launch("dgrad_s2_interleave");
-  }
-  if (dgrad_bf16_ok(p)) {      // data gradient of a stride-1 convolution = forward convolution of dy with the rotated / transposed filter
-    const pm_conv_params q = dgrad_as_fwd(p);
-    const Bf16Plan b = bf16_plan(dy, dx, &q);
-    if (b.use) {
-      PM_REQUIRE(ws && ws_bytes >= bf16_ws(b), PM_EWORKSPACE, "conv_bwd_data(bf16): workspace %zu < %zu", ws_bytes, bf16_ws(b));
-      const pm_conv_epilogue e1 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, addp, add_pitch, 0};
-      char* wext = (p->wxf && (size_t)p->wxf_bytes >= b.wb_bytes) ? (char*)p->wxf : nullptr;      // the rotated bf16 filter kept by the caller (pm_conv_wxf_bytes_dgrad)
-      return conv_bf16(dy, w, dy->c, dx->c, true, dx, &q, b, e1, ws, st0, wext, p->wxf_valid != 0);
-    }
-  }
-  {
-    const WinoPlan wp = wino_plan(dy, dx->c, p);
-    if (wp.use) {
-      PM_REQUIRE(ws && ws_bytes >= wino_ws(wp), PM_EWORKSPACE, "conv_bwd_data(winograd): workspace %zu < %zu", ws_bytes, wino_ws(wp));
-      const pm_conv_epilogue e1 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, addp, add_pitch, 0};
-      return wino_conv(dy, w, dy->c, dx->c, true, dx, wp, e1, ws, st0);
-    }
-  }
-  PM_REQUIRE(pm_is_f32(dy), PM_EUNSUPPORTED, "conv_bwd_data: a bf16 dy needs at least 32 channels and a stride-1 geometry the forward form covers");
-  long M, Nn, K;
-  gemm_dims(MODE_DGRAD, dx, dy, p, M, Nn, K);
-  Plan pl = make_plan(MODE_DGRAD, M, Nn, K, p->prec != 0);
-  PM_REQUIRE(pl.ws_bytes <= ws_bytes && (pl.ws_bytes == 0 || ws), PM_EWORKSPACE, "conv_bwd_data: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
-  ConvK k;
-  fill_geom(k, dx, dy, p);
-  k.io16 = pm_is_bf16(dx) ? 1 : 0;
-  k.A = (const float*)dy->ptr, k.B = w;
-  k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
-  k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * 4), k.b_bytes = (unsigned)((long)dy->c * p->kh * p->kw * dx->c * 4), k.kmode = (dy->c % BK == 0 && p->stride == 1) ? 0 : (dy->c >= BK ? 1 : 2);
+  const ConvRoute r = route_conv(MODE_DGRAD, dx, dy, p);
+  PM_REQUIRE(ws_bytes >= r.ws_bytes && (ws || r.ws_bytes == 0), PM_EWORKSPACE, "conv_bwd_data: workspace %zu < %zu", ws_bytes, r.ws_bytes);
   hipStream_t st = (hipStream_t)stream;
-  if (pl.ksplit > 1) {
-    k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
-    if (int e = launch<MODE_DGRAD>(k, pl, st)) return e;
-    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)dx->ptr, (long)dx->pitch, nullptr, nullptr, nullptr, addp, add_pitch, 0, st, k.io16 != 0);
+  // the fused skip gradient rides as the residual of the forward-form workers
+  const pm_conv_epilogue e1 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, add ? (const float*)add->ptr : nullptr, add ? add->pitch : 0, 0};
+  switch (r.kind) {
+    case R_S2_NATIVE: return dgrad_s2_bf16(dy, w, dx, p, add, r.s2n, ws, st);
+    case R_S2_PARITY: return dgrad_s2_parity(dy, w, dx, p, add, r, ws, st);
+    case R_BF16: {
+      char* wext = (p->wxf && (size_t)p->wxf_bytes >= r.b16.wb_bytes) ? (char*)p->wxf : nullptr;      // the rotated bf16 filter kept by the caller (pm_conv_wxf_bytes_dgrad)
+      return conv_bf16(dy, w, dy->c, dx->c, true, dx, &r.pe, r.b16, e1, ws, st, wext, p->wxf_valid != 0);
+    }
+    case R_WINO: return wino_conv(dy, w, dy->c, dx->c, true, dx, r.wino, e1, ws, st);
+    default:
+      PM_REQUIRE(pm_is_f32(dy), PM_EUNSUPPORTED, "conv_bwd_data: a bf16 dy needs at least 32 channels and a stride-1 geometry the forward form covers");
+      return conv_direct<MODE_DGRAD>(dx, dy, w, p, r.pl, e1, ws, st);
   }
-  k.C = (float*)dx->ptr, k.c_pitch = dx->pitch, k.c_split = 0;
-  k.residual = addp, k.res_pitch = add_pitch;
-  return launch<MODE_DGRAD>(k, pl, st);
 }
 
 extern "C" int pm_conv_bwd_weight(const pm_tensor* x0, const pm_tensor* dy0, float* dw, float* dbias, const pm_conv_params* p0, void* ws,
@@ -1357,124 +1397,34 @@ extern "C" int pm_conv_bwd_weight(const pm_tensor* x0, const pm_tensor* dy0, flo
   const pm_conv_params tp = tier_params(p0, x0, dy0);
   const pm_conv_params* p = &tp;
   PM_REQUIRE(dw && pm_aligned16(dw), PM_EINVAL, "conv_bwd_weight: dw null or unaligned");
+  const ConvRoute r = route_conv(MODE_WGRAD, x0, dy0, p);
+  PM_REQUIRE(ws && ws_bytes >= r.ws_bytes, PM_EWORKSPACE, "conv_bwd_weight: workspace %zu < %zu", ws_bytes, r.ws_bytes);
   hipStream_t st = (hipStream_t)stream;
-  const size_t need = pm_conv_workspace(x0, dy0, p, MODE_WGRAD);
-  PM_REQUIRE(need <= ws_bytes && ws, PM_EWORKSPACE, "conv_bwd_weight: workspace %zu < %zu", ws_bytes, need);
   const pm_tensor *x = x0, *dy = dy0;
   pm_tensor x32, dy32;
-  // bf16 tier. Both operands bf16: the gather moves 16 bytes = eight channels per lane straight into the bf16 LDS tiles of the transpose-read form (PREC 4).
-  // Mixed types (fp32 image x bf16 dy: the stem; bf16 x x fp32 dy: the 19-class heads) and a bias gradient over a bf16 dy: the bf16 side is widened to a
-  // dense fp32 copy at the end of the workspace and the call proceeds as the fp32-gather form (PREC 3) -- small tensors, once per step.
-  const bool tier = pm_is_bf16(x0) || pm_is_bf16(dy0);
-  const bool native16 = pm_is_bf16(x0) && pm_is_bf16(dy0) && dy0->c >= 32;
-  if (tier) {
-    char* tail = (char*)ws + need;
-    if (!native16 && pm_is_bf16(x0)) {
-      tail -= upcast_bytes(x0);
-      if (int e = upcast(x0, tail, &x32, st)) return e;
-      x = &x32;
-    }
-    if (pm_is_bf16(dy0) && (!native16 || dbias)) {
-      tail -= upcast_bytes(dy0);
-      if (int e = upcast(dy0, tail, &dy32, st)) return e;
-      if (!native16) dy = &dy32;
-    }
+  if (!r.native16 && pm_is_bf16(x0)) {
+    if (int e = upcast(x0, (char*)ws + r.x32_off, &x32, st)) return e;
+    x = &x32;
   }
-  long M, Nn, K;
-  gemm_dims(MODE_WGRAD, x, dy, p, M, Nn, K);
-  Plan pl = make_plan(MODE_WGRAD, M, Nn, K, p->prec != 0);
-  const Bf16WgradPlan bw = tier ? Bf16WgradPlan{} : bf16_wgrad_plan(x, dy, p);
-  if (bw.use) {
-    if (int e = conv_wgrad_bf16(x, dy, dw, p, bw, ws, st)) return e;
-    pl.ws_bytes = bf16_wgrad_ws(bw);       // the bias partials follow the bf16 buffers
+  if (pm_is_bf16(dy0) && (!r.native16 || dbias)) {      // (a native bf16 gather still sums the bias gradient over fp32 rows)
+    if (int e = upcast(dy0, (char*)ws + r.dy32_off, &dy32, st)) return e;
+    if (!r.native16) dy = &dy32;
   }
-  const WinoPlan wp = wino_plan(x, dy->c, p, true);
-  if (wp.use) {
-    const WinoWgradPlan q = wino_wgrad_plan(wp, dy->c);
-    float* kept = (p->wino_v && (size_t)p->wino_v_bytes >= wp.v_bytes) ? (float*)p->wino_v : nullptr;
-    if (int e = wino_wgrad(x, dy, dw, wp, q, ws, st, kept)) return e;
-    pl.ws_bytes = wino_wgrad_ws(wp, q);     // the bias partials follow the Winograd buffers
+  int e;
+  switch (r.kind) {
+    case R_BF16_WGRAD: e = conv_wgrad_bf16(x, dy, dw, p, r.b16w, ws, st); break;
+    case R_WINO_WGRAD: e = wino_wgrad(x, dy, dw, r.wino, r.wino_w, ws, st, (p->wino_v && (size_t)p->wino_v_bytes >= r.wino.v_bytes) ? (float*)p->wino_v : nullptr); break;
+    default: e = conv_wgrad_direct(x, dy, dw, p, r, ws, st);
   }
-  ConvK k;
-  fill_geom(k, x, dy, p);
-  // configs[2]: the weight gradient gathers the fp32 rows as before, rounds them to bf16 on the way into LDS and reads its fragments through the
-  // transpose read (PREC 3): no transposed / per-tap copies of x in HBM.
-  if (p->prec == 2) k.prec = 3;
-  if (native16) {
-    PM_REQUIRE(x->c % 8 == 0 && dy->c % 8 == 0 && pl.bn >= 64, PM_EUNSUPPORTED, "conv_bwd_weight(bf16): channels %% 8 != 0 or a tile narrower than 64");
-    k.prec = 4;
-    // the PREC 4 kernel steps 64 pixels at a time: the K range of a split must be a multiple of that (the slab count can only shrink, the workspace was sized for more)
-    pl.kper = (pl.kper + 63) / 64 * 64;
-    pl.ksplit = (int)((K + pl.kper - 1) / pl.kper);
-  }
-  const int esz = native16 ? 2 : 4;
-  k.A = (const float*)dy->ptr, k.B = (const float*)x->ptr;
-  k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
-  k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * esz), k.b_bytes = (unsigned)(pm_pixels(x) * x->pitch * esz), k.kmode = dy->w >= (native16 ? 2 * BK : BK) ? 1 : 2;
-  // round 5, second session: both operands bf16 and Cin a multiple of the 128-channel block -> the LDS-DMA persistent ring of wgrad16.hip. Its units are
-  // (256 x 128 tile, pixel range): the split is re-planned for one block per CU within the slab count the workspace was sized for.
-  pm_wgrad16 w16{};
-  bool use16 = false;
-  if (native16 && !wp.use && !bw.use) {
-    w16.X = (const pm_bf16*)x->ptr, w16.DY = (const pm_bf16*)dy->ptr;
-    w16.N = x->n, w16.H = x->h, w16.W = x->w, w16.Ho = dy->h, w16.Wo = dy->w;
-    w16.x_pitch = x->pitch, w16.dy_pitch = dy->pitch, w16.Cin = x->c, w16.Cout = dy->c;
-    w16.kh = p->kh, w16.kw = p->kw, w16.stride = p->stride, w16.pad = p->pad, w16.dil = p->dil;
-    w16.M = (int)M, w16.Nn = (int)Nn, w16.P = (int)K, w16.kper = 64, w16.c_split = M * Nn;
-    w16.C = dw;
-    use16 = K < (1l << 30) && pm_wgrad16_plan(&w16);
-    if (use16) {
-      const long tiles = (long)w16.tiles_m * w16.tiles_n, steps = (K + 63) / 64;
-      int best_ks = 1;
-      double best = 1e30;
-      for (int ks = 1; ks <= pl.ksplit; ++ks) {
-        const long per = (steps + ks - 1) / ks, kse = (steps + per - 1) / per;
-        const long rounds = (tiles * kse + 255) / 256;
-        // a unit costs its K-steps + ~6 steps of epilogue / hand-over; slabs: written and read back by the reduce (bytes / ~4 TB/s in K-steps of ~1 us)
-        const double cost = (double)rounds * (per + 6) + (kse > 1 ? (double)kse * M * Nn * 8.0 / 4e12 / 1.0e-6 : 0.0);
-        if (cost < best) best = cost, best_ks = (int)kse;
-      }
-      const long per = (steps + best_ks - 1) / best_ks;
-      w16.kper = (int)per * 64, w16.ksplit = (int)((steps + per - 1) / per);
-    }
-  }
-  if (use16) {
-    ProfRec rec{};
-    if (g_prof_on) {
-      (void)hipEventCreate(&rec.a), (void)hipEventCreate(&rec.b);
-      rec.mode = MODE_WGRAD, rec.bm = w16.bm, rec.bn = w16.bn, rec.km = 2, rec.prec = 4, rec.nst = 3, rec.M = (int)M, rec.Nn = (int)Nn, rec.K = (int)K, rec.batch = 1, rec.ksplit = w16.ksplit,
-      rec.flops = 2.0 * (double)M * (double)Nn * (double)K;
-      (void)hipEventRecord(rec.a, st);
-    }
-    if (w16.ksplit > 1) w16.C = (float*)ws;
-    const int e = pm_wgrad16_launch(&w16, st);
-    if (g_prof_on) {
-      (void)hipEventRecord(rec.b, st);
-      g_prof.push_back(rec);
-    }
-    if (e) return e;
-    if (w16.ksplit > 1)
-      if (int e2 = splitk_reduce((const float*)ws, w16.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st)) return e2;
-  } else if (wp.use || bw.use) {
-  } else if (pl.ksplit > 1) {
-    k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
-    if (int e = launch<MODE_WGRAD>(k, pl, st)) return e;
-    if (int e = splitk_reduce((const float*)ws, pl.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st)) return e;
-  } else {
-    k.C = dw, k.c_pitch = Nn, k.c_split = 0;
-    if (int e = launch<MODE_WGRAD>(k, pl, st)) return e;
-  }
-  if (dbias) {
-    const pm_tensor* dyb = pm_is_bf16(dy0) ? &dy32 : dy0;      // the bias gradient sums fp32 rows
-    const long P = pm_pixels(dyb);
-    const int rpb = colsum_rows(P, dyb->c), nb = pm_cdiv(P, rpb);
-    float* part = (float*)((char*)ws + pm_align_up(pl.ws_bytes, 256));
-    if (dyb->pitch == ((dyb->c + 3) & ~3) && dyb->pitch <= 64 && pm_aligned16(dyb->ptr))   // the tensor's own (pad-to-4) rows, not a channel slice
-      hipLaunchKernelGGL(colsum_partial_narrow_kernel, dim3(nb), dim3(256), 0, st, (const float*)dyb->ptr, (int)(dyb->pitch / 4), P, dyb->c, rpb, part);
-    else
-      hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb, pm_cdiv(dyb->c, 64)), dim3(256), 0, st, (const float*)dyb->ptr, (long)dyb->pitch, P, dyb->c, rpb, part);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(pm_cdiv(dyb->c, 64)), dim3(1024), 0, st, (const float*)part, nb, dyb->c, dbias);
-    return pm_check_launch("conv_bias_grad");
-  }
-  return PM_OK;
+  if (e || !dbias) return e;
+  const pm_tensor* dyb = pm_is_bf16(dy0) ? &dy32 : dy0;      // the bias gradient sums fp32 rows
+  const long P = pm_pixels(dyb);
+  const int rpb = colsum_rows(P, dyb->c), nb = pm_cdiv(P, rpb);
+  float* part = (float*)((char*)ws + r.bias_off);
+  if (dyb->pitch == ((dyb->c + 3) & ~3) && dyb->pitch <= 64 && pm_aligned16(dyb->ptr))   // the tensor's own (pad-to-4) rows, not a channel slice
+    hipLaunchKernelGGL(colsum_partial_narrow_kernel, dim3(nb), dim3(256), 0, st, (const float*)dyb->ptr, (int)(dyb->pitch / 4), P, dyb->c, rpb, part);
+  else
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb, pm_cdiv(dyb->c, 64)), dim3(256), 0, st, (const float*)dyb->ptr, (long)dyb->pitch, P, dyb->c, rpb, part);
+  hipLaunchKernelGGL(colsum_final_kernel, dim3(pm_cdiv(dyb->c, 64)), dim3(1024), 0, st, (const float*)part, nb, dyb->c, dbias);
+  return pm_check_launch("conv_bias_grad");
 }

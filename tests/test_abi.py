@@ -108,3 +108,74 @@ print(r.conv16_wide, r.conv16_persistent)
     out = subprocess.run([sys.executable, '-c', code, L.LIB_PATH], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     assert out.stdout.split() == ['1', '1']
+
+
+def _size_table():
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('record_conv_sizes', os.path.join(ROOT, 'tools', 'record_conv_sizes.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(tool.FIXTURE) as f:
+        return tool, json.load(f)
+
+
+def test_conv_size_queries_answer_what_the_recorded_table_holds():
+    """tests/golden/conv_size_queries.json: the seven size queries of every convolution call signature of the networks (one training step of DeepV3Plus-R50 at 2 x 128^2 and
+    8 x 768^2 on both tiers, one DeepV2 eval tile) and of a hand-written edge list, under the default routing and every single-field departure from it, recorded from the
+    library BEFORE the queries became field reads of route_conv (tools/record_conv_sizes.py against the parent commit's build). Every row is held exactly: pure host code,
+    fake aligned pointers, no GPU."""
+    import ctypes
+    from ctypes import byref
+    tool, table = _size_table()
+    lib = L.load()
+    before = L.PmRouting(ctypes.sizeof(L.PmRouting))
+    assert lib.pm_routing_get(byref(before)) == 0
+    assert 1000 <= len(table['rows']) <= 5000 and {r[1] for r in table['rows']} == {n for n, _, _ in tool.ROUTINGS}
+    try:
+        for name, fields, _ in tool.ROUTINGS:
+            with tool.routing(lib, L, fields):
+                for s, rname, want in table['rows']:
+                    if rname == name:
+                        assert tool.query(lib, L, s) == want, (s, name)
+        # the recorder itself, run against this build, writes the committed file byte for byte
+        sigs = table['network_signatures'] + [s for s in tool.edge_signatures() if s not in table['network_signatures']]
+        with open(tool.FIXTURE) as f:
+            assert tool.dumps(table['network_signatures'], tool.edge_signatures(), tool.rows(lib, L, sigs)) == f.read()
+    finally:
+        assert lib.pm_routing_set(byref(before)) == 0
+
+
+def test_conv_entry_points_require_exactly_the_queried_workspace():
+    """A query and the call it sizes share one plan: with one byte less than pm_conv_workspace answered, every entry point refuses the call before any launch
+    (PM_EWORKSPACE; there is no device here, so the calls are made with need - 1 only). Every recorded row with a workspace, fake aligned pointers."""
+    import ctypes
+    from ctypes import byref
+    tool, table = _size_table()
+    lib = L.load()
+    before = L.PmRouting(ctypes.sizeof(L.PmRouting))
+    assert lib.pm_routing_get(byref(before)) == 0
+    W, DW, WS = 0x8000000, 0x9000000, 0xC000000
+    calls = 0
+    try:
+        for name, fields, _ in tool.ROUTINGS:
+            with tool.routing(lib, L, fields):
+                for s, rname, want in table['rows']:
+                    if rname != name:
+                        continue
+                    x, y = L.PmTensor(tool.X_PTR, *s[0:7]), L.PmTensor(tool.Y_PTR, *s[7:14])
+                    p = L.conv_params(s[14], s[14], s[15], s[16], s[17], s[18])
+                    for which, need in enumerate(want[:3]):
+                        if need == 0:
+                            continue
+                        if which == 0:
+                            rc = lib.pm_conv_fwd(byref(x), W, byref(y), byref(p), None, WS, need - 1, None)
+                        elif which == 1:
+                            rc = lib.pm_conv_bwd_data(byref(y), W, byref(x), byref(p), None, WS, need - 1, None)
+                        else:
+                            rc = lib.pm_conv_bwd_weight(byref(x), byref(y), DW, None, byref(p), WS, need - 1, None)
+                        calls += 1
+                        assert rc == -2 and b'workspace' in lib.pm_last_error(), (s, name, which, need, rc, lib.pm_last_error())      # PM_EWORKSPACE
+    finally:
+        assert lib.pm_routing_set(byref(before)) == 0
+    assert calls >= 2000

@@ -1459,3 +1459,137 @@ def test_upsample_ce_rows_too_wide_for_lds_take_the_composed_route(K):
     ref = F.cross_entropy(F.interpolate(lg, size=HW, mode='bilinear', align_corners=True), lab, ignore_index=255)
     assert abs(loss.item() - ref.item()) < 1e-5 * max(1, abs(ref.item()))
     assert rel(lgg.grad.cpu(), lr.grad) < 1e-4
+
+
+# ---- one case per route of conv_igemm.hip route_conv, at the smallest shape that still takes it ------------------------------------------------------------------
+# which (0 forward / 1 data gradient / 2 weight gradient), tier, (n, cin, h, w, cout, k, stride, pad, dil), routing fields, options, profiler record that proves the kernel
+# (mode, prec): mode 0 / 1 / 2 the implicit-GEMM template (the Winograd point products run as mode 0), 4 the LDS-DMA bf16 kernel; prec 4 with km 2 / nst 3 the wgrad16 ring
+ROUTE_CASES = {
+    'fwd-winograd-f4':        (0, 'f32', (1, 128, 16, 16, 128, 3, 1, 1, 1), {}, {'wxf_points': 36}, (0, None)),
+    'fwd-winograd-f2-dilated': (0, 'f32', (1, 128, 12, 12, 128, 3, 1, 6, 6), {}, {'wxf_points': 16}, (0, None)),
+    'fwd-bf16-reg-staged':    (0, 'bf16', (1, 64, 8, 8, 64, 3, 1, 1, 1), {}, {}, (0, 2)),
+    'fwd-bf16-lds-dma':       (0, 'bf16', (1, 64, 16, 16, 64, 3, 1, 1, 1), {}, {}, (4, 5)),
+    'fwd-bf16-48ch-padded':   (0, 'bf16', (1, 48, 16, 16, 64, 3, 1, 1, 1), {}, {'padded_copy': True}, (4, 5)),
+    'fwd-direct-splitk':      (0, 'f32', (1, 2048, 4, 4, 256, 3, 1, 1, 1), {'winograd': 0}, {'slabs': True}, (0, 5)),
+    'dgrad-winograd':         (1, 'f32', (1, 128, 16, 16, 128, 3, 1, 1, 1), {}, {}, (0, None)),
+    'dgrad-s2-parity-f32':    (1, 'f32', (1, 8, 9, 9, 8, 3, 2, 1, 1), {}, {}, (1, 0)),
+    'dgrad-s2-native-bf16':   (1, 'bf16', (1, 64, 10, 10, 64, 3, 2, 1, 1), {}, {}, (4, 5)),
+    'dgrad-s2-bf16-dy32':     (1, 'bf16', (1, 64, 10, 10, 32, 3, 2, 1, 1), {}, {'upcast_dy': True}, (1, 1)),
+    'wgrad-winograd-kept-v':  (2, 'f32', (1, 256, 16, 16, 256, 3, 1, 1, 1), {}, {'keep_v': True}, (2, None)),
+    'wgrad-winograd':         (2, 'f32', (1, 256, 16, 16, 256, 3, 1, 1, 1), {}, {'v_bytes': True}, (2, None)),
+    'wgrad-direct-splitk-dbias': (2, 'f32', (2, 64, 24, 20, 64, 3, 1, 1, 1), {}, {'dbias': True, 'slabs': True}, (2, None)),
+    'wgrad-mixed-stem-dbias': (2, 'stem', (2, 4, 40, 36, 64, 7, 2, 3, 1), {}, {'dbias': True, 'upcast_dy': True}, (2, 3)),
+    # (the ring wants Cout >= 128: 128 -> 64 stays on the register-staged bf16 gather, 128 -> 128 is the smallest shape on the ring)
+    'wgrad-bf16-native-dbias': (2, 'bf16', (1, 128, 16, 16, 64, 3, 1, 1, 1), {}, {'dbias': True, 'upcast_dy': True}, (2, 4)),
+    'wgrad-bf16-ring-dbias':  (2, 'bf16', (1, 128, 16, 16, 128, 3, 1, 1, 1), {}, {'dbias': True, 'upcast_dy': True, 'ring': True}, (2, 4)),
+    'wgrad-bf16-ring-off':    (2, 'bf16', (1, 128, 16, 16, 128, 3, 1, 1, 1), {'wgrad16': 0}, {'dbias': True, 'upcast_dy': True, 'ring': False}, (2, 4)),
+    'wgrad-bf16-transposed':  (2, 'bf16_operands', (1, 64, 16, 16, 64, 3, 1, 1, 1), {'bf16_wgrad': 1}, {'transposed': True}, (0, 2)),
+}
+
+
+@pytest.mark.parametrize('name', list(ROUTE_CASES))
+def test_conv_routes_stay_inside_the_workspace_they_ask_for(K, name):
+    """Every route of route_conv through the C ABI with EXACTLY the workspace pm_conv_workspace answers: the allocation carries 4096 guard bytes behind it that must
+    come back untouched, the size queries and the profiler's record confirm the route, and the result meets the comparator and tolerance of the route's own test above
+    (fp32: fp64 convolution, 2e-5 / 5e-5 for dw; bf16 tensors: one-and-a-half bf16 roundings of the fp32 formula on the rounded operands; dw of the bf16 forms 2e-4)."""
+    import ctypes
+    from ctypes import byref
+    from pinthememory_amd.hip import lib as L
+    which, tier, (n, cin, h, w, cout, k, s, p, d), route, opt, (rec_mode, rec_prec) = ROUTE_CASES[name]
+    lib = L.load()
+    r16 = (lambda t: t) if tier == 'f32' else (lambda t: t.bfloat16().float())
+    dev = lambda t, dt: nhwc(t).to(dt)
+    xdt = torch.float32 if tier in ('f32', 'stem', 'bf16_operands') else torch.bfloat16
+    ydt = torch.float32 if tier in ('f32', 'bf16_operands') else torch.bfloat16
+    prec = 0 if tier == 'f32' else 2
+    x = rnd(n, cin, h, w, seed=1) if tier in ('stem', 'bf16_operands') else r16(rnd(n, cin, h, w, seed=1))
+    wt = rnd(cout, cin, k, k, seed=2, scale=(2.0 / (cin * k * k)) ** 0.5)
+    ref_t = torch.float64 if tier == 'f32' else torch.float32
+    xr, wr = r16(x).to(ref_t).requires_grad_(True), (wt if which == 2 else r16(wt)).to(ref_t).requires_grad_(True)
+    y_ref = F.conv2d(xr, wr, None, stride=s, padding=p, dilation=d)
+    dy = rnd(*y_ref.shape, seed=4)
+    y_ref.backward(r16(dy).to(ref_t))
+    wg = wt.permute(0, 2, 3, 1).contiguous().cuda()
+    xg = dev(x, xdt)
+    yg = torch.empty((n,) + tuple(y_ref.shape[2:]) + (cout,), dtype=ydt, device='cuda') if which == 0 else dev(r16(dy) if tier != 'bf16_operands' else dy, ydt)
+    if which == 1:
+        xg = torch.empty_like(xg)
+    before = K.routing(**route)
+    try:
+        xd, yd, prm = L.tdesc(xg), L.tdesc(yg), L.conv_params(k, k, s, p, d, prec)
+        need = lib.pm_conv_workspace(byref(xd), byref(yd), byref(prm), which)
+        nbv, nbu = lib.pm_conv_winograd_v_bytes(byref(xd), byref(yd), byref(prm)), lib.pm_conv_wxf_bytes(byref(xd), byref(yd), byref(prm))
+        # -- the route, as the size queries tell it
+        al = lambda v: (v + 255) // 256 * 256
+        kp = (cin + 31) // 32 * 32
+        if 'wxf_points' in opt:
+            assert nbu == al(opt['wxf_points'] * cout * kp * 4) and wino_route(h, w, d, 4) == {36: 4, 16: 2}[opt['wxf_points']]
+        elif which == 0 and tier == 'bf16':
+            assert nbu == al(cout * k * k * ((cin + 63) // 64 * 64) * 2)
+            assert (need - nbu >= al(n * h * w * 64 * 2)) == bool(opt.get('padded_copy'))
+        elif which == 0:
+            assert nbu == 0 and need >= 2 * n * y_ref.shape[2] * y_ref.shape[3] * cout * 4      # no transformed filter, at least two split-K slabs
+        if which == 1 and tier == 'bf16':
+            assert lib.pm_conv_wxf_bytes_dgrad(byref(yd), byref(xd), byref(prm)) == 0      # stride 2: no kept rotated filter
+        if which == 2:
+            P = n * y_ref.shape[2] * y_ref.shape[3]
+            cb = max(1, (cout + 63) // 64)
+            want = 256 if cb == 1 else max(1, 1024 // cb)
+            bias_part = al(-(-P // min(2048, max(64, -(-P // want)))) * cout * 4)      # conv_igemm.hip colsum_rows
+            own = need - bias_part - (al(P * cout * 4) if opt.get('upcast_dy') else 0) - (al(n * h * w * cin * 4) if (tier == 'bf16' and xdt == torch.bfloat16) else 0)
+            assert (nbv > 0) == ('keep_v' in opt or 'v_bytes' in opt)
+            if nbv:
+                assert own > 2 * nbv                                        # V, Z and the slabs
+            if opt.get('slabs'):
+                assert own >= 2 * cout * k * k * cin * 4                    # at least two split-K slabs of dw
+            if opt.get('transposed'):
+                assert own >= al(cout * P * 2) + al(k * k * cin * P * 2)    # dy^T and the per-tap x^T
+        ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device='cuda')
+        K.profile_enable(True)
+        K.profile_read(clear=True)
+        st = L.stream()
+        if which == 0:
+            L.check(lib.pm_conv_fwd(byref(xd), wg.data_ptr(), byref(yd), byref(prm), None, ws.data_ptr(), need, st), 'pm_conv_fwd')
+        elif which == 1:
+            L.check(lib.pm_conv_bwd_data(byref(yd), wg.data_ptr(), byref(xd), byref(prm), None, ws.data_ptr(), need, st), 'pm_conv_bwd_data')
+        else:
+            dw = torch.empty_like(wg)
+            db = torch.empty(cout, device='cuda') if opt.get('dbias') else None
+            if opt.get('keep_v'):      # the forward pass leaves its transformed input for the weight gradient
+                v, y0 = torch.empty(nbv // 4, device='cuda'), torch.empty_like(yg)
+                pf = L.conv_params(k, k, s, p, d, prec)
+                pf.wino_v, pf.wino_v_bytes = v.data_ptr(), nbv
+                nf = lib.pm_conv_workspace(byref(xd), byref(yd), byref(pf), 0)
+                wf = torch.full((nf + 4096,), 0xA5, dtype=torch.uint8, device='cuda')
+                L.check(lib.pm_conv_fwd(byref(xd), wg.data_ptr(), byref(L.tdesc(y0)), byref(pf), None, wf.data_ptr(), nf, st), 'pm_conv_fwd')
+                assert bool((wf[nf:] == 0xA5).all())
+                K.profile_read(clear=True)
+                prm.wino_v, prm.wino_v_bytes = v.data_ptr(), nbv
+            L.check(lib.pm_conv_bwd_weight(byref(xd), byref(yd), dw.data_ptr(), L.ptr(db), byref(prm), ws.data_ptr(), need, st), 'pm_conv_bwd_weight')
+        torch.cuda.synchronize()
+        K.profile_enable(False)
+        assert bool((ws[need:] == 0xA5).all()), 'the call wrote behind the workspace it asked for'
+        # -- the kernel, as the profiler recorded it
+        assert K.profile_read(mode=rec_mode, prec=-1 if rec_prec is None else rec_prec)[2] > 0, 'no launch of the expected kernel form'
+        if which != rec_mode and rec_mode != 4 and not opt.get('transposed'):
+            assert K.profile_read(mode=which)[2] == 0      # Winograd point products run as forward GEMMs, never the direct data gradient
+        if 'ring' in opt:
+            assert any(K.profile_read(mode=2, bm=bm, bn=bn, km=2, nst=3, prec=4)[2] for bm, bn in ((256, 128), (128, 256))) == opt['ring']
+        K.profile_read(clear=True)
+    finally:
+        K.profile_enable(False)
+        K.routing(**before)
+    if which == 0:
+        if ydt == torch.bfloat16:
+            close16(nchw(yg.float()), y_ref.detach(), ulps=1.5)
+        else:
+            assert rel(nchw(yg), y_ref.detach()) < 2e-5
+    elif which == 1:
+        if xdt == torch.bfloat16:
+            close16(nchw(xg.float()), xr.grad, ulps=1.5)
+        else:
+            assert rel(nchw(xg), xr.grad) < 2e-5
+    else:
+        assert rel(dw.permute(0, 3, 1, 2), wr.grad) < (5e-5 if tier == 'f32' else 2e-4)
+        if db is not None:
+            assert rel(db, r16(dy).sum((0, 2, 3))) < 2e-5
