@@ -77,7 +77,9 @@ def test_conv_fwd_bwd(K, case):
 
 
 SPLIT_CASES = [
-    # n, cin, h, w, cout, k, stride, pad, dil   -- every gather form of the split path (conv_split.hip): k-contiguous / m-contiguous operands, the three K-state modes
+    # n, cin, h, w, cout, k, stride, pad, dil   -- the split path (conv_split.hip) at small sizes, with and without the Winograd route. With at most 1 152 output rows and
+    # output widths of at most 24 the direct route takes only the 64-row tiles in the forward pass and the data gradient and only the K_SMALL weight gradient on the
+    # 128 x 128 tile; tests/test_split_kernels.py reaches every tile and K-state instantiation at the same bar and proves it by the launch record
     (2, 256, 24, 24, 512, 1, 1, 0, 1),      # pointwise, K_FAST forward / data gradient; weight gradient over 1 152 pixels
     (2, 512, 24, 24, 128, 1, 1, 0, 1),      # 128-column output (128 x 128 or 64 x 128 tile)
     (1, 160, 20, 20, 192, 3, 1, 1, 1),      # direct 3x3 (channels below the Winograd route's 128 x 128 rule? no: taken -- see wino below), K_FAST
