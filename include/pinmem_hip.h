@@ -329,6 +329,31 @@ int pm_upsample_ce_fwd_field(const pm_tensor* logits, float inv_temp, const int6
 int pm_upsample_ce_bwd_field(const pm_tensor* logits /* shape only */, float inv_temp, int H, int W, const float* loss_out, const float* gscale,
                              const float* field, const pm_tensor* dlogits, void* stream);
 
+/* Weighted forms of K6: CrossEntropyLoss(weight=...) (loss.py:20-43,71-88), CrossEntropyLoss2d (:167-180) and ImageBasedCrossEntropyLoss2d (:120-163), still
+ * without the [B,C,H,W] logits. w = weights[b * weight_stride + label] (weight_stride 0: one [C] row for the whole batch); only labels in [0, C) contribute.
+ *   per_image == 0: loss = sum w nll / sum w over the batch (nn.CrossEntropyLoss(weight));
+ *   per_image == 1: loss = sum over images b, in index order, of (sum w nll)_b / (sum w)_b; an image whose weight sum is 0 makes it NaN, as nll_loss does.
+ * loss_out holds pm_upsample_wce_loss_floats(n) floats: [0] loss, [1] total weight sum, [2 + b] weight sum of image b. The gradient field is the unweighted one
+ * with every pixel's softmax - onehot multiplied by w: same layout and size (pm_upsample_ce_field_bytes). Backward scale per element:
+ * gscale * inv_temp / (per_image ? loss_out[2 + b] : loss_out[1]). With all-ones weights and per_image == 0 loss_out[0..1], the field and dlogits carry the
+ * bits of the unweighted entry points. Deterministic. */
+size_t pm_upsample_wce_loss_floats(int n);
+size_t pm_upsample_wce_workspace(int n, int H, int W);
+int pm_upsample_wce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                        int per_image, float* loss_out, void* ws /* pm_upsample_wce_workspace */, size_t ws_bytes, void* stream);
+int pm_upsample_wce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                              int per_image, float* loss_out, float* field, void* ws /* pm_upsample_wce_workspace */, size_t ws_bytes, void* stream);
+int pm_upsample_wce_bwd_field(const pm_tensor* logits /* shape only */, float inv_temp, int H, int W, int per_image, const float* loss_out,
+                              const float* gscale, const float* field, const pm_tensor* dlogits, void* stream);
+
+/* ImageBasedCrossEntropyLoss2d.calculate_weights (loss.py:136-146) on the device: weights[b][c] = ((hist != 0) * upper_bound * (1 - hist)) + 1 with
+ * hist = count of label c in image b / count of labels in [0, classes) in image b, evaluated in double as numpy does (product and sum rounded separately) and
+ * rounded to float -- bit-equal to the numpy expression. norm: 1 / hist instead of 1 - hist. per_batch: one histogram over all images, written to every row.
+ * An image without a countable label gets a NaN row (0 / 0). labels int64 [n,H,W]; weights float [n][classes], classes <= 32. Integer counts: deterministic. */
+size_t pm_label_class_weights_workspace(int n);
+int pm_label_class_weights(const int64_t* labels, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ---- K7 memory read (memory.py:317-336 + get_score :167-189) ---------------------------------------------------
  * x: [N rows of d=256] (NHWC feature map); mem [m<=32][d]; writes qr = [qhat | P_m.M] (2d channels, input of
  * memory.output), score S [N][m] (raw cosine scores), P_m [N][m] (softmax over slots, or gumbel if noise given). */

@@ -7,6 +7,10 @@
 // Backward: the transposed bilinear operator is separable, so the gradient is gathered in two passes without atomics
 // (deterministic): (1) per hi-res row, softmax - onehot of every hi-res pixel once (staged in LDS) reduced over its columns to the
 // low-res columns -> T[n][H][w][C]; (2) per low-res pixel, T reduced over the supporting hi-res rows.
+// Weighted forms (bool template parameter WT; the WT = false instantiations are the kernels above, unchanged): CrossEntropyLoss(weight=...), CrossEntropyLoss2d and
+// ImageBasedCrossEntropyLoss2d (/root/reference/loss.py:20-43,71-88,120-180). Every pixel's terms are multiplied by w[image][label] and the divisor is a weight sum
+// (of the batch, or of each image with the per-image losses added in image order); pm_label_class_weights builds the image-based weight rows from the labels on
+// the device (loss.py:136-146), so the criterion needs neither the materialised logits nor a host round trip.
 #include "pm_common.h"
 
 namespace {
@@ -20,6 +24,10 @@ struct CEGeom {
   const int64_t* labels;
   int H, W;
   float sy, sx, inv_temp;
+  // weighted forms only (WT): w = wts[b * wstride + label]; per_image: every image is divided by its own weight sum
+  const float* wts;
+  long wstride;
+  int per_image;
 };
 
 // interpolated logits of hi-res pixel (b, Y, X) into v[0..C)
@@ -50,15 +58,20 @@ __device__ __forceinline__ int ce_xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
-template <int C_>
+// WT: blockIdx.y = image (the final reduce needs every image's partials apart), the x blocks stride over that image's pixels; (sum w nll, sum w) per block.
+template <int C_, bool WT = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __restrict__ part) {
   const int C = C_ > 0 ? C_ : g.C;
-  const long total = (long)g.n * g.H * g.W;
+  const long total = WT ? (long)g.H * g.W : (long)g.n * g.H * g.W;
+  const int64_t* labels = WT ? g.labels + (long)blockIdx.y * total : g.labels;
   float lsum = 0.f, lcnt = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int64_t lab = g.labels[i];
+    const int64_t lab = labels[i];
     if (lab == 255) continue;
-    const int X = (int)(i % g.W), Y = (int)((i / g.W) % g.H), b = (int)(i / ((long)g.W * g.H));
+    if constexpr (WT) {
+      if (lab < 0 || lab >= C) continue;      // only labels of a class carry a weight
+    }
+    const int X = (int)(i % g.W), Y = (int)((i / g.W) % g.H), b = WT ? (int)blockIdx.y : (int)(i / ((long)g.W * g.H));
     const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h), lx = pm_ac_lerp(g.sx, X, g.w);
     float v[C_ > 0 ? C_ : MAXC];
     interp_logits<C_>(g, b, ly, lx, v);
@@ -73,8 +86,14 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __re
 #pragma unroll
     for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
       if (c < C) se += expf(v[c] - mx);
-    lsum += (mx + logf(se)) - vl;
-    lcnt += 1.f;
+    if constexpr (WT) {
+      const float wl = g.wts[(long)b * g.wstride + lab];
+      lsum += wl * ((mx + logf(se)) - vl);
+      lcnt += wl;
+    } else {
+      lsum += (mx + logf(se)) - vl;
+      lcnt += 1.f;
+    }
   }
   __shared__ float sm[2][4];
   lsum = pm_wave_sum(lsum);
@@ -82,21 +101,33 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __re
   if ((threadIdx.x & 63) == 0) sm[0][threadIdx.x >> 6] = lsum, sm[1][threadIdx.x >> 6] = lcnt;
   __syncthreads();
   if (threadIdx.x == 0) {
-    part[blockIdx.x * 2] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
-    part[blockIdx.x * 2 + 1] = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
+    const long pb = WT ? (long)blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
+    part[pb * 2] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
+    part[pb * 2 + 1] = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
   }
+}
+
+// WT kernels whose block belongs to one image: that image's C weights, staged once per block (visible after the block's next barrier)
+__device__ __forceinline__ void ce_stage_weights(const CEGeom& g, int b, float* wsm) {
+  if ((int)threadIdx.x < g.C) wsm[threadIdx.x] = g.wts[(long)b * g.wstride + threadIdx.x];
 }
 
 // Row-staged forward: block = one hi-res row (Y, image b). The two low-res logit rows that row interpolates between are staged in LDS
 // once (coalesced, pre-scaled by 1/T); every hi-res pixel then gathers its 4 x C taps from LDS instead of issuing 4 x C scattered global
 // loads. The interpolation expression is the one of interp_logits / ce_bwd_rows_kernel, so the per-pixel logits carry the same bits.
-template <int C_>
+template <int C_, bool WT = false>
 __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float* __restrict__ part) {
   extern __shared__ float L[];
   const int C = C_ > 0 ? C_ : g.C;
   const int CP = C | 1;
   const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
+  float* wsm = nullptr;
+  if constexpr (WT) {
+    __shared__ float wrow[MAXC];
+    wsm = wrow;
+    ce_stage_weights(g, b, wsm);
+  }
   const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
   float* L0 = L;
   float* L1 = L + (size_t)g.w * CP;
@@ -114,6 +145,9 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
   for (int X = threadIdx.x, u = 0; X < g.W; X += 256, ++u) {
     const int64_t lab = u < 3 ? (u == 0 ? labs[0] : (u == 1 ? labs[1] : labs[2])) : lrow[X];
     if (lab == 255) continue;
+    if constexpr (WT) {
+      if (lab < 0 || lab >= C) continue;
+    }
     const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
     const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
     float v[C_ > 0 ? C_ : MAXC];
@@ -129,8 +163,14 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
 #pragma unroll
     for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
       if (c < C) se += __expf(v[c] - mx);   // v_exp_f32 (~1 ulp per term, as in the backward pass): the libm expf was 2/3 of this kernel's ALU work
-    lsum += (mx + logf(se)) - vl;
-    lcnt += 1.f;
+    if constexpr (WT) {
+      const float wl = wsm[lab];
+      lsum += wl * ((mx + logf(se)) - vl);
+      lcnt += wl;
+    } else {
+      lsum += (mx + logf(se)) - vl;
+      lcnt += 1.f;
+    }
   }
   __shared__ float sm[2][4];
   lsum = pm_wave_sum(lsum);
@@ -165,6 +205,37 @@ __global__ __launch_bounds__(CE_FINAL_T) void ce_final_kernel(const float* __res
   }
 }
 
+// Weighted forms: the block partials are image-major, `per` consecutive ones per image. One block folds image after image (the tree of ce_final_kernel per image, in
+// double): out[2 + b] = weight sum of image b; per_image: out[0] = sum over b, in index order, of (sum w nll)_b / (sum w)_b -- 0 / 0 = NaN for an image without a
+// weighted pixel, as nll_loss -- and out[1] = total weight sum. Without per_image, out[0] and out[1] are ce_final_kernel's (same order as the unweighted loss).
+__global__ __launch_bounds__(CE_FINAL_T) void ce_final_img_kernel(const float* __restrict__ part, int per, int n, int per_image, float* __restrict__ out) {
+  __shared__ double s[2][CE_FINAL_T];
+  double loss = 0.0, den = 0.0;
+  for (int b = 0; b < n; ++b) {
+    double a = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < per; i += CE_FINAL_T) {
+      const float2 v = *reinterpret_cast<const float2*>(part + ((long)b * per + i) * 2);
+      a += (double)v.x, c += (double)v.y;
+    }
+    s[0][threadIdx.x] = a, s[1][threadIdx.x] = c;
+    __syncthreads();
+    for (int w = CE_FINAL_T / 2; w >= 1; w >>= 1) {
+      if ((int)threadIdx.x < w) s[0][threadIdx.x] += s[0][threadIdx.x + w], s[1][threadIdx.x] += s[1][threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      out[2 + b] = (float)s[1][0];
+      loss += s[0][0] / s[1][0];
+      den += s[1][0];
+    }
+    __syncthreads();      // s is rewritten for the next image
+  }
+  if (threadIdx.x == 0 && per_image) {
+    out[0] = (float)loss;
+    out[1] = (float)den;
+  }
+}
+
 __host__ __device__ __forceinline__ void support(float scale, int i, int out, int& lo, int& hi) {   // hi-res indices that can touch low-res index i
   if (scale <= 0.f) {
     lo = 0, hi = out - 1;
@@ -176,7 +247,8 @@ __host__ __device__ __forceinline__ void support(float scale, int i, int out, in
 }
 __device__ __forceinline__ float tap_weight(const pm_lerp& l, int i) { return (l.i0 == i ? l.w0 : 0.f) + (l.i1 == i ? l.w1 : 0.f); }
 
-// pass 2: thread per (low-res pixel, class): supporting hi-res rows in ascending order, then the loss scale
+// pass 2: thread per (low-res pixel, class): supporting hi-res rows in ascending order, then the loss scale (WT, per_image: the image's own weight sum divides)
+template <bool WT = false>
 __global__ __launch_bounds__(256) void ce_bwd_cols_kernel(const CEGeom g, const float* __restrict__ T, const float* __restrict__ loss_out,
                                                           const float* __restrict__ gscale, float* __restrict__ dl, long dlp) {
   const int C = g.C;
@@ -193,7 +265,12 @@ __global__ __launch_bounds__(256) void ce_bwd_cols_kernel(const CEGeom g, const 
     support(g.sy, y, g.H, lo, hi);
     float acc = 0.f;
     for (int Y = lo; Y <= hi; ++Y) acc += tap_weight(pm_ac_lerp(g.sy, Y, g.h), y) * T[(((long)b * g.H + Y) * g.w + x) * C + c];
-    dl[((long)(b * g.h + y) * g.w + x) * dlp + c] = acc * gs;
+    if constexpr (WT) {
+      const float gsb = g.per_image ? (gscale ? gscale[0] : 1.f) * g.inv_temp / loss_out[2 + b] : gs;
+      dl[((long)(b * g.h + y) * g.w + x) * dlp + c] = acc * gsb;
+    } else {
+      dl[((long)(b * g.h + y) * g.w + x) * dlp + c] = acc * gs;
+    }
   }
 }
 
@@ -217,7 +294,7 @@ __device__ __forceinline__ int ce_first_ge(float sx, int k, int w, int W) {   //
   return X;
 }
 
-template <int C_, int PARTS, bool WITH_T>
+template <int C_, int PARTS, bool WITH_T, bool WT = false>
 __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, float* __restrict__ part, float* __restrict__ T) {
   extern __shared__ float L[];
   __shared__ float carry[MAXC];   // B of the last column of a round, owed to the first column of the next (rows wider than one round only)
@@ -226,6 +303,12 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
   const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
   const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
+  float* wsm = nullptr;
+  if constexpr (WT) {
+    __shared__ float wrow[MAXC];
+    wsm = wrow;
+    ce_stage_weights(g, b, wsm);
+  }
   const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
   float* L0 = L;
   float* L1 = L + (size_t)g.w * CP;                                   // (+ C floats of slack behind it: bufB holds one column more than a round)
@@ -267,6 +350,9 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
       for (int X = ja; X < jb; ++X) {
         const int lab = lab8[X];
         if (lab == 255) continue;
+        if constexpr (WT && C_ > 0) {
+          if (lab >= C) continue;      // only labels of a class carry a weight
+        }
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
         const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
         float v[CR];
@@ -282,15 +368,25 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
 #pragma unroll
         for (int c = 0; c < CR; ++c)
           if (c < C) v[c] = __expf(v[c] - mx), se += v[c];
-        lsum += (mx + logf(se)) - vl;
-        lcnt += 1.f;
+        float wl = 1.f;
+        if constexpr (WT) {
+          // generic class count: a label that is no class weighs 0 by a select, not by the branch above -- the branch tells the compiler that C > 0, it then
+          // lays out the class loop differently and contracts the interpolation of class 0 into another fma than the unweighted kernel does (1 ulp)
+          wl = C_ > 0 || lab < C ? wsm[min(lab, MAXC - 1)] : 0.f;
+          lsum += wl * ((mx + logf(se)) - vl);
+          lcnt += wl;
+        } else {
+          lsum += (mx + logf(se)) - vl;
+          lcnt += 1.f;
+        }
         if constexpr (WITH_T) {
           const float inv = 1.f / se;
           const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
           for (int c = 0; c < CR; ++c)
             if (c < C) {
-              const float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
+              float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
+              if constexpr (WT) gq *= wl;      // w (softmax - onehot): every other expression stays the unweighted one, so w = 1 leaves its bits
               A[c] += wa * gq, B[c] += wb * gq;
             }
         }
@@ -347,7 +443,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
 //     for all rounds put the 1 024-thread block 27 registers over its 128-register budget and the spills into the pixel loop: 190 instead of 120 us), loss
 //     partials per block: all fixed-order, deterministic.
 __host__ __device__ __forceinline__ int ce2_rows_per_interval(int h, int H) { return (H + h - 1) / h + 1; }
-template <int C_>
+template <int C_, bool WT = false>
 __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, float* __restrict__ part, float* __restrict__ FA, float* __restrict__ FB, int tpr, int rg, int nseg, int ws) {
   extern __shared__ float L[];
   __shared__ float sm2[2][16];
@@ -364,6 +460,12 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
   const int seg = bid % nseg, y = (bid / nseg) % g.h, b = bid / (nseg * g.h);
   const int y1 = min(y + 1, g.h - 1);
+  float* wsm = nullptr;
+  if constexpr (WT) {
+    __shared__ float wrow[MAXC];
+    wsm = wrow;
+    ce_stage_weights(g, b, wsm);
+  }
   const int c0 = seg * ws, ncol = min(ws, g.w - c0);
   const int cb = max(c0 - 1, 0), ce = min(c0 + ncol, g.w - 1), nst = ce - cb + 1;   // staged low-res columns [cb, ce]: the taps of the lanes' pixels
   const int Wp = (g.W + 15) & ~15;
@@ -409,6 +511,9 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
       for (int X = j0; X < j1; ++X) {
         const int lab = mylab[X - Xlo];
         if (lab == 255) continue;
+        if constexpr (WT) {
+          if (lab >= C) continue;
+        }
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
         const float *p00 = L0 + (lx.i0 - cb) * CP, *p01 = L0 + (lx.i1 - cb) * CP, *p10 = L1 + (lx.i0 - cb) * CP, *p11 = L1 + (lx.i1 - cb) * CP;
         float v[CR];
@@ -424,13 +529,20 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
 #pragma unroll
         for (int c = 0; c < CR; ++c)
           if (c < C) v[c] = __expf(v[c] - mx), se += v[c];
-        if (own) lsum += (mx + logf(se)) - vl, lcnt += 1.f;      // the left-neighbour lane's pixels are counted by the segment that owns them
+        float wl = 1.f;
+        if constexpr (WT) {
+          wl = wsm[lab];
+          if (own) lsum += wl * ((mx + logf(se)) - vl), lcnt += wl;
+        } else {
+          if (own) lsum += (mx + logf(se)) - vl, lcnt += 1.f;      // the left-neighbour lane's pixels are counted by the segment that owns them
+        }
         const float inv = 1.f / se;
         const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
         for (int c = 0; c < CR; ++c)
           if (c < C) {
-            const float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
+            float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
+            if constexpr (WT) gq *= wl;      // as in ce_fused_rows_kernel
             A[c] += wa * gq, B[c] += wb * gq;
           }
       }
@@ -476,6 +588,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   }
 }
 // backward of the interval form: dl[b][y][x][c] = (FA[b][y][x][c] + FB[b][y - 1][x][c]) x upstream scale / valid pixels / T
+template <bool WT = false>
 __global__ __launch_bounds__(256) void ce_bwd_rows2_kernel(const CEGeom g, const float* __restrict__ FA, const float* __restrict__ FB, const float* __restrict__ loss_out,
                                                            const float* __restrict__ gscale, float* __restrict__ dl, long dlp) {
   const int C = g.C;
@@ -486,7 +599,12 @@ __global__ __launch_bounds__(256) void ce_bwd_rows2_kernel(const CEGeom g, const
     const int c = (int)(i - pix * C);
     const int y = (int)((pix / g.w) % g.h);
     const float v = FA[i] + (y > 0 ? FB[i - rowsz] : 0.f);
-    dl[pix * dlp + c] = v * gs;
+    if constexpr (WT) {
+      const float gsb = g.per_image ? (gscale ? gscale[0] : 1.f) * g.inv_temp / loss_out[2 + pix / ((long)g.w * g.h)] : gs;
+      dl[pix * dlp + c] = v * gsb;
+    } else {
+      dl[pix * dlp + c] = v * gs;
+    }
   }
 }
 constexpr size_t ROWS2_MAX_LDS = 120 * 1024;      // dynamic LDS of the interval form (opt-in beyond 64 KB, set per device at the first launch)
@@ -513,11 +631,12 @@ inline Rows2Plan rows2_plan(const CEGeom& g) {
   return p;
 }
 
+template <bool WT = false>
 inline void rows2_launch(const CEGeom& g, const Rows2Plan& r, float* part, float* field, hipStream_t st) {
   static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs the opt-in, once per device
-  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19>), (int)ROWS2_MAX_LDS);
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19, WT>), (int)ROWS2_MAX_LDS);
   const long half = (long)g.n * g.h * g.w * g.C;
-  hipLaunchKernelGGL(ce_fused_rows2_kernel<19>, dim3(g.n * g.h * r.nseg), dim3(r.tpr * r.rg), r.lds, st, g, part, field, field + half, r.tpr, r.rg, r.nseg, r.ws);
+  hipLaunchKernelGGL((ce_fused_rows2_kernel<19, WT>), dim3(g.n * g.h * r.nseg), dim3(r.tpr * r.rg), r.lds, st, g, part, field, field + half, r.tpr, r.rg, r.nseg, r.ws);
 }
 
 inline int fwd_blocks(long total) { return (int)std::min<long>((total + 255) / 256, 4096); }
@@ -528,6 +647,7 @@ int fill(CEGeom& g, const pm_tensor* logits, float inv_temp, const int64_t* labe
   g.logits = (const float*)logits->ptr, g.lp = logits->pitch, g.n = logits->n, g.h = logits->h, g.w = logits->w, g.C = logits->c;
   g.labels = labels, g.H = H, g.W = W;
   g.sy = pm_ac_scale(logits->h, H), g.sx = pm_ac_scale(logits->w, W), g.inv_temp = inv_temp;
+  g.wts = nullptr, g.wstride = 0, g.per_image = 0;
   return PM_OK;
 }
 
@@ -576,16 +696,16 @@ inline FusedPlan fused_plan(const CEGeom& g) {
   return p;
 }
 constexpr size_t FUSED_MAX_LDS = 159 * 1024;   // dynamic part; the kernel also declares 160 B of static LDS
-template <int CC, int PP, bool WITH_T>
+template <int CC, int PP, bool WITH_T, bool WT>
 void fused_launch_one(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
   // > 64 KB of dynamic LDS (logit rows wider than ~420 pixels x 19 classes) needs an explicit opt-in, once per kernel AND device
   static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, WITH_T>), (int)FUSED_MAX_LDS);
-  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, WITH_T>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, WITH_T, WT>), (int)FUSED_MAX_LDS);
+  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, WITH_T, WT>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
 }
-template <bool WITH_T>
+template <bool WITH_T, bool WT = false>
 int fused_launch(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
-#define PM_CE_LAUNCH(CC, PP) fused_launch_one<CC, PP, WITH_T>(g, p, part, T, st)
+#define PM_CE_LAUNCH(CC, PP) fused_launch_one<CC, PP, WITH_T, WT>(g, p, part, T, st)
 #define PM_CE_PARTS(CC)                         \
   switch (p.parts) {                            \
     case 1: PM_CE_LAUNCH(CC, 1); break;         \
@@ -645,11 +765,11 @@ extern "C" int pm_upsample_ce_bwd_field(const pm_tensor* logits, float inv_temp,
   PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "upsample_ce_bwd_field: bad args");
   const long total = (long)g.n * g.h * g.w * g.C;
   if (rows2_plan(g).ok) {
-    hipLaunchKernelGGL(ce_bwd_rows2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, field + total,
+    hipLaunchKernelGGL(ce_bwd_rows2_kernel<false>, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, field + total,
                        loss_out, gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
     return pm_check_launch("upsample_ce_bwd_field");
   }
-  hipLaunchKernelGGL(ce_bwd_cols_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, loss_out,
+  hipLaunchKernelGGL(ce_bwd_cols_kernel<false>, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, loss_out,
                      gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
   return pm_check_launch("upsample_ce_bwd_field");
 }
@@ -682,3 +802,159 @@ extern "C" int pm_upsample_ce_bwd(const pm_tensor* logits, float inv_temp, const
   return pm_upsample_ce_bwd_field(logits, inv_temp, H, W, loss_out, gscale, field, dlogits, stream);
 }
 
+
+// ---- weighted forms: CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d (loss.py:20-43,71-88,120-180) ---------------------------------------------------------
+// Same kernels (WT = true), same routing between them as the unweighted entry points, same field layout. Block partials are (sum w nll, sum w), image-major.
+namespace {
+inline int wfwd_blocks(long hw) { return (int)std::min<long>((hw + 255) / 256, 512); }      // x blocks per image of the flat weighted forward
+
+int fill_w(CEGeom& g, const float* weights, int64_t weight_stride, int per_image, const char* who) {
+  PM_REQUIRE(weights, PM_EINVAL, "%s: null weights", who);
+  PM_REQUIRE(weight_stride == 0 || weight_stride >= g.C, PM_EINVAL, "%s: weight_stride %lld is neither 0 nor >= %d classes", who, (long long)weight_stride, g.C);
+  PM_REQUIRE(per_image == 0 || per_image == 1, PM_EINVAL, "%s: per_image %d is neither 0 nor 1", who, per_image);
+  g.wts = weights, g.wstride = (long)weight_stride, g.per_image = per_image;
+  return PM_OK;
+}
+
+// per: block partials per image. Global form: loss and total weight in the order of the unweighted reduce, then the per-image weight sums.
+inline void wce_final(const float* part, int per, int n, int per_image, float* loss_out, hipStream_t st) {
+  if (!per_image) hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, n * per, loss_out);
+  hipLaunchKernelGGL(ce_final_img_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, per, n, per_image, loss_out);
+}
+}  // namespace
+
+extern "C" size_t pm_upsample_wce_loss_floats(int n) { return (size_t)2 + (size_t)std::max(n, 0); }
+
+extern "C" size_t pm_upsample_wce_workspace(int n, int H, int W) {      // one (sum w nll, sum w) pair per block of any weighted forward kernel
+  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H * 2) * 2 * sizeof(float), 256);
+}
+
+extern "C" int pm_upsample_wce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                                   int per_image, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
+  PM_REQUIRE_F32(logits, "upsample_wce_fwd");
+  CEGeom g;
+  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_wce_fwd")) return e;
+  if (int e = fill_w(g, weights, weight_stride, per_image, "upsample_wce_fwd")) return e;
+  PM_REQUIRE(loss_out && ws && ws_bytes >= pm_upsample_wce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_wce_fwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  int per;
+  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);
+  if (row_lds <= 48 * 1024 && (long)g.n * H <= (1 << 20) && W >= 32) {      // as pm_upsample_ce_fwd
+    per = H;
+    if (g.C == 19) hipLaunchKernelGGL((ce_fwd_rows_kernel<19, true>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
+    else hipLaunchKernelGGL((ce_fwd_rows_kernel<0, true>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
+  } else {
+    PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "upsample_wce_fwd: %d images > 65535", g.n);
+    per = wfwd_blocks((long)H * W);
+    if (g.C == 19) hipLaunchKernelGGL((ce_fwd_kernel<19, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws);
+    else hipLaunchKernelGGL((ce_fwd_kernel<0, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws);
+  }
+  wce_final((const float*)ws, per, g.n, per_image, loss_out, st);
+  return pm_check_launch("upsample_wce_fwd");
+}
+
+extern "C" int pm_upsample_wce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                                         int per_image, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
+  PM_REQUIRE_F32(logits, "upsample_wce_fwd_field");
+  CEGeom g;
+  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_wce_fwd_field")) return e;
+  if (int e = fill_w(g, weights, weight_stride, per_image, "upsample_wce_fwd_field")) return e;
+  PM_REQUIRE(loss_out && field && ws && ws_bytes >= pm_upsample_wce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_wce_fwd_field: workspace too small / null field");
+  hipStream_t st = (hipStream_t)stream;
+  if (const Rows2Plan r = rows2_plan(g); r.ok) {
+    rows2_launch<true>(g, r, (float*)ws, field, st);
+    wce_final((const float*)ws, g.h * r.nseg, g.n, per_image, loss_out, st);
+    return pm_check_launch("upsample_wce_fwd_field");
+  }
+  const FusedPlan p = fused_plan(g);
+  PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * H <= (1l << 30), PM_EUNSUPPORTED, "upsample_wce_fwd_field: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
+  if (int e = fused_launch<true, true>(g, p, (float*)ws, field, st)) return e;
+  wce_final((const float*)ws, H, g.n, per_image, loss_out, st);
+  return pm_check_launch("upsample_wce_fwd_field");
+}
+
+extern "C" int pm_upsample_wce_bwd_field(const pm_tensor* logits, float inv_temp, int H, int W, int per_image, const float* loss_out, const float* gscale,
+                                         const float* field, const pm_tensor* dlogits, void* stream) {
+  PM_REQUIRE_F32(logits, "upsample_wce_bwd_field");
+  PM_REQUIRE_F32(dlogits, "upsample_wce_bwd_field");
+  CEGeom g;
+  static const int64_t dummy = 0;
+  if (int e = fill(g, logits, inv_temp, &dummy, H, W, "upsample_wce_bwd_field")) return e;      // the row pass reads neither labels, logits nor weights
+  PM_REQUIRE(per_image == 0 || per_image == 1, PM_EINVAL, "upsample_wce_bwd_field: per_image %d is neither 0 nor 1", per_image);
+  PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "upsample_wce_bwd_field: bad args");
+  g.per_image = per_image;
+  const long total = (long)g.n * g.h * g.w * g.C;
+  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
+  if (rows2_plan(g).ok)
+    hipLaunchKernelGGL(ce_bwd_rows2_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, field + total, loss_out, gscale, (float*)dlogits->ptr,
+                       (long)dlogits->pitch);
+  else
+    hipLaunchKernelGGL(ce_bwd_cols_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, loss_out, gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
+  return pm_check_launch("upsample_wce_bwd_field");
+}
+
+// ---- per-image class weights from the labels: ImageBasedCrossEntropyLoss2d.calculate_weights (loss.py:136-146) without the trip through the host ---------------------
+// counts: LDS integer counters per block, one row of block counts per (image, block), folded by integer adds -- order-free, so deterministic. The weight expression is
+// numpy's ((hist != 0) * ub * (1 - hist)) + 1 in double, product and sum rounded separately (no fma), then rounded to float.
+namespace {
+constexpr int LCW_BLOCKS = 64;      // count blocks per image, at most
+constexpr int LCW_PIX = 4096;       // pixels per count block, at least
+inline int lcw_blocks(long hw) { return (int)std::max<long>(1, std::min<long>(LCW_BLOCKS, (hw + LCW_PIX - 1) / LCW_PIX)); }
+
+__global__ __launch_bounds__(256) void label_count_kernel(const int64_t* __restrict__ labels, long hw, int classes, unsigned* __restrict__ counts) {
+  __shared__ unsigned cnt[MAXC];
+  if (threadIdx.x < MAXC) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t* lab = labels + (long)blockIdx.y * hw;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < hw; i += (long)gridDim.x * 256) {
+    const int64_t l = lab[i];
+    if (l >= 0 && l < classes) atomicAdd(&cnt[(int)l], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < MAXC) counts[((long)blockIdx.y * gridDim.x + blockIdx.x) * MAXC + threadIdx.x] = cnt[threadIdx.x];
+}
+
+__device__ __forceinline__ double lcw_weight(double hist, double ub, int norm) {
+#pragma clang fp contract(off)
+  const double m = hist != 0.0 ? ub : 0.0;
+  const double t = norm ? 1.0 / hist : 1.0 - hist;
+  const double p = m * t;
+  return p + 1.0;
+}
+
+// block = one output row b: 32 classes x 8 slices of the count blocks of image b (per_batch: of every image)
+__global__ __launch_bounds__(256) void label_weights_kernel(const unsigned* __restrict__ counts, int nblk, int n, int classes, double ub, int norm, int per_batch,
+                                                            float* __restrict__ weights) {
+  __shared__ unsigned long long tot[MAXC];
+  const int b = blockIdx.x, c = threadIdx.x & (MAXC - 1), sl = threadIdx.x / MAXC;
+  if (threadIdx.x < MAXC) tot[threadIdx.x] = 0ull;
+  __syncthreads();
+  const long r0 = per_batch ? 0 : (long)b * nblk, r1 = per_batch ? (long)n * nblk : (long)(b + 1) * nblk;
+  unsigned long long a = 0ull;
+  for (long r = r0 + sl; r < r1; r += 256 / MAXC) a += counts[r * MAXC + c];
+  if (a) atomicAdd(&tot[c], a);
+  __syncthreads();
+  if ((int)threadIdx.x < classes) {
+    unsigned long long all = 0ull;
+    for (int k = 0; k < classes; ++k) all += tot[k];
+    const double hist = (double)tot[threadIdx.x] / (double)all;      // 0 / 0 = NaN for an image without a countable pixel, as numpy
+    weights[(long)b * classes + threadIdx.x] = (float)lcw_weight(hist, ub, norm);
+  }
+}
+}  // namespace
+
+extern "C" size_t pm_label_class_weights_workspace(int n) { return pm_align_up((size_t)std::max(n, 1) * LCW_BLOCKS * MAXC * sizeof(unsigned), 256); }
+
+extern "C" int pm_label_class_weights(const int64_t* labels, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  PM_REQUIRE(labels && weights && n > 0 && H > 0 && W > 0, PM_EINVAL, "label_class_weights: null/empty");
+  PM_REQUIRE(classes >= 1 && classes <= MAXC, PM_EUNSUPPORTED, "label_class_weights: classes %d not in 1..%d", classes, MAXC);
+  PM_REQUIRE(n <= 65535, PM_EUNSUPPORTED, "label_class_weights: %d images > 65535", n);
+  PM_REQUIRE(ws && ws_bytes >= pm_label_class_weights_workspace(n), PM_EWORKSPACE, "label_class_weights: workspace too small");
+  const long hw = (long)H * W;
+  const int nblk = lcw_blocks(hw);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(label_count_kernel, dim3(nblk, n), dim3(256), 0, st, labels, hw, classes, (unsigned*)ws);
+  hipLaunchKernelGGL(label_weights_kernel, dim3(n), dim3(256), 0, st, (const unsigned*)ws, nblk, n, classes, upper_bound, norm != 0, per_batch != 0, weights);
+  return pm_check_launch("label_class_weights");
+}

@@ -702,6 +702,80 @@ def upsample_ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp=1.
     return dl
 
 
+# ---- weighted forms: CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d (loss.py:20-43,71-88,120-180) -------------------------
+def label_class_weights(labels, classes, upper_bound=1.0, norm=False, per_batch=False, out=None):
+    """ImageBasedCrossEntropyLoss2d.calculate_weights on the device: int64 labels [n,H,W] -> float32 [n, classes] weight rows, bit-equal to the numpy
+    expression, without a host sync (per_batch: the batch histogram in every row). `out`: a contiguous float32 buffer of at least n * classes elements."""
+    n, H, W = labels.shape
+    labels = labels.contiguous()
+    assert labels.dtype == torch.int64 and labels.is_cuda
+    if out is None:
+        out = torch.empty((n, classes), dtype=torch.float32, device=labels.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * classes
+    lib = _lib()
+    nb = lib.pm_label_class_weights_workspace(n)
+    ws = workspace(nb, labels.device)
+    check(lib.pm_label_class_weights(labels.data_ptr(), n, H, W, classes, float(upper_bound), int(bool(norm)), int(bool(per_batch)), out.data_ptr(), ptr(ws), nb,
+                                     stream()), 'pm_label_class_weights')
+    return out
+
+
+def _wce_weights(weights, logits):
+    """[C] (one row for the batch: stride 0) or [n, C] float32 weights -> (tensor kept alive, row stride)."""
+    n, C = logits.shape[0], logits.shape[3]
+    weights = weights.to(device=logits.device, dtype=torch.float32)
+    if weights.dim() == 1:
+        assert weights.shape[0] == C, 'expected %d class weights, got %s' % (C, tuple(weights.shape))
+        return weights.contiguous(), 0
+    assert weights.dim() == 2 and tuple(weights.shape) == (n, C), 'expected [%d, %d] weight rows, got %s' % (n, C, tuple(weights.shape))
+    if weights.stride(1) != 1:
+        weights = weights.contiguous()
+    return weights, (weights.stride(0) if n > 1 else C)
+
+
+def _wce_out(n, device, out):
+    need = _lib().pm_upsample_wce_loss_floats(n)
+    if out is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
+    return out
+
+
+def upsample_wce_fwd(logits, labels, weights, per_image, inv_temp=1.0, out=None):
+    """-> loss_out[2 + n]: [0] the loss, [1] the total weight sum, [2 + b] the weight sum of image b (include/pinmem_hip.h)."""
+    n, H, W = labels.shape
+    out = _wce_out(n, logits.device, out)
+    wt, stride = _wce_weights(weights, logits)
+    lib = _lib()
+    nb = lib.pm_upsample_wce_workspace(n, H, W)
+    ws = workspace(nb, logits.device)
+    check(lib.pm_upsample_wce_fwd(byref(tdesc(logits)), inv_temp, labels.data_ptr(), H, W, wt.data_ptr(), stride, int(bool(per_image)), out.data_ptr(), ptr(ws), nb,
+                                  stream()), 'pm_upsample_wce_fwd')
+    return out
+
+
+def upsample_wce_fwd_field(logits, labels, weights, per_image, inv_temp=1.0, out=None):
+    """Training forward: -> (loss_out[2 + n], field); the field has the layout and size of upsample_ce_fwd_field's."""
+    n, H, W = labels.shape
+    out = _wce_out(n, logits.device, out)
+    wt, stride = _wce_weights(weights, logits)
+    lib, ld = _lib(), tdesc(logits)
+    field = torch.empty(lib.pm_upsample_ce_field_bytes(byref(ld), H, W) // 4, dtype=torch.float32, device=logits.device)
+    nb = lib.pm_upsample_wce_workspace(n, H, W)
+    ws = workspace(nb, logits.device)
+    check(lib.pm_upsample_wce_fwd_field(byref(ld), inv_temp, labels.data_ptr(), H, W, wt.data_ptr(), stride, int(bool(per_image)), out.data_ptr(), field.data_ptr(),
+                                        ptr(ws), nb, stream()), 'pm_upsample_wce_fwd_field')
+    return out, field
+
+
+def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image, inv_temp=1.0):
+    H, W = label_hw
+    dl = new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
+    check(_lib().pm_upsample_wce_bwd_field(byref(tdesc(logits)), inv_temp, H, W, int(bool(per_image)), loss_out.data_ptr(), ptr(gscale), field.data_ptr(),
+                                           byref(tdesc(dl)), stream()), 'pm_upsample_wce_bwd_field')
+    return dl
+
+
 def refresh_f32_filters():
     """fp32 tier twin of refresh_bf16_filters(): every kept Winograd FORWARD transform (U = G g Gt of the wide stride-1 3x3 layers) that was used since the last call and
     is now out of date, rewritten in one launch (pm_conv_wxf_refresh_f32) behind the optimizer step instead of ~20 latency-bound per-layer launches in front of the

@@ -667,6 +667,29 @@ class _UpsampleCE(torch.autograd.Function):
         return nchw(K.upsample_ce_bwd(lv, labels, out, gs, ctx.inv_temp)), None, None, None
 
 
+class _UpsampleWCE(torch.autograd.Function):
+    """_UpsampleCE with class weights: w = weights[label] ([C]) or weights[image][label] ([n, C]); per_image: the sum over images of each image's weighted mean
+    (ImageBasedCrossEntropyLoss2d), else sum w nll / sum w over the batch (CrossEntropyLoss(weight)). The weights carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weights, per_image, inv_temp, want_grad):
+        lv = nhwc(logits)
+        labels = labels.contiguous()
+        ctx.inv_temp, ctx.hw, ctx.per_image = inv_temp, tuple(labels.shape[1:]), per_image
+        if want_grad:
+            out, field = K.upsample_wce_fwd_field(lv, labels, weights, per_image, inv_temp)
+            ctx.save_for_backward(lv, out, field)
+        else:
+            out = K.upsample_wce_fwd(lv, labels, weights, per_image, inv_temp)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gs = g.reshape(1).float().contiguous()
+        lv, out, field = ctx.saved_tensors
+        return nchw(K.upsample_wce_bwd_field(lv, ctx.hw, out, field, gs, ctx.per_image, ctx.inv_temp)), None, None, None, None, None
+
+
 class _MemRead(torch.autograd.Function):
     """memory.py:317-336. Returns (qr [B,2d,h,w], score [B,h,w,m], p_mem [B,h,w,m])."""
 
@@ -822,6 +845,30 @@ def upsample_ce(logits, labels, inv_temp=1.0):
         full = resize(logits, tuple(labels.shape[1:]))
         return torch.nn.functional.cross_entropy(full * float(inv_temp), labels, ignore_index=255, reduction='mean')
     return _UpsampleCE.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
+
+
+def weighted_ce(full, labels, weights, per_image):
+    """The weighted loss of upsample_wce on materialised logits, composed from torch ops (no host sync): the route of shapes the fused kernels do not take."""
+    lp = torch.nn.functional.log_softmax(full, dim=1)
+    weights = weights.to(device=full.device, dtype=lp.dtype)
+    if weights.dim() == 1 and not per_image:
+        return torch.nn.functional.nll_loss(lp, labels, weight=weights, ignore_index=255, reduction='mean')
+    rows = weights.expand(full.shape[0], -1) if weights.dim() == 1 else weights
+    num = [torch.nn.functional.nll_loss(lp[b:b + 1], labels[b:b + 1], weight=rows[b], ignore_index=255, reduction='sum') for b in range(full.shape[0])]
+    valid = (labels >= 0) & (labels < full.shape[1])
+    den = [torch.where(valid[b], rows[b][labels[b].clamp(0, full.shape[1] - 1)], lp.new_zeros(())).sum() for b in range(full.shape[0])]
+    if per_image:
+        return sum(nu / de for nu, de in zip(num, den))
+    return sum(num) / sum(den)
+
+
+def upsample_wce(logits, labels, weights, per_image, inv_temp=1.0):
+    """Weighted cross entropy (ignore_index 255) of the bilinearly up-sampled logits, logits never materialised. weights: [C], or [n, C] rows per image (for the
+    image-based criterion: K.label_class_weights). per_image False: sum w nll / sum w over the batch; True: the sum over images of each image's weighted mean."""
+    per_image = bool(per_image)
+    if not K.upsample_ce_fused_ok(nhwc(logits), tuple(labels.shape[1:])):      # as upsample_ce: rows too wide for the fused kernels' LDS
+        return weighted_ce(resize(logits, tuple(labels.shape[1:])) * float(inv_temp), labels, weights, per_image)
+    return _UpsampleWCE.apply(logits, labels, weights.detach(), per_image, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
 
 
 def mem_read(x, mem, noise=None):

@@ -9,6 +9,7 @@ from . import Resnet, memory
 from .mynn import Norm2d, Upsample, channels_last_weights, initialize_weights
 from ..hip import kernels as K
 from ..hip import ops
+from .. import loss as _loss
 
 
 def _cbr(cin, cout, k, **kw):
@@ -25,11 +26,29 @@ def fused_ce_ok(criterion):
             and criterion.weight is None and getattr(criterion, 'label_smoothing', 0.0) == 0.0)
 
 
+def _plain_nll(c):
+    """ignore 255, mean reduction, no label smoothing: the form the fused kernels compute."""
+    return c.ignore_index == 255 and getattr(c, 'reduction', 'mean') == 'mean' and getattr(c, 'label_smoothing', 0.0) == 0.0 and getattr(c, 'size_average', True) in (None, True)
+
+
+def fused_wce_weights(criterion, labels):
+    """(weights, per_image) when `criterion` is one of the weighted forms the fused kernels serve (ops.upsample_wce), else None: nn.CrossEntropyLoss(weight) and
+    loss.CrossEntropyLoss2d(weight) (loss.py:20-43,71-88,167-180), loss.ImageBasedCrossEntropyLoss2d (:120-163; its weight rows come from the labels on the device)."""
+    if isinstance(criterion, _loss.ImageBasedCrossEntropyLoss2d):
+        return (criterion.class_weights(labels), True) if _plain_nll(criterion) else None
+    if isinstance(criterion, (nn.CrossEntropyLoss, _loss.CrossEntropyLoss2d)) and _plain_nll(criterion) and criterion.weight is not None:
+        return criterion.weight, False
+    return None
+
+
 def segmentation_loss(criterion, logits, labels, size=None):
-    """criterion(Upsample(logits, size), labels) (deepv3plus.py:575-578). For the reference's own criterion
-    (loss.py:38-39: CrossEntropyLoss(mean, ignore_index=255)) the up-sampled logits are never materialised."""
-    if fused_ce_ok(criterion):
+    """criterion(Upsample(logits, size), labels) (deepv3plus.py:575-578). For the reference's own criteria -- CrossEntropyLoss(mean, ignore_index=255) with or
+    without class weights, CrossEntropyLoss2d, ImageBasedCrossEntropyLoss2d (loss.py:14-88,120-180) -- the up-sampled logits are never materialised."""
+    if fused_ce_ok(criterion) or (isinstance(criterion, _loss.CrossEntropyLoss2d) and _plain_nll(criterion) and criterion.weight is None):
         return ops.upsample_ce(logits, labels)
+    weighted = fused_wce_weights(criterion, labels)
+    if weighted is not None:
+        return ops.upsample_wce(logits, labels, weighted[0], weighted[1])
     full = logits if size is None else Upsample(logits, size)
     return criterion(full, labels)
 
