@@ -124,6 +124,13 @@ int pm_conv_fwd(const pm_tensor* x, const float* w_krsc, const pm_tensor* y, con
  * identity/downsample branch of a Bottleneck (Resnet.py:207). */
 int pm_conv_bwd_data(const pm_tensor* dy, const float* w_krsc, const pm_tensor* dx, const pm_conv_params* p,
                      const pm_tensor* add, void* ws, size_t ws_bytes, void* stream);
+/* The same with a MASKED add: dx = dgrad(dy) + (bit ? add : 0). add_mask (NULL: exactly the call above) holds one byte per float4 channel group of dx, dense
+ * [pixels][c / 4], bit e = element e of the group is added -- the bytes pm_bn_apply_mask leaves behind, so the skip gradient of a Bottleneck tail is passed on as
+ * (incoming gradient, ReLU bytes) and its masked copy is never stored. fp32 tensors; same plan and workspace as the unmasked call (pm_conv_workspace(.., 1)).
+ * Served where the call routes to the fp32 implicit-GEMM kernels (every stride-1 1x1 data gradient: streaming pointwise kernel, tile epilogue, split-K reduce);
+ * a call that routes to Winograd, the stride-2 class kernels or the bf16 tier returns PM_EUNSUPPORTED -- the mask is never dropped. */
+int pm_conv_bwd_data_masked(const pm_tensor* dy, const float* w_krsc, const pm_tensor* dx, const pm_conv_params* p,
+                            const pm_tensor* add, const uint8_t* add_mask, void* ws, size_t ws_bytes, void* stream);
 /* dw_krsc [Cout][kh][kw][Cin]; dbias [Cout] or NULL. Deterministic (split-K partials reduced in fixed order). */
 int pm_conv_bwd_weight(const pm_tensor* x, const pm_tensor* dy, float* dw_krsc, float* dbias, const pm_conv_params* p,
                        void* ws, size_t ws_bytes, void* stream);
@@ -233,6 +240,17 @@ int pm_bn_apply_mask(const pm_tensor* x, const float* mean, const float* invstd,
                      const pm_tensor* residual /*nullable*/, int relu, const pm_tensor* y, uint8_t* mask /*nullable*/, void* stream);
 int pm_bn_bwd_reduce_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd,
                           const pm_tensor* gmask /*nullable*/, float* sums, void* ws, size_t ws_bytes, void* stream);
+/* pm_bn_apply_mask whose residual is the BatchNorm output of a second raw tensor r (same shape), (r-r_mean)*r_invstd*r_gamma + r_beta, evaluated in the launch
+ * with the arithmetic pm_bn_apply would have stored -- bit-identical to the two-launch form, and the normalised residual (the downsample branch of a stage's
+ * first Bottleneck, Resnet.py:207-216) is never written. fp32 tensors only. */
+int pm_bn_apply_mask_affine(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                            const pm_tensor* r, const float* r_mean, const float* r_invstd, const float* r_gamma, const float* r_beta,
+                            int relu, const pm_tensor* y, uint8_t* mask /*nullable*/, void* stream);
+/* pm_bn_bwd_apply (below) on dyz = dy masked by those bytes, for ANY x of the mask's shape with its own statistics: together with
+ * pm_bn_bwd_reduce_mask(gmask = NULL) the backward of BN + residual + ReLU -- and of the downsample BatchNorm behind it -- without a stored masked gradient.
+ * Bit-identical to pm_bn_bwd_apply(dy = gmask, relu = 0). fp32 tensors only. */
+int pm_bn_bwd_apply_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                         const float* sums, float count, const pm_tensor* dx, void* stream);
 /* backward: dyz = dy * mask, sums[2*C] = sum(dyz) | sum(dyz * xhat).  relu: 0 no activation (mask = 1); 1 mask = y > 0 read from the
  * forward output (BN + residual + ReLU, Resnet.py:207-216); 2 mask rebuilt from x with gamma / beta (BN + ReLU without a residual:
  * one tensor less to read).  gmask (nullable, relu != 0): dyz is also stored there -- it is the gradient of the residual branch, and
@@ -274,6 +292,17 @@ int pm_cast(const pm_tensor* x, const pm_tensor* y, void* stream);
 /* ---- K3 pooling (Resnet.py:432 MaxPool2d(3,2,1); deepv3plus.py:85 AdaptiveAvgPool2d(1)) ------------------------- */
 int pm_maxpool3x3s2_fwd(const pm_tensor* x, const pm_tensor* y, uint8_t* argmax, void* stream);
 int pm_maxpool3x3s2_bwd(const pm_tensor* dy, const uint8_t* argmax, const pm_tensor* dx, void* stream);
+/* The stem tail (Resnet.py:471-478: conv -> BN -> ReLU -> max pool) without its full-resolution activation and gradient; fp32, c % 4 == 0.
+ * Forward: pm_maxpool3x3s2_fwd of relu(bn(x)), x the raw convolution output -- each tap is normalised and clamped before the comparison, so y and argmax (ties
+ * among clamped zeros included) are those of pooling the stored activation.
+ * Backward: pm_bn_bwd_reduce / pm_bn_bwd_apply with relu = 2 whose incoming gradient is pm_maxpool3x3s2_bwd(dy_pooled, argmax), gathered per pixel inside the
+ * pass instead of read from a tensor. Bit-identical to the separate kernels; workspace of pm_bn_workspace(x); count as pm_bn_bwd_apply. */
+int pm_maxpool3x3s2_bn_relu_fwd(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* y,
+                                uint8_t* argmax, void* stream);
+int pm_bn_bwd_reduce_pool(const pm_tensor* dy_pooled, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                          const float* beta, float* sums, void* ws, size_t ws_bytes, void* stream);
+int pm_bn_bwd_apply_pool(const pm_tensor* dy_pooled, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                         const float* beta, const float* sums, float count, const pm_tensor* dx, void* stream);
 int pm_global_avgpool_fwd(const pm_tensor* x, const pm_tensor* y /*n,1,1,c*/, void* stream);
 int pm_global_avgpool_bwd(const pm_tensor* dy, const pm_tensor* dx, int accumulate, void* stream);
 

@@ -12,10 +12,7 @@ constexpr int RL = 16;    // row lanes per block (256 threads = 16 float4 groups
 
 // y = (x - mean) * invstd * gamma + beta, evaluated the same way in the forward pass and wherever the backward pass rebuilds the
 // ReLU mask from x (two explicit FMAs: bit-identical in both places whatever the compiler would contract).
-__device__ __forceinline__ float bn_affine(float v, float mu, float is, float ga, float be) {
-  const float s = is * ga;
-  return fmaf(v, s, fmaf(-mu, s, be));
-}
+__device__ __forceinline__ float bn_affine(float v, float mu, float is, float ga, float be) { return pm_bn_affine(v, mu, is, ga, be); }
 
 inline int chunk_rows(long P, int C) {  // pixels per block: >= 2048 blocks over (pixel chunks x 64-channel groups), >= 64 rows each
   const long colblocks = std::max<long>(1, (C + CB - 1) / CB);
@@ -204,6 +201,41 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
     if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
   }
 }
+// bn_bwd_partial<2, false> whose incoming gradient is not a tensor: dy of pixel p is gathered from the gradient of the 3x3 / s2 max pool that followed the activation
+// (pm_maxpool_gather4: the values pm_maxpool3x3s2_bwd would have stored, in the same order), so the full-resolution gradient is never written. Same accumulation order.
+__global__ __launch_bounds__(256) void bn_bwd_partial_pool(const float* __restrict__ dyp, long dpitch, int Ho, int Wo, const uint8_t* __restrict__ arg, int H, int W,
+                                                           const float* __restrict__ x, long xpitch, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, long P, int C, int rows,
+                                                           float* __restrict__ part) {
+  __shared__ float sm[RL][CB][2];
+  const int g = threadIdx.x & 15, r = threadIdx.x >> 4;
+  const int c = blockIdx.y * CB + g * 4;
+  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
+  float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  if (c < C) {
+    const float4 mu = PM_LD4(mean + c), is = PM_LD4(invstd + c), ga = PM_LD4(gamma + c), be = PM_LD4(beta + c);
+    for (long p = p0 + r; p < p1; p += RL) {
+      float4 d = pm_maxpool_gather4(dyp, dpitch, Ho, Wo, arg, H, W, C, p, c);
+      const float4 v = PM_LD4(x + p * xpitch + c);
+      d.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? d.x : 0.f, d.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? d.y : 0.f;
+      d.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? d.z : 0.f, d.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? d.w : 0.f;
+      s1[0] += d.x, s1[1] += d.y, s1[2] += d.z, s1[3] += d.w;
+      s2[0] += d.x * ((v.x - mu.x) * is.x), s2[1] += d.y * ((v.y - mu.y) * is.y);
+      s2[2] += d.z * ((v.z - mu.z) * is.z), s2[3] += d.w * ((v.w - mu.w) * is.w);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sm[r][g * 4 + j][0] = s1[j], sm[r][g * 4 + j][1] = s2[j];
+  __syncthreads();
+  if (threadIdx.x < CB * 2) {
+    const int cc = threadIdx.x >> 1, w = threadIdx.x & 1;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < RL; ++i) s += sm[i][cc][w];
+    const int ch = blockIdx.y * CB + cc;
+    if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
+  }
+}
 __global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ part, int nb, int C, float* __restrict__ sums) {
   const int c = blockIdx.x * FC + (threadIdx.x & (FC - 1)), lane = threadIdx.x / FC;
   double s1, s2;
@@ -372,6 +404,37 @@ extern "C" int pm_bn_apply(const pm_tensor* x, const float* mean, const float* i
   return pm_bn_apply_mask(x, mean, invstd, gamma, beta, res, relu, y, nullptr, stream);
 }
 
+namespace {
+
+// RAFF: the residual is itself a BatchNorm output that was never stored -- bn_affine(r, ...) of the raw tensor r with its own (mean, invstd, gamma, beta),
+// the two FMAs pm_bn_apply would have evaluated before storing it (an fp32 store and reload is lossless: same bits), added exactly where a stored residual is.
+template <bool RAFF>
+int bn_apply_launch(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res, const float* rmean,
+                    const float* rinvstd, const float* rgamma, const float* rbeta, int relu, const pm_tensor* y, uint8_t* mask, hipStream_t stream) {
+  const float *px = (const float*)x->ptr, *pr = res ? (const float*)res->ptr : nullptr;
+  float* py = (float*)y->ptr;
+  const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, cq = x->c >> 2;
+  return pm_ew_launch(true, pm_pixels(x), x->c, stream, "bn_apply", [=] __device__(long p, int ch) {
+    const float4 v = PM_LD4(px + p * a + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
+    float4 o = make_float4(bn_affine(v.x, mu.x, is.x, ga.x, be.x), bn_affine(v.y, mu.y, is.y, ga.y, be.y), bn_affine(v.z, mu.z, is.z, ga.z, be.z),
+                           bn_affine(v.w, mu.w, is.w, ga.w, be.w));
+    if (pr) {
+      float4 q = PM_LD4(pr + p * b + ch);
+      if constexpr (RAFF) {
+        const float4 rm = PM_LD4(rmean + ch), ri = PM_LD4(rinvstd + ch), rg = PM_LD4(rgamma + ch), rb = PM_LD4(rbeta + ch);
+        q = make_float4(bn_affine(q.x, rm.x, ri.x, rg.x, rb.x), bn_affine(q.y, rm.y, ri.y, rg.y, rb.y), bn_affine(q.z, rm.z, ri.z, rg.z, rb.z),
+                        bn_affine(q.w, rm.w, ri.w, rg.w, rb.w));
+      }
+      o.x += q.x, o.y += q.y, o.z += q.z, o.w += q.w;
+    }
+    if (mask) mask[p * cq + (ch >> 2)] = (unsigned char)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
+    if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
+    PM_ST4(py + p * c + ch, o);
+  });
+}
+
+}  // namespace
+
 extern "C" int pm_bn_apply_mask(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res,
                                 int relu, const pm_tensor* y, uint8_t* mask, void* stream) {
   PM_REQUIRE(x && y, PM_EINVAL, "bn_apply: null");
@@ -383,21 +446,20 @@ extern "C" int pm_bn_apply_mask(const pm_tensor* x, const float* mean, const flo
     if (int e = check_bn(res, "bn_apply")) return e;
     PM_REQUIRE(pm_same_shape(x, res), PM_EINVAL, "bn_apply: residual shape mismatch");
   }
-  const float *px = (const float*)x->ptr, *pr = res ? (const float*)res->ptr : nullptr;
-  float* py = (float*)y->ptr;
-  const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, cq = x->c >> 2;
-  return pm_ew_launch(true, pm_pixels(x), x->c, (hipStream_t)stream, "bn_apply", [=] __device__(long p, int ch) {
-    const float4 v = PM_LD4(px + p * a + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
-    float4 o = make_float4(bn_affine(v.x, mu.x, is.x, ga.x, be.x), bn_affine(v.y, mu.y, is.y, ga.y, be.y), bn_affine(v.z, mu.z, is.z, ga.z, be.z),
-                           bn_affine(v.w, mu.w, is.w, ga.w, be.w));
-    if (pr) {
-      const float4 q = PM_LD4(pr + p * b + ch);
-      o.x += q.x, o.y += q.y, o.z += q.z, o.w += q.w;
-    }
-    if (mask) mask[p * cq + (ch >> 2)] = (unsigned char)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
-    if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
-    PM_ST4(py + p * c + ch, o);
-  });
+  return bn_apply_launch<false>(x, mean, invstd, gamma, beta, res, nullptr, nullptr, nullptr, nullptr, relu, y, mask, (hipStream_t)stream);
+}
+
+// pm_bn_apply_mask whose residual is bn(r) of a second raw tensor (the downsample branch of a stage's first Bottleneck): the normalised residual is never stored.
+extern "C" int pm_bn_apply_mask_affine(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* r,
+                                       const float* r_mean, const float* r_invstd, const float* r_gamma, const float* r_beta, int relu, const pm_tensor* y,
+                                       uint8_t* mask, void* stream) {
+  PM_REQUIRE(x && y && r, PM_EINVAL, "bn_apply_mask_affine: null");
+  if (int e = check_bn(x, "bn_apply_mask_affine")) return e;      // fp32 only: the bf16 tier stores its normalised residual
+  if (int e = check_bn(y, "bn_apply_mask_affine")) return e;
+  if (int e = check_bn(r, "bn_apply_mask_affine")) return e;
+  PM_REQUIRE(pm_same_shape(x, y) && pm_same_shape(x, r) && mean && invstd && gamma && beta && r_mean && r_invstd && r_gamma && r_beta, PM_EINVAL,
+             "bn_apply_mask_affine: bad args");
+  return bn_apply_launch<true>(x, mean, invstd, gamma, beta, r, r_mean, r_invstd, r_gamma, r_beta, relu, y, mask, (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_bwd_reduce(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
@@ -496,6 +558,94 @@ extern "C" int pm_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y, const pm
       g.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f, g.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
     }
     if (pdr) PM_ST4(pdr + p * e2 + ch, g);
+    const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
+    float4 r;
+    r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);
+    r.y = (g.y - s1.y * inv_n - (v.y - mu.y) * is.y * (s2.y * inv_n)) * (is.y * ga.y);
+    r.z = (g.z - s1.z * inv_n - (v.z - mu.z) * is.z * (s2.z * inv_n)) * (is.z * ga.z);
+    r.w = (g.w - s1.w * inv_n - (v.w - mu.w) * is.w * (s2.w * inv_n)) * (is.w * ga.w);
+    PM_ST4(pdx + p * d + ch, r);
+  });
+}
+
+// pm_bn_bwd_apply on dyz = dy masked by pm_bn_apply_mask's bytes (bit e of byte [pixel][ch / 4]: the ReLU passed element e), for ANY x of that shape: the BatchNorm the
+// mask came from, or the downsample BatchNorm whose output was that activation's residual. Same arithmetic as pm_bn_bwd_apply(relu = 0) on the stored masked
+// gradient, which therefore need not exist.
+extern "C" int pm_bn_bwd_apply_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                                    const float* sums, float count, const pm_tensor* dx, void* stream) {
+  PM_REQUIRE(dy && x && dx && mask, PM_EINVAL, "bn_bwd_apply_mask: null");
+  if (int e = check_bn(dy, "bn_bwd_apply_mask")) return e;
+  if (int e = check_bn(x, "bn_bwd_apply_mask")) return e;
+  if (int e = check_bn(dx, "bn_bwd_apply_mask")) return e;
+  PM_REQUIRE(pm_same_shape(dy, x) && pm_same_shape(dx, x) && mean && invstd && gamma && sums, PM_EINVAL, "bn_bwd_apply_mask: bad args");
+  const float *pd = (const float*)dy->ptr, *px = (const float*)x->ptr;
+  float* pdx = (float*)dx->ptr;
+  const long a = dy->pitch, c = x->pitch, d = dx->pitch;
+  const int C = x->c, cq = C >> 2;
+  const bool dev_count = !(count > 0.f);      // as pm_bn_bwd_apply: the global count at sums[2 * C]
+  const float host_inv_n = dev_count ? 0.f : 1.f / count;
+  return pm_ew_launch(true, pm_pixels(x), C, (hipStream_t)stream, "bn_bwd_apply_mask", [=] __device__(long p, int ch) {
+    const float inv_n = dev_count ? 1.f / sums[2 * C] : host_inv_n;
+    float4 g = PM_LD4(pd + p * a + ch);
+    const unsigned mb = mask[p * cq + (ch >> 2)];
+    g.x = (mb & 1u) ? g.x : 0.f, g.y = (mb & 2u) ? g.y : 0.f, g.z = (mb & 4u) ? g.z : 0.f, g.w = (mb & 8u) ? g.w : 0.f;
+    const float4 v = PM_LD4(px + p * c + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch);
+    const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
+    float4 r;
+    r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);
+    r.y = (g.y - s1.y * inv_n - (v.y - mu.y) * is.y * (s2.y * inv_n)) * (is.y * ga.y);
+    r.z = (g.z - s1.z * inv_n - (v.z - mu.z) * is.z * (s2.z * inv_n)) * (is.z * ga.z);
+    r.w = (g.w - s1.w * inv_n - (v.w - mu.w) * is.w * (s2.w * inv_n)) * (is.w * ga.w);
+    PM_ST4(pdx + p * d + ch, r);
+  });
+}
+
+// ---- the stem's BN + ReLU backward behind a 3x3 / s2 max pool, straight from the pooled gradient ------------------------------------------------------------------
+// pm_bn_bwd_reduce / pm_bn_bwd_apply with relu = 2 (mask rebuilt from x) where dy is what pm_maxpool3x3s2_bwd(dyp, argmax) would have written: each pass gathers
+// it per pixel from the pooled gradient and the argmax bytes (a quarter of the pixels), so neither the full-resolution activation nor its gradient exists.
+namespace {
+int check_pool_bn(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const char* who) {
+  PM_REQUIRE(dyp && argmax && x, PM_EINVAL, "%s: null", who);
+  if (int e = check_bn(dyp, who)) return e;
+  if (int e = check_bn(x, who)) return e;
+  PM_REQUIRE(dyp->n == x->n && dyp->c == x->c && dyp->h == (x->h + 2 - 3) / 2 + 1 && dyp->w == (x->w + 2 - 3) / 2 + 1, PM_EINVAL,
+             "%s: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x", who);
+  return PM_OK;
+}
+}  // namespace
+
+extern "C" int pm_bn_bwd_reduce_pool(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                                     const float* beta, float* sums, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = check_pool_bn(dyp, argmax, x, "bn_bwd_reduce_pool")) return e;
+  PM_REQUIRE(mean && invstd && gamma && beta && sums, PM_EINVAL, "bn_bwd_reduce_pool: bad args");
+  PM_REQUIRE(ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_bwd_reduce_pool: workspace too small");
+  const long P = pm_pixels(x);
+  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(bn_bwd_partial_pool, dim3(nb, pm_cdiv(x->c, CB)), dim3(256), 0, st, (const float*)dyp->ptr, (long)dyp->pitch, dyp->h, dyp->w, argmax, x->h, x->w,
+                     (const float*)x->ptr, (long)x->pitch, mean, invstd, gamma, beta, P, x->c, rows, (float*)ws);
+  hipLaunchKernelGGL(bn_bwd_final, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, x->c, sums);
+  return pm_check_launch("bn_bwd_reduce_pool");
+}
+
+extern "C" int pm_bn_bwd_apply_pool(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                                    const float* beta, const float* sums, float count, const pm_tensor* dx, void* stream) {
+  if (int e = check_pool_bn(dyp, argmax, x, "bn_bwd_apply_pool")) return e;
+  PM_REQUIRE(dx, PM_EINVAL, "bn_bwd_apply_pool: null");
+  if (int e = check_bn(dx, "bn_bwd_apply_pool")) return e;
+  PM_REQUIRE(pm_same_shape(dx, x) && mean && invstd && gamma && beta && sums, PM_EINVAL, "bn_bwd_apply_pool: bad args");
+  const float *pd = (const float*)dyp->ptr, *px = (const float*)x->ptr;
+  float* pdx = (float*)dx->ptr;
+  const long a = dyp->pitch, c = x->pitch, d = dx->pitch;
+  const int C = x->c, H = x->h, W = x->w, Ho = dyp->h, Wo = dyp->w;
+  const bool dev_count = !(count > 0.f);      // as pm_bn_bwd_apply: the global count at sums[2 * C]
+  const float host_inv_n = dev_count ? 0.f : 1.f / count;
+  return pm_ew_launch(true, pm_pixels(x), C, (hipStream_t)stream, "bn_bwd_apply_pool", [=] __device__(long p, int ch) {
+    const float inv_n = dev_count ? 1.f / sums[2 * C] : host_inv_n;
+    float4 g = pm_maxpool_gather4(pd, a, Ho, Wo, argmax, H, W, C, p, ch);
+    const float4 v = PM_LD4(px + p * c + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
+    g.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f, g.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
+    g.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f, g.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
     const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
     float4 r;
     r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);

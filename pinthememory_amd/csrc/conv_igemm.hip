@@ -28,7 +28,7 @@ template <int ZL, bool O16 = false>
 __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __restrict__ ws, int ksplit, long slab, int M, int Nn,
                                                                 float* __restrict__ C, long c_pitch, const float* bias,
                                                                 const float* scale, const float* shift, const float* residual,
-                                                                long res_pitch, int relu) {
+                                                                long res_pitch, int relu, const unsigned char* res_mask) {
   constexpr int GP = 256 / ZL;   // output groups per block
   __shared__ float4 red[ZL > 1 ? ZL : 1][GP];
   const int gl = threadIdx.x % GP, zl = threadIdx.x / GP;
@@ -69,7 +69,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
           const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const pm_bf16*>(residual) + (long)row * res_pitch + col);
           v.x += __uint_as_float(q.x << 16), v.y += __uint_as_float(q.x & 0xffff0000u), v.z += __uint_as_float(q.y << 16), v.w += __uint_as_float(q.y & 0xffff0000u);
         } else {
-          const float4 r = PM_LD4(residual + (long)row * res_pitch + col);
+          float4 r = PM_LD4(residual + (long)row * res_pitch + col);
+          if (res_mask) {      // masked skip gradient (ConvK::res_mask): byte [row][col / 4], bit e = element e is added
+            const unsigned mb = res_mask[grp];
+            r.x = (mb & 1u) ? r.x : 0.f, r.y = (mb & 2u) ? r.y : 0.f, r.z = (mb & 4u) ? r.z : 0.f, r.w = (mb & 8u) ? r.w : 0.f;
+          }
           v.x += r.x, v.y += r.y, v.z += r.z, v.w += r.w;
         }
       }
@@ -99,8 +103,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 int splitk_reduce(const float* ws, int ksplit, long M, long Nn, float* C, long c_pitch, const float* bias, const float* scale, const float* shift,
-                  const float* residual, long res_pitch, int relu, hipStream_t st, bool out16 = false) {
+                  const float* residual, long res_pitch, int relu, hipStream_t st, bool out16 = false, const unsigned char* res_mask = nullptr) {
   const long total = M * Nn;
+  PM_REQUIRE(!res_mask || (residual && !out16), PM_EUNSUPPORTED, "splitk_reduce: a masked residual is an fp32 operand");
   if (out16) {      // bf16 tier: bf16 output / residual, four outputs = 8 bytes per thread
     PM_REQUIRE((Nn % 4 == 0) && (c_pitch % 4 == 0) && (res_pitch % 4 == 0) && pm_aligned16(ws) && (reinterpret_cast<uintptr_t>(C) & 7) == 0 &&
                    (reinterpret_cast<uintptr_t>(residual) & 7) == 0 && (!bias || pm_aligned16(bias)) && (!scale || (pm_aligned16(scale) && pm_aligned16(shift))),
@@ -109,16 +114,17 @@ int splitk_reduce(const float* ws, int ksplit, long M, long Nn, float* C, long c
     const int zl = (ksplit >= 32 && groups < (1 << 18)) ? 16 : (ksplit >= 8 && groups < (1 << 20) ? 4 : 1);
     const int nb = (int)std::min<long>((groups + 256 / zl - 1) / (256 / zl), 8192);
     if (zl == 16)
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<16, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL((splitk_reduce_vec_kernel<16, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
     else if (zl == 4)
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<4, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL((splitk_reduce_vec_kernel<4, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
     else
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<1, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL((splitk_reduce_vec_kernel<1, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
     return pm_check_launch("splitk_reduce(bf16)");
   }
   const bool vec = (Nn % 4 == 0) && (c_pitch % 4 == 0) && (res_pitch % 4 == 0) && pm_aligned16(ws) && pm_aligned16(C) &&
                    (!bias || pm_aligned16(bias)) && (!scale || (pm_aligned16(scale) && pm_aligned16(shift))) && (!residual || pm_aligned16(residual));
   if (!vec) {
+    PM_REQUIRE(!res_mask, PM_EUNSUPPORTED, "splitk_reduce: a masked residual needs 16-byte aligned rows");
     const int nb = (int)std::min<long>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual,
                        res_pitch, relu);
@@ -129,11 +135,11 @@ int splitk_reduce(const float* ws, int ksplit, long M, long Nn, float* C, long c
     const int gp = 256 / zl;
     const int nb = (int)std::min<long>((groups + gp - 1) / gp, 8192);
     if (zl == 16)
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<16>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL(splitk_reduce_vec_kernel<16>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
     else if (zl == 4)
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<4>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL(splitk_reduce_vec_kernel<4>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
     else
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<1>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu);
+      hipLaunchKernelGGL(splitk_reduce_vec_kernel<1>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
   }
   return pm_check_launch("splitk_reduce");
 }
@@ -426,7 +432,7 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   if constexpr (MODE != MODE_WGRAD) {      // short pointwise reductions of the fp32 tier stream wave by wave (pwstream.hip): the split path's arithmetic, no tiles
     if (pm_route.split && (k.prec == 0 || k.prec == 5) && !k.io16 && batch == 1 && p.ksplit == 1 && !k.stats && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) {      // fp32 operands only (prec 1 / 2: bf16-operand forms of the older tier)
       pm_gemm_pw g;
-      g.A = k.A, g.B = k.B, g.C = k.C, g.bias = k.bias, g.scale = k.scale, g.shift = k.shift, g.residual = k.residual;
+      g.A = k.A, g.B = k.B, g.C = k.C, g.bias = k.bias, g.scale = k.scale, g.shift = k.shift, g.residual = k.residual, g.res_mask = k.res_mask;
       g.a_pitch = MODE == MODE_FWD ? k.x_pitch : k.y_pitch, g.c_pitch = k.c_pitch, g.res_pitch = k.res_pitch;
       g.b_sn = MODE == MODE_FWD ? k.K : 1, g.b_sk = MODE == MODE_FWD ? 1 : k.Nn;
       g.M = k.M, g.Nn = k.Nn, g.K = k.K, g.relu = k.relu;
@@ -495,7 +501,7 @@ void fill_geom(ConvK& k, const pm_tensor* x, const pm_tensor* y, const pm_conv_p
   k.T_eff = p->kh * p->kw, k.tk_w = p->kw, k.ky0 = k.kx0 = 0, k.ksy = k.ksx = 1;
   k.sub = k.sub_cy = k.sub_cx = 0, k.Hc = x->h, k.Wc = x->w;
   k.bias = k.scale = k.shift = k.residual = nullptr;
-  k.res_pitch = 0, k.relu = 0, k.stats = nullptr, k.io16 = 0;
+  k.res_pitch = 0, k.res_mask = nullptr, k.relu = 0, k.stats = nullptr, k.io16 = 0;
   k.stage_ep = 1;      // staged epilogue; launch() turns it off for batched launches
   k.spl_prio = 1;      // PREC 5: the odd hardware wave slot at a raised priority (measured level; DESIGN.md, the split path)
   k.n_group = 8;       // N tiles walked in groups of eight columns (tile order: L2-miss traffic down, time level)
@@ -1099,7 +1105,9 @@ int dgrad_s2_parity(const pm_tensor* dy0, const float* w, const pm_tensor* dx, c
 
 // the implicit-GEMM kernel on fp32 rows, forward (MODE_FWD: xin = x, out = y) and stride-1 data gradient (MODE_DGRAD: xin = dy, out = dx; only e.residual is set)
 template <int MODE>
-int conv_direct(const pm_tensor* x, const pm_tensor* y, const float* w, const pm_conv_params* p, const Plan& pl, const pm_conv_epilogue& e, void* ws, hipStream_t st) {
+// res_mask: e.residual enters masked (ConvK::res_mask) -- every fp32 form of this worker decodes it: the streaming pointwise kernel, the staged tile epilogue, the split-K reduce
+int conv_direct(const pm_tensor* x, const pm_tensor* y, const float* w, const pm_conv_params* p, const Plan& pl, const pm_conv_epilogue& e, void* ws, hipStream_t st,
+                const unsigned char* res_mask = nullptr) {
   const pm_tensor *xin = MODE == MODE_FWD ? x : y, *out = MODE == MODE_FWD ? y : x;
   long M, Nn, K;
   gemm_dims(MODE, x, y, p, M, Nn, K);
@@ -1113,10 +1121,11 @@ int conv_direct(const pm_tensor* x, const pm_tensor* y, const float* w, const pm
   if (pl.ksplit > 1) {
     k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
     if (int err = launch<MODE>(k, pl, st)) return err;
-    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)out->ptr, (long)out->pitch, e.bias, e.scale, e.shift, e.residual, (long)e.residual_pitch, e.relu, st, k.io16 != 0);
+    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)out->ptr, (long)out->pitch, e.bias, e.scale, e.shift, e.residual, (long)e.residual_pitch, e.relu, st, k.io16 != 0,
+                         res_mask);
   }
   k.C = (float*)out->ptr, k.c_pitch = out->pitch, k.c_split = 0;
-  k.bias = e.bias, k.scale = e.scale, k.shift = e.shift, k.residual = e.residual, k.res_pitch = e.residual_pitch, k.relu = e.relu;
+  k.bias = e.bias, k.scale = e.scale, k.shift = e.shift, k.residual = e.residual, k.res_pitch = e.residual_pitch, k.res_mask = res_mask, k.relu = e.relu;
   k.stats = e.bn_partials;
   return launch<MODE>(k, pl, st);
 }
@@ -1366,6 +1375,14 @@ extern "C" int pm_conv_fwd(const pm_tensor* x, const float* w, const pm_tensor* 
 
 extern "C" int pm_conv_bwd_data(const pm_tensor* dy, const float* w, const pm_tensor* dx, const pm_conv_params* p0, const pm_tensor* add,
                                 void* ws, size_t ws_bytes, void* stream) {
+  return pm_conv_bwd_data_masked(dy, w, dx, p0, add, nullptr, ws, ws_bytes, stream);
+}
+
+// add_mask: `add` counts as (bit ? add : 0) per element, one byte per float4 group of dx, dense [pixels][c / 4] as pm_bn_apply_mask writes it -- dv and the ReLU bytes
+// of a Bottleneck tail in place of the stored masked gradient. Same plan and workspace as pm_conv_bwd_data. Served by the fp32 implicit-GEMM worker (streaming pointwise
+// kernel, staged tile epilogue, split-K reduce); a call routed anywhere else (Winograd, stride 2, the bf16 tier) is refused, never run unmasked.
+extern "C" int pm_conv_bwd_data_masked(const pm_tensor* dy, const float* w, const pm_tensor* dx, const pm_conv_params* p0, const pm_tensor* add,
+                                       const uint8_t* add_mask, void* ws, size_t ws_bytes, void* stream) {
   if (int e = check_common(dx, dy, p0)) return e;
   const pm_conv_params tp = tier_params(p0, dy, dx);
   const pm_conv_params* p = &tp;
@@ -1374,6 +1391,12 @@ extern "C" int pm_conv_bwd_data(const pm_tensor* dy, const float* w, const pm_te
   PM_REQUIRE(w && pm_aligned16(w), PM_EINVAL, "conv_bwd_data: weight null or unaligned");
   const ConvRoute r = route_conv(MODE_DGRAD, dx, dy, p);
   PM_REQUIRE(ws_bytes >= r.ws_bytes && (ws || r.ws_bytes == 0), PM_EWORKSPACE, "conv_bwd_data: workspace %zu < %zu", ws_bytes, r.ws_bytes);
+  if (add_mask) {
+    PM_REQUIRE(add && pm_is_f32(add) && pm_is_f32(dy) && pm_vec4(add) && pm_vec4(dx), PM_EINVAL, "conv_bwd_data: a masked `add` is an fp32 tensor with 16-byte rows and c %% 4 == 0");
+    PM_REQUIRE(r.kind == R_DIRECT, PM_EUNSUPPORTED,
+               "conv_bwd_data: a masked `add` is served by the fp32 implicit-GEMM route only (this call routes to %s)",
+               r.kind == R_WINO ? "Winograd" : (r.kind == R_BF16 ? "the bf16 kernels" : "the stride-2 class kernels"));
+  }
   hipStream_t st = (hipStream_t)stream;
   // the fused skip gradient rides as the residual of the forward-form workers
   const pm_conv_epilogue e1 = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, add ? (const float*)add->ptr : nullptr, add ? add->pitch : 0, 0};
@@ -1387,7 +1410,7 @@ extern "C" int pm_conv_bwd_data(const pm_tensor* dy, const float* w, const pm_te
     case R_WINO: return wino_conv(dy, w, dy->c, dx->c, true, dx, r.wino, e1, ws, st);
     default:
       PM_REQUIRE(pm_is_f32(dy), PM_EUNSUPPORTED, "conv_bwd_data: a bf16 dy needs at least 32 channels and a stride-1 geometry the forward form covers");
-      return conv_direct<MODE_DGRAD>(dx, dy, w, p, r.pl, e1, ws, st);
+      return conv_direct<MODE_DGRAD>(dx, dy, w, p, r.pl, e1, ws, st, add_mask);
   }
 }
 

@@ -37,6 +37,8 @@ struct ConvK {
   const float* shift;
   const float* residual;
   long res_pitch;
+  const unsigned char* res_mask;   // data gradient, fp32 staged epilogue only, or null: `residual` enters masked -- one byte per float4 group of C, dense [M][Nn / 4] (pm_bn_apply_mask's
+                                   // layout), bit e set = element e of the group is added, clear = it counts as 0 (the skip gradient behind a ReLU, never stored masked)
   int relu;
   float* stats;               // train-mode BN statistics of the output: (mean, M2) per 32-row slab and channel, or null
   int io16;                   // the bf16 tier: C and `residual` are bf16 tensors (pitches in elements); accumulation and the epilogue arithmetic stay fp32
@@ -938,7 +940,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
         if (row < a.M && cok) {
           if (aff) v.x = (v.x + bi[0]) * sc[0] + sh[0], v.y = (v.y + bi[1]) * sc[1] + sh[1], v.z = (v.z + bi[2]) * sc[2] + sh[2], v.w = (v.w + bi[3]) * sc[3] + sh[3];
           if (res) {
-            const float4 qv = PM_LD4(a.residual + row * a.res_pitch + col);
+            float4 qv = PM_LD4(a.residual + row * a.res_pitch + col);
+            if constexpr (MODE == MODE_DGRAD) if (a.res_mask) {      // (data gradients only: the forward instantiations keep their register allocation)
+              const unsigned mb = a.res_mask[row * (a.Nn >> 2) + (col >> 2)];
+              qv.x = (mb & 1u) ? qv.x : 0.f, qv.y = (mb & 2u) ? qv.y : 0.f, qv.z = (mb & 4u) ? qv.z : 0.f, qv.w = (mb & 8u) ? qv.w : 0.f;
+            }
             v.x += qv.x, v.y += qv.y, v.z += qv.z, v.w += qv.w;
           }
           if (relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);

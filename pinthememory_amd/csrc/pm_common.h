@@ -144,6 +144,7 @@ struct pm_gemm_pw {
   const float* B;            // element (n, k) at B[n * b_sn + k * b_sk]
   float* C;                  // rows of Nn floats, c_pitch floats apart
   const float *bias, *scale, *shift, *residual;      // v = (acc + bias) * scale + shift (+ residual) (relu): the tile kernels' epilogue
+  const unsigned char* res_mask;                     // null, or residual enters masked: byte [row][col / 4] of a dense [M][Nn / 4] array, bit e = element e is added
   long a_pitch, c_pitch, res_pitch;
   int b_sn, b_sk;
   long M;
@@ -256,6 +257,39 @@ __device__ __forceinline__ void pm_slab_stats16(const float* Ws, int rr0, int cc
 #pragma unroll
     for (int e = 0; e < 8; e += 2) *reinterpret_cast<float4*>(dst + 2 * e) = make_float4(mu[e], m2[e], mu[e + 1], m2[e + 1]);
   }
+}
+
+// BatchNorm's y = (x - mean) * invstd * gamma + beta, evaluated the same way wherever it appears -- the apply pass, every backward pass that rebuilds the ReLU mask
+// from x, the max pool that normalises its taps itself (two explicit FMAs: bit-identical in all of them whatever the compiler would contract).
+__device__ __forceinline__ float pm_bn_affine(float v, float mu, float is, float ga, float be) {
+  const float s = is * ga;
+  return fmaf(v, s, fmaf(-mu, s, be));
+}
+
+// Gradient of input pixel ip (channels ch ... ch + 3) of a 3x3 / stride 2 / pad 1 max pool: the sum, in window order, of dy over the (at most four) windows that
+// cover the pixel and whose argmax byte names this tap. A gather: no atomics, deterministic. Shared by the pool's own backward and by the BatchNorm backward passes
+// that read a pooled gradient (the stem), so both produce the same bits.
+__device__ __forceinline__ float4 pm_maxpool_gather4(const float* __restrict__ dy, long dp, int Ho, int Wo, const uint8_t* __restrict__ arg, int H, int W, int C, long ip,
+                                                     int ch) {
+  const int ix = (int)(ip % W), iy = (int)((ip / W) % H), n = (int)(ip / ((long)W * H));
+  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int oy_hi = min((iy + 1) >> 1, Ho - 1), ox_hi = min((ix + 1) >> 1, Wo - 1);
+  for (int oy = iy >> 1; oy <= oy_hi; ++oy) {
+    const int ky = iy + 1 - 2 * oy;
+    if (ky < 0 || ky > 2) continue;
+    for (int ox = ix >> 1; ox <= ox_hi; ++ox) {
+      const int kx = ix + 1 - 2 * ox;
+      if (kx < 0 || kx > 2) continue;
+      const long op = (long)(n * Ho + oy) * Wo + ox;
+      const unsigned a = *reinterpret_cast<const unsigned*>(arg + op * C + ch), want = (unsigned)(ky * 3 + kx);
+      const float4 d = *reinterpret_cast<const float4*>(dy + op * dp + ch);
+      g.x += (a & 255u) == want ? d.x : 0.f;
+      g.y += ((a >> 8) & 255u) == want ? d.y : 0.f;
+      g.z += ((a >> 16) & 255u) == want ? d.z : 0.f;
+      g.w += (a >> 24) == want ? d.w : 0.f;
+    }
+  }
+  return g;
 }
 
 __device__ __forceinline__ float pm_wave_sum(float v) {

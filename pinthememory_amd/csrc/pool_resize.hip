@@ -6,9 +6,14 @@
 namespace {
 
 // ---------------- max pool ------------------------------------------------------------------------------------
-template <bool VEC>
+// BN (VEC only): x is a raw convolution output and every tap is relu(bn(x)) -- normalised and clamped BEFORE the comparison, so values, argmax bytes and the ties
+// among clamped zeros are those of pooling the stored activation, which is never written (the stem, Resnet.py:471-478).
+template <bool VEC, bool BN = false>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, long xp, int H, int W, float* __restrict__ y, long yp, int Ho,
-                                                          int Wo, int C, long total, uint8_t* __restrict__ arg) {
+                                                          int Wo, int C, long total, uint8_t* __restrict__ arg, const float* __restrict__ mean = nullptr,
+                                                          const float* __restrict__ invstd = nullptr, const float* __restrict__ gamma = nullptr,
+                                                          const float* __restrict__ beta = nullptr) {
+  static_assert(VEC || !BN, "the normalising form is vectorised");
   constexpr int V = VEC ? 4 : 1;
   const int cg = C / V;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -19,6 +24,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
     uint8_t bi[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) best[v] = -INFINITY, bi[v] = 0;
+    float4 mu, is, ga, be;
+    if constexpr (BN) mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
     bool first = true;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
@@ -34,6 +41,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
           const float4 q = PM_LD4(p);
           v[0] = q.x;
           if (V > 1) v[1 % V] = q.y, v[2 % V] = q.z, v[3 % V] = q.w;
+          if constexpr (BN) {
+            v[0] = fmaxf(pm_bn_affine(v[0], mu.x, is.x, ga.x, be.x), 0.f), v[1 % V] = fmaxf(pm_bn_affine(v[1 % V], mu.y, is.y, ga.y, be.y), 0.f);
+            v[2 % V] = fmaxf(pm_bn_affine(v[2 % V], mu.z, is.z, ga.z, be.z), 0.f), v[3 % V] = fmaxf(pm_bn_affine(v[3 % V], mu.w, is.w, ga.w, be.w), 0.f);
+          }
         } else {
           v[0] = *p;
         }
@@ -57,24 +68,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_vec_kernel(const float* __res
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long ip = i / cg;
     const int ch = (int)(i - ip * cg) * 4;
-    const int ix = (int)(ip % W), iy = (int)((ip / W) % H), n = (int)(ip / ((long)W * H));
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int oy_hi = min((iy + 1) >> 1, Ho - 1), ox_hi = min((ix + 1) >> 1, Wo - 1);
-    for (int oy = iy >> 1; oy <= oy_hi; ++oy) {
-      const int ky = iy + 1 - 2 * oy;
-      if (ky < 0 || ky > 2) continue;
-      for (int ox = ix >> 1; ox <= ox_hi; ++ox) {
-        const int kx = ix + 1 - 2 * ox;
-        if (kx < 0 || kx > 2) continue;
-        const long op = (long)(n * Ho + oy) * Wo + ox;
-        const unsigned a = *reinterpret_cast<const unsigned*>(arg + op * C + ch), want = (unsigned)(ky * 3 + kx);
-        const float4 d = PM_LD4(dy + op * dp + ch);
-        g.x += (a & 255u) == want ? d.x : 0.f;
-        g.y += ((a >> 8) & 255u) == want ? d.y : 0.f;
-        g.z += ((a >> 16) & 255u) == want ? d.z : 0.f;
-        g.w += (a >> 24) == want ? d.w : 0.f;
-      }
-    }
+    const float4 g = pm_maxpool_gather4(dy, dp, Ho, Wo, arg, H, W, C, ip, ch);
     PM_ST4(dx + ip * xp + ch, g);
   }
 }
@@ -375,6 +369,20 @@ extern "C" int pm_maxpool3x3s2_fwd(const pm_tensor* x, const pm_tensor* y, uint8
     hipLaunchKernelGGL(maxpool_fwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x->ptr, (long)x->pitch, x->h, x->w,
                        (float*)y->ptr, (long)y->pitch, y->h, y->w, y->c, total, argmax);
   return pm_check_launch("maxpool_fwd");
+}
+
+// pm_maxpool3x3s2_fwd of relu(bn(x)) for a raw convolution output x: the normalised activation is evaluated per tap and never stored. fp32, c % 4 == 0.
+extern "C" int pm_maxpool3x3s2_bn_relu_fwd(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* y,
+                                           uint8_t* argmax, void* stream) {
+  PM_REQUIRE(x && y && argmax && x->ptr && y->ptr && mean && invstd && gamma && beta, PM_EINVAL, "maxpool_bn_relu_fwd: null");
+  PM_REQUIRE(y->h == (x->h + 2 - 3) / 2 + 1 && y->w == (x->w + 2 - 3) / 2 + 1 && x->n == y->n && x->c == y->c, PM_EINVAL, "maxpool_bn_relu_fwd: shape mismatch");
+  PM_REQUIRE_F32(x, "maxpool_bn_relu_fwd"); PM_REQUIRE_F32(y, "maxpool_bn_relu_fwd");
+  PM_REQUIRE(pm_vec4(x) && pm_vec4(y), PM_EINVAL, "maxpool_bn_relu_fwd: tensors must be 16B aligned with pitch %% 4 == 0 and c %% 4 == 0");
+  const long total = pm_pixels(y) * y->c / 4;
+  if (total == 0) return PM_OK;
+  hipLaunchKernelGGL((maxpool_fwd_kernel<true, true>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x->ptr, (long)x->pitch, x->h, x->w,
+                     (float*)y->ptr, (long)y->pitch, y->h, y->w, x->c, total, argmax, mean, invstd, gamma, beta);
+  return pm_check_launch("maxpool_bn_relu_fwd");
 }
 
 extern "C" int pm_maxpool3x3s2_bwd(const pm_tensor* dy, const uint8_t* argmax, const pm_tensor* dx, void* stream) {

@@ -30,8 +30,9 @@ struct PwsK {
   const float* B;            // element (n, k) at B[n * b_sn + k * b_sk]
   float* C;                  // rows of Nn floats, c_pitch floats apart
   const float *bias, *scale, *shift, *residual;      // epilogue of the tile kernels: v = (acc + bias) * scale + shift (+ residual) (relu)
+  const unsigned char* res_mask;                     // null, or one byte per float4 group of C ([M][Nn / 4]): bit e clear = element e of the residual counts as 0
   long a_pitch, c_pitch, res_pitch;
-  unsigned a_bytes, c_bytes, res_bytes;               // buffer extents: rows >= M read zeros / are not stored
+  unsigned a_bytes, c_bytes, res_bytes, mask_bytes;   // buffer extents: rows >= M read zeros / are not stored
   int b_sn, b_sk;
   int M, Nn, row_tiles, relu;
 };
@@ -95,8 +96,10 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A), 0, (int)a.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(a.C, 0, (int)a.c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.residual ? a.residual : a.A), 0, (int)(a.residual ? a.res_bytes : 0u), 0x00020000);
-  const unsigned a_row = (unsigned)(a.a_pitch * 4), c_row = (unsigned)(a.c_pitch * 4), r_row = (unsigned)(a.res_pitch * 4);
-  const bool aff = a.bias || a.scale, res = a.residual != nullptr, relu = a.relu != 0;
+  const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.res_mask ? a.res_mask : reinterpret_cast<const unsigned char*>(a.A)), 0,
+                                                                      (int)(a.res_mask ? a.mask_bytes : 0u), 0x00020000);
+  const unsigned a_row = (unsigned)(a.a_pitch * 4), c_row = (unsigned)(a.c_pitch * 4), r_row = (unsigned)(a.res_pitch * 4), m_row = (unsigned)(a.Nn >> 2);
+  const bool aff = a.bias || a.scale, res = a.residual != nullptr, msk = a.res_mask != nullptr, relu = a.relu != 0;
   const int first = grp * 4 + wave, stride = groups * 4;
   v4f raw[NB][2 * KG];
   auto load = [&](v4f* dst, int tile) {
@@ -155,7 +158,14 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
         const unsigned row = (unsigned)(tile * 32 + rr + 8 * ps);
         v4f v = *reinterpret_cast<const v4f*>(stg + (rr + 8 * ps) * 144 + cg * 16);
         if (aff) v = (v + bi) * sc + sh;
-        if (res) v += __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rR, (int)(row * r_row + (unsigned)(n0 + c) * 4u), 0, 0));
+        if (res) {
+          v4f q = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rR, (int)(row * r_row + (unsigned)(n0 + c) * 4u), 0, 0));
+          if (msk) {      // rows beyond M: outside the mask's extent as well (reads 0; the row is not stored)
+            const unsigned mb = __builtin_amdgcn_raw_buffer_load_b8(rM, (int)(row * m_row + (unsigned)((n0 + c) >> 2)), 0, 0);
+            q.x = (mb & 1u) ? q.x : 0.f, q.y = (mb & 2u) ? q.y : 0.f, q.z = (mb & 4u) ? q.z : 0.f, q.w = (mb & 8u) ? q.w : 0.f;
+          }
+          v += q;
+        }
         if (relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rC, (int)(row * c_row + (unsigned)(n0 + c) * 4u), 0, 0);
       }
@@ -209,6 +219,7 @@ int pm_pwstream_launch(const pm_gemm_pw* g, hipStream_t st) {
   k.a_bytes = (unsigned)((g->M - 1) * g->a_pitch * 4 + (long)g->K * 4);
   k.c_bytes = (unsigned)((g->M - 1) * g->c_pitch * 4 + (long)g->Nn * 4);
   k.res_bytes = g->residual ? (unsigned)((g->M - 1) * g->res_pitch * 4 + (long)g->Nn * 4) : 0u;
+  k.res_mask = g->residual ? g->res_mask : nullptr, k.mask_bytes = k.res_mask ? (unsigned)(g->M * (g->Nn >> 2)) : 0u;
   k.b_sn = g->b_sn, k.b_sk = g->b_sk, k.M = (int)g->M, k.Nn = g->Nn, k.row_tiles = (int)((g->M + 31) / 32), k.relu = g->relu;
 
   // 512 blocks = two per CU, one tile in flight behind the one being multiplied: three / four blocks per CU and two / three tiles in flight measured level

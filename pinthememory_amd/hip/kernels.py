@@ -309,8 +309,9 @@ def conv_fwd(x, w_krsc, stride, pad, dil, bias=None, scale=None, shift=None, res
     return y
 
 
-def conv_bwd_data(dy, w_krsc, x_shape, stride, pad, dil, add=None, dtype=None):
-    """dtype: element type of dx = the type of the tensor it is the gradient of (default: dy's)."""
+def conv_bwd_data(dy, w_krsc, x_shape, stride, pad, dil, add=None, dtype=None, add_mask=None):
+    """dtype: element type of dx = the type of the tensor it is the gradient of (default: dy's). add_mask: bn_apply(want_mask=True)'s bytes -- `add` enters as
+    (bit ? add : 0); fp32, and only where the call routes to the implicit-GEMM kernels (the library refuses it elsewhere)."""
     cout, kh, kw, cin = w_krsc.shape
     dx = new(x_shape, dy, dtype=dtype)
     dyd, dxd = tdesc(dy), tdesc(dx)
@@ -321,7 +322,10 @@ def conv_bwd_data(dy, w_krsc, x_shape, stride, pad, dil, add=None, dtype=None):
     ws = workspace(nb, dy.device) if nb else None
     ad = tdesc(add) if add is not None else None
     u_ent = _wino_u(p, w_krsc, nbu, dgrad=True) if CONV_PREC == 2 else None      # bf16 tier: the rotated bf16 filter is kept per weight version
-    check(lib.pm_conv_bwd_data(byref(dyd), w_krsc.data_ptr(), byref(dxd), byref(p), byref(ad) if ad else None, ptr(ws), nb, stream()), 'pm_conv_bwd_data')
+    if add_mask is not None:
+        check(lib.pm_conv_bwd_data_masked(byref(dyd), w_krsc.data_ptr(), byref(dxd), byref(p), byref(ad), add_mask.data_ptr(), ptr(ws), nb, stream()), 'pm_conv_bwd_data_masked')
+    else:
+        check(lib.pm_conv_bwd_data(byref(dyd), w_krsc.data_ptr(), byref(dxd), byref(p), byref(ad) if ad else None, ptr(ws), nb, stream()), 'pm_conv_bwd_data')
     if u_ent is not None:
         ent, version = u_ent
         cur = L.stream_obj()
@@ -442,6 +446,24 @@ def bn_apply(x, mean, invstd, gamma, beta, residual=None, relu=False, out=None, 
     return (y, mask) if want_mask else y
 
 
+def bn_apply_res_affine(x, mean, invstd, gamma, beta, r, r_mean, r_invstd, r_gamma, r_beta, relu=False, want_mask=False):
+    """bn_apply(x, ..., residual=bn_apply(r, r_mean, r_invstd, r_gamma, r_beta)) in one launch: the normalised residual is never stored (fp32; same bits)."""
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    mask = torch.empty((x.shape[0] * x.shape[1] * x.shape[2], x.shape[3] // 4), dtype=torch.uint8, device=x.device) if want_mask else None
+    check(_lib().pm_bn_apply_mask_affine(byref(tdesc(x)), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), byref(tdesc(r)), r_mean.data_ptr(),
+                                         r_invstd.data_ptr(), r_gamma.data_ptr(), r_beta.data_ptr(), 1 if relu else 0, byref(tdesc(y)), ptr(mask), stream()),
+          'pm_bn_apply_mask_affine')
+    return (y, mask) if want_mask else y
+
+
+def bn_bwd_apply_mask(dy, mask, x, mean, invstd, gamma, sums, count):
+    """bn_bwd_apply(dy * mask, relu=0) with the mask read from bn_apply(want_mask=True)'s bytes; x: any tensor of that shape with its own statistics (fp32)."""
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    check(_lib().pm_bn_bwd_apply_mask(byref(tdesc(dy)), mask.data_ptr(), byref(tdesc(x)), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(),
+                                      float(count), byref(tdesc(dx)), stream()), 'pm_bn_bwd_apply_mask')
+    return dx
+
+
 def bn_bwd_reduce_mask(dy, mask, x, mean, invstd, want_gmask=True, with_count=False):
     """bn_bwd_reduce(relu=1) with the ReLU mask read from bn_apply(want_mask=True)'s bytes instead of the forward output."""
     c = x.shape[3]
@@ -534,6 +556,37 @@ def maxpool_fwd(x):
     arg = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
     check(_lib().pm_maxpool3x3s2_fwd(byref(tdesc(x)), byref(tdesc(y)), arg.data_ptr(), stream()), 'pm_maxpool3x3s2_fwd')
     return y, arg
+
+
+def maxpool_bn_relu_fwd(x, mean, invstd, gamma, beta):
+    """maxpool_fwd(bn_apply(x, ..., relu=True)) without the normalised tensor: -> (pooled, argmax bytes), the same bits (fp32)."""
+    n, h, w, c = x.shape
+    y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=x.dtype, device=x.device)
+    arg = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+    check(_lib().pm_maxpool3x3s2_bn_relu_fwd(byref(tdesc(x)), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), byref(tdesc(y)), arg.data_ptr(), stream()),
+          'pm_maxpool3x3s2_bn_relu_fwd')
+    return y, arg
+
+
+def bn_relu_bwd_pool(dyp, arg, x, mean, invstd, gamma, beta, with_count=False, reduce_sums=None):
+    """Backward of relu(bn(x)) followed by the 3x3 / s2 max pool, from the pooled gradient dyp and the argmax bytes: -> (dx, local sums [sum dy | sum dy xhat (| count)]).
+    = maxpool_bwd, bn_bwd_reduce(relu=2), bn_bwd_apply(relu=2) without the full-resolution gradient. reduce_sums: SyncBatchNorm's all-reduce of the sums (with_count)."""
+    c = x.shape[3]
+    sums = torch.empty(2 * c + (1 if with_count else 0), dtype=torch.float32, device=x.device)
+    if with_count:
+        sums[2 * c:].fill_(float(x.shape[0] * x.shape[1] * x.shape[2]))
+    xd, dd = tdesc(x), tdesc(dyp)
+    lib = _lib()
+    nb = _sizes(('bn', x.shape, x.dtype), lambda: lib.pm_bn_workspace(byref(xd)))
+    ws = workspace(nb, x.device)
+    check(lib.pm_bn_bwd_reduce_pool(byref(dd), arg.data_ptr(), byref(xd), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), sums.data_ptr(), ptr(ws), nb,
+                                    stream()), 'pm_bn_bwd_reduce_pool')
+    total = reduce_sums(sums) if reduce_sums is not None else sums
+    count = -1.0 if with_count else float(x.shape[0] * x.shape[1] * x.shape[2])
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    check(lib.pm_bn_bwd_apply_pool(byref(dd), arg.data_ptr(), byref(xd), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), total.data_ptr(), count,
+                                   byref(tdesc(dx)), stream()), 'pm_bn_bwd_apply_pool')
+    return dx, sums
 
 
 def maxpool_bwd(dy, arg, x_shape):

@@ -74,6 +74,7 @@ SIGNATURES = {
     'pm_conv_workspace': (_sz, [_T, _T, _P, _i]),
     'pm_conv_fwd': (_i, [_T, _vp, _T, _P, _E, _vp, _sz, _vp]),
     'pm_conv_bwd_data': (_i, [_T, _vp, _T, _P, _T, _vp, _sz, _vp]),
+    'pm_conv_bwd_data_masked': (_i, [_T, _vp, _T, _P, _T, _vp, _vp, _sz, _vp]),
     'pm_conv_bwd_weight': (_i, [_T, _T, _vp, _vp, _P, _vp, _sz, _vp]),
     'pm_set_winograd': (_i, [_i]),
     'pm_set_winograd_fused': (_i, [_i]),
@@ -94,6 +95,8 @@ SIGNATURES = {
     'pm_bn_apply': (_i, [_T, _vp, _vp, _vp, _vp, _T, _i, _T, _vp]),
     'pm_bn_apply_mask': (_i, [_T, _vp, _vp, _vp, _vp, _T, _i, _T, _vp, _vp]),
     'pm_bn_bwd_reduce_mask': (_i, [_T, _vp, _T, _vp, _vp, _T, _vp, _vp, _sz, _vp]),
+    'pm_bn_apply_mask_affine': (_i, [_T, _vp, _vp, _vp, _vp, _T, _vp, _vp, _vp, _vp, _i, _T, _vp, _vp]),
+    'pm_bn_bwd_apply_mask': (_i, [_T, _vp, _T, _vp, _vp, _vp, _vp, _f, _T, _vp]),
     'pm_bn_bwd_reduce': (_i, [_T, _T, _T, _vp, _vp, _vp, _vp, _i, _T, _vp, _vp, _sz, _vp]),
     'pm_bn_bwd_apply': (_i, [_T, _T, _T, _vp, _vp, _vp, _vp, _vp, _f, _i, _T, _T, _vp]),
     'pm_relu_bwd': (_i, [_T, _T, _T, _vp]),
@@ -103,6 +106,9 @@ SIGNATURES = {
     'pm_scale_shift_act': (_i, [_T, _vp, _vp, _T, _i, _T, _vp]),
     'pm_maxpool3x3s2_fwd': (_i, [_T, _T, _vp, _vp]),
     'pm_maxpool3x3s2_bwd': (_i, [_T, _vp, _T, _vp]),
+    'pm_maxpool3x3s2_bn_relu_fwd': (_i, [_T, _vp, _vp, _vp, _vp, _T, _vp, _vp]),
+    'pm_bn_bwd_reduce_pool': (_i, [_T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pm_bn_bwd_apply_pool': (_i, [_T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _f, _T, _vp]),
     'pm_global_avgpool_fwd': (_i, [_T, _T, _vp]),
     'pm_global_avgpool_bwd': (_i, [_T, _T, _i, _vp]),
     'pm_resize_bilinear_fwd': (_i, [_T, _T, _vp]),

@@ -222,8 +222,8 @@ def _mergeable(bns, ys):
             and len({y.shape[3] for y in ys}) == 1)
 
 
-def _bn_train_fwd(y, gamma, beta, bn, residual, relu, out=None, partials=None, want_mask=False):
-    """Batch statistics (merged across ranks for SyncBN) -> normalise + residual + ReLU. Returns (o, mean, invstd).
+def _bn_train_stats(y, bn, partials=None):
+    """Batch statistics of y (merged across ranks for SyncBN) -> (mean, invstd); running moments updated in place.
     partials: the (mean, M2) slab partials the producing convolution's epilogue emitted for y (K.conv_fwd(bn_partials=...)), or None:
     with them no kernel re-reads y for its statistics."""
     c = y.shape[3]
@@ -242,6 +242,12 @@ def _bn_train_fwd(y, gamma, beta, bn, residual, relu, out=None, partials=None, w
         if bn.group is not None:
             mom = D.merge_moments(mom, c, bn.group)
         mean, invstd = K.bn_finalize(mom, c, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
+    return mean, invstd
+
+
+def _bn_train_fwd(y, gamma, beta, bn, residual, relu, out=None, partials=None, want_mask=False):
+    """Batch statistics (_bn_train_stats) -> normalise + residual + ReLU. Returns (o, mean, invstd)."""
+    mean, invstd = _bn_train_stats(y, bn, partials)
     if want_mask:      # BN + residual + ReLU: one byte per float4 group tells the backward which gradients the ReLU passes (1 / 16 of re-reading the output)
         o, mask = K.bn_apply(y, mean, invstd, gamma, beta, residual=residual, relu=relu, out=out, want_mask=True)
         return o, mean, invstd, mask
@@ -273,6 +279,16 @@ def _bn_train_bwd(dv, o, y, mean, invstd, gamma, beta, relu, group, want_dres, h
     return dy, dres, local[c:2 * c], local[:c]
 
 
+def _bn_bwd_masked(dv, mask, y, mean, invstd, gamma, group):
+    """-> (dy, dgamma, dbeta) of a BatchNorm whose output gradient is dv masked by `mask` (bn_apply(want_mask=True)'s bytes): what _bn_train_bwd computes from the
+    stored masked gradient, without storing it. y / mean / invstd / gamma: the BatchNorm the mask came from, or the downsample BatchNorm behind the same ReLU. fp32."""
+    c = y.shape[3]
+    local, _ = K.bn_bwd_reduce_mask(dv, mask, y, mean, invstd, want_gmask=False, with_count=group is not None)
+    sums = local if group is None else D.all_reduce_sum_copy(local, group)
+    count = float(y.shape[0] * y.shape[1] * y.shape[2]) if group is None else -1.0
+    return K.bn_bwd_apply_mask(dv, mask, y, mean, invstd, gamma, sums, count), local[c:2 * c], local[:c]
+
+
 class _Bottleneck(torch.autograd.Function):
     """One ResNet Bottleneck (Resnet.py:181-216) as a single autograd node in train mode: the gradient of the block input is
     produced by conv1's dgrad with the skip-path gradient fused in (`add`), so autograd never launches a separate add, and the
@@ -294,15 +310,25 @@ class _Bottleneck(torch.autograd.Function):
             kd = K.krsc(wd)
             yd = K.conv_fwd(xv, kd, *geoms[3], bn_partials=ps)
             merged = _mergeable([bns[3], bns[2]], [yd, y3])
+            # fp32: the normalised downsample output is never stored -- bn3's apply pass evaluates it from yd (K.bn_apply_res_affine). The bf16 tier keeps its two launches.
+            fold = y3.dtype == torch.float32 and yd.dtype == torch.float32
             if merged:      # SyncBN: the two independent statistics exchanges of the block's tail travel as one
                 (md, idd), (m3, i3) = _bn_train_stats_multi([yd, y3], [bns[3], bns[2]], [ps[3], ps[2]])
-                res = K.bn_apply(yd, md, idd, gd, bd, residual=None, relu=False)
+                res = None if fold else K.bn_apply(yd, md, idd, gd, bd, residual=None, relu=False)
+            elif fold:
+                md, idd = _bn_train_stats(yd, bns[3], ps[3])
+                m3, i3 = _bn_train_stats(y3, bns[2], ps[2])
+                res = None
             else:
                 res, md, idd = _bn_train_fwd(yd, gd, bd, bns[3], None, False, partials=ps[3])
         else:
             kd = yd = md = idd = None
             res = xv
-        if merged:
+        if res is None:
+            out, mask3 = K.bn_apply_res_affine(y3, m3, i3, g3, b3, yd, md, idd, gd, bd, relu=True, want_mask=True)
+            if not RELU_MASK_BYTES:
+                mask3 = None
+        elif merged:
             out, mask3 = K.bn_apply(y3, m3, i3, g3, b3, residual=res, relu=True, want_mask=True) if RELU_MASK_BYTES else (K.bn_apply(y3, m3, i3, g3, b3, residual=res, relu=True), None)
         elif RELU_MASK_BYTES:
             out, m3, i3, mask3 = _bn_train_fwd(y3, g3, b3, bns[2], res, True, partials=ps[2], want_mask=True)
@@ -333,6 +359,11 @@ class _Bottleneck(torch.autograd.Function):
             dres, dg3, db3 = gm, s3[c3:2 * c3], s3[:c3]
             dyd, _ = K.bn_bwd_apply(gm, None, yd, md, idd, gd, gdsum, -1.0, 0, False, None)
             pair = (dyd, sd[c3:2 * c3], sd[:c3])
+        elif mask3 is not None and dv.dtype == torch.float32 and K.CONV_PREC != 2:
+            # fp32: the masked gradient dv * mask3 (bn3's input gradient AND the skip gradient) is never stored -- every reader takes (dv, mask3). ('bf16_operands' sends
+            # conv1's data gradient to the bf16 kernels, whose epilogue takes no masked add: that configuration keeps the stored form.)
+            dy3, dg3, db3 = _bn_bwd_masked(dv, mask3, y3, m3, i3, g3, gr[2])
+            dres = None
         else:
             dy3, dres, dg3, db3 = _bn_train_bwd(dv, out, y3, m3, i3, g3, b3, True, gr[2], True, True, mask=mask3)
         dw3, _ = _wgrad(o2, dy3, tuple(k3.shape), ge[2], deferred=df[2])
@@ -343,16 +374,18 @@ class _Bottleneck(torch.autograd.Function):
         dy1, _, dg1, db1 = _bn_train_bwd(do1, o1, y1, m1, i1, g1, b1, True, gr[0], False, False)
         dw1, _ = _wgrad(xv, dy1, tuple(k1.shape), ge[0], deferred=df[0])
         dwd = dgd = dbd = None
-        skip = dres
+        skip, skip_mask = (dres, None) if dres is not None else (dv, mask3)
         if ctx.has_ds:
             if pair is not None:
                 dyd, dgd, dbd = pair
+            elif dres is None:
+                dyd, dgd, dbd = _bn_bwd_masked(dv, mask3, yd, md, idd, gd, gr[3])
             else:
                 dyd, _, dgd, dbd = _bn_train_bwd(dres, None, yd, md, idd, gd, None, False, gr[3], False, False)
             dwdk, _ = _wgrad(xv, dyd, tuple(kd.shape), ge[3], deferred=df[3])
             dwd = dwdk.permute(0, 3, 1, 2)
-            skip = K.conv_bwd_data(dyd, kd, tuple(xv.shape), *ge[3]) if ctx.needs_input_grad[0] else None
-        dx = nchw(K.conv_bwd_data(dy1, k1, tuple(xv.shape), *ge[0], add=skip)) if ctx.needs_input_grad[0] else None
+            skip, skip_mask = (K.conv_bwd_data(dyd, kd, tuple(xv.shape), *ge[3]) if ctx.needs_input_grad[0] else None), None
+        dx = nchw(K.conv_bwd_data(dy1, k1, tuple(xv.shape), *ge[0], add=skip, add_mask=skip_mask)) if ctx.needs_input_grad[0] else None
         p = lambda d: d.permute(0, 3, 1, 2)
         return dx, p(dw1), dg1, db1, p(dw2), dg2, db2, p(dw3), dg3, db3, dwd, dgd, dbd, None, None, None
 
@@ -466,6 +499,46 @@ class _ConvBnAct(torch.autograd.Function):
             dwk, db = _wgrad(xv, dy, tuple(wk.shape), (stride, pad, dil), want_bias=ctx.has_bias, deferred=ctx.deferred, wino_v=vk)
             dw = dwk.permute(0, 3, 1, 2)
         return dx, dw, db, dgamma, dbeta, (nchw(dres) if dres is not None else None), None, None, None, None, None
+
+
+class _Stem(torch.autograd.Function):
+    """The stem tail, conv -> BatchNorm(train) -> ReLU -> 3x3 / s2 max pool (Resnet.py:471-478), as one node on the fp32 tier: the pool normalises its taps itself and
+    the BatchNorm backward gathers its incoming gradient from the pooled gradient and the argmax bytes, so neither the full-resolution activation nor its gradient
+    (302 MB each at 8 x 768^2) is ever written. Same kernels' arithmetic as _ConvBnAct + _MaxPool, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, geom, bn):
+        xv, wk = nhwc(x), K.krsc(w)
+        kv, ps = [], []
+        y = K.conv_fwd(xv, wk, *geom, keep_v=kv if ctx.needs_input_grad[1] else None, bn_partials=ps)
+        mean, invstd = _bn_train_stats(y, bn, ps[0])
+        out, arg = K.maxpool_bn_relu_fwd(y, mean, invstd, gamma, beta)
+        ctx.geom, ctx.group = geom, bn.group
+        ctx.save_for_backward(xv, wk, y, mean, invstd, gamma, beta, arg, kv[0] if kv else None)
+        return nchw(out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xv, wk, y, mean, invstd, gamma, beta, arg, vk = ctx.saved_tensors
+        c = y.shape[3]
+        grp = ctx.group
+        dy, local = K.bn_relu_bwd_pool(_grad_view(dout), arg, y, mean, invstd, gamma, beta, with_count=grp is not None,
+                                       reduce_sums=(lambda s: D.all_reduce_sum_copy(s, grp)) if grp is not None else None)
+        dx = nchw(K.conv_bwd_data(dy, wk, tuple(xv.shape), *ctx.geom, dtype=xv.dtype)) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dwk, _ = _wgrad(xv, dy, tuple(wk.shape), ctx.geom, wino_v=vk)
+            dw = dwk.permute(0, 3, 1, 2)
+        return dx, dw, local[c:2 * c], local[:c], None, None
+
+
+def stem_tail(x, w, conv, bn):
+    """conv(x, w) -> bn -> ReLU -> maxpool3x3s2. w: the weight the convolution runs with (the stem pads conv.weight to four input channels). One fused node in train
+    mode with gradients on the fp32 tier; everywhere else (eval, no-grad, the bf16 tier) the two separate nodes. The stem convolution has no bias (Resnet.py:404)."""
+    st = BNState(bn)
+    if st.training and torch.is_grad_enabled() and K.ACT_DTYPE == torch.float32 and x.dtype == torch.float32 and w.shape[0] % 4 == 0:
+        return _Stem.apply(x, w, bn.weight, bn.bias, _geom(conv), st)
+    return maxpool3x3s2(_ConvBnAct.apply(x, w, None, bn.weight, bn.bias, None, _geom(conv), st, True, None))
 
 
 class _ConvBnActN(torch.autograd.Function):

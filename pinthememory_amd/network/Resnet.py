@@ -91,8 +91,7 @@ def stem(conv1, bn1, x):
     from ..hip import kernels as K
     x4 = ops.nchw(K.nchw_to_nhwc(x.float(), c_pad=4)) if x.shape[1] == 3 else x
     w4 = F.pad(conv1.weight, (0, 0, 0, 0, 0, 4 - conv1.weight.shape[1])) if conv1.weight.shape[1] == 3 else conv1.weight
-    y = ops._ConvBnAct.apply(x4, w4, None, bn1.weight, bn1.bias, None, ops._geom(conv1), ops.BNState(bn1), True, None)
-    return ops.maxpool3x3s2(y)
+    return ops.stem_tail(x4, w4, conv1, bn1)
 
 
 def _pretrained(model, name):
