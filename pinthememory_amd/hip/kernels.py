@@ -4,6 +4,7 @@ import ctypes
 from ctypes import byref
 
 import os
+import weakref
 
 import torch
 
@@ -110,14 +111,12 @@ BN_EP_MIN_BYTES = int(float(os.environ.get('PM_BN_EP_MIN_MB', '0')) * (1 << 20))
 KEEP_WINOGRAD_U = {'0': False, '1': True}.get(os.environ.get('PM_KEEP_U', ''))      # None = owner-scoped (default)
 
 _U_OWNERS = {}      # storage address -> weakref to the registered leaf parameter
-_U_CACHE = {}       # key -> [weakref(owner) or the weight itself when forced, version, U]
 _U_CACHE_MAX = 256
 _U_CACHE_BYTES = int(os.environ.get('PM_KEEP_U_MB', '2048')) << 20     # one ResNet-50 DeepLabV3+ keeps 0.43 GB, a ResNet-101 DeepLabV2 0.65 GB
 
 
 def register_filter_owners(params):
     """Called by an optimizer for the weights it owns: it promises that every update of them moves the tensor version (optim.SGD does)."""
-    import weakref
     for p in params:
         if isinstance(p, torch.nn.Parameter) and p.is_leaf and p.is_cuda and p.dim() == 4 and p.dtype == torch.float32:
             _U_OWNERS[p.data_ptr()] = weakref.ref(p)
@@ -128,8 +127,7 @@ def unregister_filter_owners(params=None):
     ptrs = None if params is None else {p.data_ptr() for p in params}
     for k in [k for k in _U_OWNERS if ptrs is None or k in ptrs]:
         del _U_OWNERS[k]
-    for k in [k for k in _U_CACHE if ptrs is None or k[0] in ptrs]:
-        del _U_CACHE[k]
+    _U_CACHE.drop_if(lambda ent: ptrs is None or ent.ptr in ptrs)
 
 
 def _filter_owner(w_krsc):
@@ -142,95 +140,139 @@ def _filter_owner(w_krsc):
     return p if (p.data_ptr() == w_krsc.data_ptr() and p.numel() == w_krsc.numel() and p.is_leaf) else None
 
 
-_U_STREAMS = {}     # every stream that ever read or wrote a kept transform (main stream, the harness' commit stream)
+class _KeptFilter:
+    """One kept transform. ptr ... dgrad are the fields of its lookup key: the weight's storage address and KRSC shape, the bytes of the transform, the device
+    index, the tier (CONV_PREC) and whether it is the rotated / transposed bf16 filter of a data gradient.
+    owner: call it -> the tensor whose version vouches for the buffer, or None once that tensor is gone (a weak reference to the registered parameter; forced
+    mode holds the unregistered weight of the call itself). version: the owner's version the buffer holds, -1 while a rewrite is pending.
+    event / stream: recorded behind the launch that last wrote buf, and that launch's raw stream (None: nothing to wait for). used: read since the last refresh."""
+    __slots__ = ('ptr', 'shape', 'nbytes', 'device', 'prec', 'dgrad', 'owner', 'version', 'buf', 'event', 'stream', 'used')
 
 
-def _evict(ent):
-    """The buffer goes back to the pool of the stream that allocated it, while a launch on ANOTHER stream (the commit forward) may still be reading it:
-    tell the allocator about every stream that uses the cache, so that the block is not handed out again before their queued work is done."""
-    if ent[2].is_cuda:
-        for s in _U_STREAMS.values():
-            ent[2].record_stream(s)
+class _FilterCache(dict):
+    """lookup key -> _KeptFilter, oldest first (dicts keep insertion order; hits are re-inserted)."""
+    def __init__(self):
+        self.nbytes = 0         # of all kept buffers
+        self.streams = {}       # raw handle -> every stream that ever read or wrote a kept transform (main stream, the harness' commit stream)
+
+    def _stream(self):
+        raw = stream()
+        cur = self.streams.get(raw)
+        if cur is None:
+            cur = self.streams[raw] = L.stream_obj()
+        return raw, cur
+
+    def _drop(self, key):
+        """The one way an entry leaves. The buffer goes back to the pool of the stream that allocated it, while a launch on ANOTHER stream (the commit forward) may still
+        be reading it: tell the allocator about every stream that uses the cache, so that the block is not handed out again before their queued work is done."""
+        ent = self.pop(key)
+        self.nbytes -= ent.nbytes
+        if ent.buf.is_cuda:
+            for s in self.streams.values():
+                ent.buf.record_stream(s)
+
+    def drop_if(self, pred):
+        for key in [k for k, ent in self.items() if pred(ent)]:
+            self._drop(key)
+
+    def clear(self):
+        """Drop every kept transform (the registered owners stay)."""
+        self.drop_if(lambda ent: True)
+
+    def lookup(self, p, w_krsc, nbu, dgrad=False):
+        """Point the call's parameters `p` at the kept transform of this weight, allocating one on a miss. nbu: bytes of the transformed filter of this call
+        (pm_conv_wxf_bytes / _dgrad; 0: none). -> None when the call finds it valid (or nothing is kept), else (entry, version): the call rewrites the buffer and
+        hands the pair to commit() once its launch is enqueued."""
+        if KEEP_WINOGRAD_U is False or not nbu:
+            return None
+        registered = _filter_owner(w_krsc)
+        if registered is None and KEEP_WINOGRAD_U is not True:
+            return None
+        owner = w_krsc if registered is None else registered      # forced mode keeps unregistered weights too: the tensor of this call stands in for an owner
+        key = (w_krsc.data_ptr(), tuple(w_krsc.shape), nbu, w_krsc.device.index, p.prec, dgrad)
+        ent = self.get(key)
+        if ent is not None and ent.owner() is not owner:
+            self._drop(key)            # another tensor now lives at this address: the kept transform is somebody else's
+            ent = None
+        if ent is None:
+            # only a miss evicts (a captured step has the buffer addresses of its hits baked in): models that are gone release their buffers here, then the oldest go
+            self.drop_if(lambda e: e.owner() is None)
+            while self and (len(self) >= _U_CACHE_MAX or self.nbytes + nbu > _U_CACHE_BYTES):
+                self._drop(next(iter(self)))
+            ent = _KeptFilter()
+            ent.ptr, ent.shape, ent.nbytes, ent.device, ent.prec, ent.dgrad = key
+            ent.owner = (lambda: w_krsc) if registered is None else weakref.ref(registered)
+            ent.version, ent.buf, ent.event, ent.stream = -1, torch.empty(nbu // 4, dtype=torch.float32, device=w_krsc.device), None, None
+            self.nbytes += nbu
+        else:
+            del self[key]       # a hit moves to the young end
+        self[key] = ent
+        ent.used = True
+        version = owner._version
+        valid = ent.version == version
+        if not valid:
+            ent.version = -1            # invalid until the launch that fills it has been enqueued (the caller commits the version after check())
+        p.wxf, p.wxf_bytes, p.wxf_valid = ent.buf.data_ptr(), nbu, 1 if valid else 0
+        raw, cur = self._stream()
+        if valid and ent.event is not None and ent.stream != raw:
+            cur.wait_event(ent.event)   # the transform was written by a launch on another stream (harness: the commit forward runs on its own)
+        return None if valid else (ent, version)
+
+    def commit(self, *pending):
+        """pending: (entry, version) pairs whose buffers the launch just enqueued on the current stream writes (check() has passed): only now are they valid;
+        hits from another stream wait for this event."""
+        raw, cur = self._stream()
+        event = cur.record_event()
+        for ent, version in pending:
+            ent.version, ent.event, ent.stream = version, event, raw
+
+    def forget_events(self):
+        """Drop the 'written by a launch on another stream' events of every kept transform. Call after torch.cuda.synchronize(): harness.GraphedAggStep does once its capture
+        has ended -- events recorded inside a stream capture must not be waited for from eager code, and a replay (a single launch in stream order) needs none."""
+        for ent in self.values():
+            ent.event = ent.stream = None
 
 
-def _wino_u(p, w_krsc, nbu, dgrad=False):
-    """nbu: bytes of the transformed filter of this call (pm_conv_wxf_bytes / _dgrad; 0: none). dgrad: the kept transform is the rotated / transposed bf16 filter
-    of a data gradient on the bf16 tier."""
-    if KEEP_WINOGRAD_U is False or not nbu:
-        return None
-    owner = _filter_owner(w_krsc)
-    if owner is None and KEEP_WINOGRAD_U is not True:
-        return None
-    import weakref
-    key = (w_krsc.data_ptr(), tuple(w_krsc.shape), nbu, w_krsc.device.index, p.prec, dgrad)
-    ent = _U_CACHE.pop(key, None)
-    if ent is not None and (ent[0]() if isinstance(ent[0], weakref.ref) else ent[0]) is not (owner if owner is not None else w_krsc):
-        ent = None                 # another tensor now lives at this address: the kept transform is somebody else's
-    if ent is None:
-        # oldest entries go first (dicts keep insertion order; hits are re-inserted): models that are gone release their buffers here
-        for k in [k for k, e in _U_CACHE.items() if isinstance(e[0], weakref.ref) and e[0]() is None]:
-            _evict(_U_CACHE.pop(k))
-        while _U_CACHE and (len(_U_CACHE) >= _U_CACHE_MAX or sum(e[2].numel() * 4 for e in _U_CACHE.values()) + nbu > _U_CACHE_BYTES):
-            _evict(_U_CACHE.pop(next(iter(_U_CACHE))))
-        ent = [weakref.ref(owner) if owner is not None else w_krsc, -1, torch.empty(nbu // 4, dtype=torch.float32, device=w_krsc.device), None, None, True]
-    ent[5] = True                       # used since the last refresh_bf16_filters()
-    version = (owner if owner is not None else w_krsc)._version
-    valid = ent[1] == version
-    if not valid:
-        ent[1] = -1                     # invalid until the launch that fills it has been enqueued (conv_fwd commits the version after check())
-    _U_CACHE[key] = ent
-    p.wxf, p.wxf_bytes, p.wxf_valid = ent[2].data_ptr(), nbu, 1 if valid else 0
-    raw = stream()
-    if raw not in _U_STREAMS:
-        _U_STREAMS[raw] = L.stream_obj()
-    if valid and ent[3] is not None and ent[4] != raw:
-        _U_STREAMS[raw].wait_event(ent[3])          # the transform was written by a launch on another stream (harness: the commit forward runs on its own)
-    return None if valid else (ent, version)
+_U_CACHE = _FilterCache()
+clear_filters, forget_filter_events = _U_CACHE.clear, _U_CACHE.forget_events
+
+# tier (CONV_PREC) -> (the library's batched rewrite, does it take only the forward transforms of 3x3 filters).
+# 2: every kept bf16 filter (forward copy, rotated copy of the data gradient) in ONE or two launches instead of one small cast in front of each of the ~142 convolution
+# calls of the next step. 0: every kept Winograd FORWARD transform (U = G g Gt of the wide stride-1 3x3 layers) in one launch instead of ~20 latency-bound per-layer
+# launches in front of the next forward pass. Same kernel bodies as the per-call transforms, same bits.
+_REFRESH = {2: ('pm_conv_wxf_refresh_bf16', False), 0: ('pm_conv_wxf_refresh_f32', True)}
 
 
-def forget_filter_events():
-    """Drop the 'written by a launch on another stream' events of every kept transform. Call after torch.cuda.synchronize(): harness.GraphedAggStep does once its capture has
-    ended -- events recorded inside a stream capture must not be waited for from eager code, and a replay (a single launch in stream order) needs none."""
-    for ent in _U_CACHE.values():
-        ent[3] = ent[4] = None
-
-
-WXF_REFRESH = os.environ.get('PM_WXF_REFRESH', '1') != '0'      # A/B knob
-
-
-def refresh_bf16_filters():
-    """bf16 tier, called by the optimizer right after it moved the weights: rewrite every kept bf16 filter (forward copy, rotated copy of the data gradient) that
-    was used since the last call and is now out of date, in ONE or two launches (pm_conv_wxf_refresh_bf16) instead of one small cast in front of each of the
-    ~142 convolution calls of the next step. Entries nobody used in the last step are left to go stale (their convolution re-derives them if it returns).
-    The caller has already made sure no other stream still reads the buffers (optim.SGD.step: ops.wait_commit()). Returns the number of filters rewritten."""
-    if CONV_PREC != 2 or KEEP_WINOGRAD_U is False or not _U_CACHE or not WXF_REFRESH:
+def refresh_filters():
+    """Called by the optimizer right after it moved the weights: rewrite every kept filter transform of the active tier that was used since the last call and is now
+    out of date, in one call of the library. Entries nobody used in the last step are left to go stale (their convolution re-derives them if it returns), dead or moved
+    owners are skipped. The caller has already made sure no other stream still reads the buffers (optim.SGD.step: ops.wait_commit()). Returns the number of filters
+    rewritten (0: no launch)."""
+    if KEEP_WINOGRAD_U is False or not _U_CACHE or CONV_PREC not in _REFRESH:
         return 0
-    import weakref
+    entry_point, forward_3x3_only = _REFRESH[CONV_PREC]
     dev = torch.cuda.current_device()
     todo = []
-    for key, ent in _U_CACHE.items():
-        if key[4] != 2 or key[3] != dev or not ent[5]:
+    for ent in _U_CACHE.values():
+        if ent.prec != CONV_PREC or ent.device != dev or not ent.used:
             continue
-        ent[5] = False
-        owner = ent[0]() if isinstance(ent[0], weakref.ref) else ent[0]
-        if owner is None or owner.data_ptr() != key[0] or ent[1] == owner._version or not ent[2].is_cuda:
+        cout, kh, kw, cin = ent.shape
+        if forward_3x3_only and (ent.dgrad or kh != 3 or kw != 3):
             continue
-        todo.append((key, ent, owner))
+        ent.used = False
+        owner = ent.owner()
+        if owner is None or owner.data_ptr() != ent.ptr or ent.version == owner._version or not ent.buf.is_cuda:
+            continue
+        todo.append((ent, owner._version))
     if not todo:
         return 0
     jobs = (L.PmWxfJob * len(todo))()
-    for j, (key, ent, owner) in zip(jobs, todo):
-        cout, kh, kw, cin = key[1]
-        j.w, j.wxf, j.wxf_bytes, j.cout, j.kh, j.kw, j.cin, j.dgrad = key[0], ent[2].data_ptr(), key[2], cout, kh, kw, cin, 1 if key[5] else 0
-        ent[1] = -1
-    check(_lib().pm_conv_wxf_refresh_bf16(jobs, len(todo), stream()), 'pm_conv_wxf_refresh_bf16')
-    cur = L.stream_obj()
-    raw = cur.cuda_stream
-    if raw not in _U_STREAMS:
-        _U_STREAMS[raw] = cur
-    ev = cur.record_event()
-    for key, ent, owner in todo:
-        ent[1], ent[3], ent[4] = owner._version, ev, raw
+    for j, (ent, version) in zip(jobs, todo):
+        cout, kh, kw, cin = ent.shape
+        j.w, j.wxf, j.wxf_bytes, j.cout, j.kh, j.kw, j.cin, j.dgrad = ent.ptr, ent.buf.data_ptr(), ent.nbytes, cout, kh, kw, cin, 1 if ent.dgrad else 0
+        ent.version = -1
+    check(getattr(_lib(), entry_point)(jobs, len(todo), stream()), entry_point)
+    _U_CACHE.commit(*todo)
     return len(todo)
 
 
@@ -284,7 +326,7 @@ def conv_fwd(x, w_krsc, stride, pad, dil, bias=None, scale=None, shift=None, res
             p.wino_v, p.wino_v_bytes = v.data_ptr(), nbv
     u_ent = None
     if (kh == 3 and CONV_PREC == 0) or CONV_PREC == 2:
-        u_ent = _wino_u(p, w_krsc, nbu)        # (cache entry this call is about to (re)write, version to commit once the launch is enqueued) or None
+        u_ent = _U_CACHE.lookup(p, w_krsc, nbu)        # (cache entry this call is about to (re)write, version to commit once the launch is enqueued) or None
     if _XFORM_COUNT[1] and p.wxf_valid == 0 and nbu:
         _XFORM_COUNT[0] += 1      # this call transforms its filter
     ws = workspace(nb, x.device) if nb else None
@@ -301,11 +343,8 @@ def conv_fwd(x, w_krsc, stride, pad, dil, bias=None, scale=None, shift=None, res
         ep = L.conv_epilogue(ptr(bias), ptr(scale), ptr(shift), rd.ptr if rd else None, rd.pitch if rd else 0, 1 if relu else 0, ptr(part),
                             part.numel() * 4 if part is not None else 0)
     check(lib.pm_conv_fwd(byref(xd), w_krsc.data_ptr(), byref(yd), byref(p), byref(ep) if ep else None, ptr(ws), nb, stream()), 'pm_conv_fwd')
-    if u_ent is not None:               # the launch is enqueued: only now is the kept transform valid; hits from another stream wait for this event
-        ent, version = u_ent
-        cur = L.stream_obj()
-        ent[3], ent[4] = cur.record_event(), cur.cuda_stream
-        ent[1] = version
+    if u_ent is not None:
+        _U_CACHE.commit(u_ent)
     return y
 
 
@@ -321,16 +360,13 @@ def conv_bwd_data(dy, w_krsc, x_shape, stride, pad, dil, add=None, dtype=None, a
                      lambda: (lib.pm_conv_workspace(byref(dxd), byref(dyd), byref(p), 1), lib.pm_conv_wxf_bytes_dgrad(byref(dyd), byref(dxd), byref(p))))
     ws = workspace(nb, dy.device) if nb else None
     ad = tdesc(add) if add is not None else None
-    u_ent = _wino_u(p, w_krsc, nbu, dgrad=True) if CONV_PREC == 2 else None      # bf16 tier: the rotated bf16 filter is kept per weight version
+    u_ent = _U_CACHE.lookup(p, w_krsc, nbu, dgrad=True) if CONV_PREC == 2 else None      # bf16 tier: the rotated bf16 filter is kept per weight version
     if add_mask is not None:
         check(lib.pm_conv_bwd_data_masked(byref(dyd), w_krsc.data_ptr(), byref(dxd), byref(p), byref(ad), add_mask.data_ptr(), ptr(ws), nb, stream()), 'pm_conv_bwd_data_masked')
     else:
         check(lib.pm_conv_bwd_data(byref(dyd), w_krsc.data_ptr(), byref(dxd), byref(p), byref(ad) if ad else None, ptr(ws), nb, stream()), 'pm_conv_bwd_data')
     if u_ent is not None:
-        ent, version = u_ent
-        cur = L.stream_obj()
-        ent[3], ent[4] = cur.record_event(), cur.cuda_stream
-        ent[1] = version
+        _U_CACHE.commit(u_ent)
     return dx
 
 
@@ -827,46 +863,6 @@ def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image,
     check(_lib().pm_upsample_wce_bwd_field(byref(tdesc(logits)), inv_temp, H, W, int(bool(per_image)), loss_out.data_ptr(), ptr(gscale), field.data_ptr(),
                                            byref(tdesc(dl)), stream()), 'pm_upsample_wce_bwd_field')
     return dl
-
-
-def refresh_f32_filters():
-    """fp32 tier twin of refresh_bf16_filters(): every kept Winograd FORWARD transform (U = G g Gt of the wide stride-1 3x3 layers) that was used since the last call and
-    is now out of date, rewritten in one launch (pm_conv_wxf_refresh_f32) behind the optimizer step instead of ~20 latency-bound per-layer launches in front of the
-    next forward pass. Same kernel body, same bits. Returns the number of filters rewritten."""
-    if CONV_PREC != 0 or KEEP_WINOGRAD_U is False or not _U_CACHE or not WXF_REFRESH:
-        return 0
-    import weakref
-    dev = torch.cuda.current_device()
-    todo = []
-    for key, ent in _U_CACHE.items():
-        if key[4] != 0 or key[5] or key[3] != dev or not ent[5] or key[1][1] != 3 or key[1][2] != 3:
-            continue
-        ent[5] = False
-        owner = ent[0]() if isinstance(ent[0], weakref.ref) else ent[0]
-        if owner is None or owner.data_ptr() != key[0] or ent[1] == owner._version or not ent[2].is_cuda:
-            continue
-        todo.append((key, ent, owner))
-    if not todo:
-        return 0
-    jobs = (L.PmWxfJob * len(todo))()
-    for j, (key, ent, owner) in zip(jobs, todo):
-        cout, kh, kw, cin = key[1]
-        j.w, j.wxf, j.wxf_bytes, j.cout, j.kh, j.kw, j.cin, j.dgrad = key[0], ent[2].data_ptr(), key[2], cout, kh, kw, cin, 0
-        ent[1] = -1
-    check(_lib().pm_conv_wxf_refresh_f32(jobs, len(todo), stream()), 'pm_conv_wxf_refresh_f32')
-    cur = L.stream_obj()
-    raw = cur.cuda_stream
-    if raw not in _U_STREAMS:
-        _U_STREAMS[raw] = cur
-    ev = cur.record_event()
-    for key, ent, owner in todo:
-        ent[1], ent[3], ent[4] = owner._version, ev, raw
-    return len(todo)
-
-
-def refresh_filters():
-    """Called by the optimizer right after it moved the weights: the kept filter transforms of the active tier, rewritten in one launch."""
-    return refresh_bf16_filters() if CONV_PREC == 2 else refresh_f32_filters()
 
 
 # ---- memory ---------------------------------------------------------------------------------------------------------

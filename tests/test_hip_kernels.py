@@ -536,7 +536,7 @@ def test_winograd_filter_cache(K):
     wk = w.detach().permute(0, 2, 3, 1)                       # KRSC view of the parameter's own memory
     assert wk.data_ptr() == w.data_ptr() and wk.is_contiguous()
     ref = lambda: F.conv2d(nchw(x), w.detach().cpu(), padding=1)
-    K._U_CACHE.clear()
+    K.clear_filters()
     K.unregister_filter_owners()
     was = K.KEEP_WINOGRAD_U
     K.KEEP_WINOGRAD_U = None                                  # the default: only weights an optimizer registered are cached
@@ -556,13 +556,13 @@ def test_winograd_filter_cache(K):
     assert len(K._U_CACHE) == 1
     assert len(K._U_CACHE) == 1 and rel(nchw(y1), ref()) < 2e-5
     ent = next(iter(K._U_CACHE.values()))
-    u_before = ent[2].clone()
+    u_before = ent.buf.clone()
     y2 = K.conv_fwd(x, wk, 1, 1, 1)                           # hit: same bits, U untouched
-    assert torch.equal(y1, y2) and torch.equal(ent[2], u_before) and len(K._U_CACHE) == 1
+    assert torch.equal(y1, y2) and torch.equal(ent.buf, u_before) and len(K._U_CACHE) == 1
     with torch.no_grad():
         w.mul_(0.5)                                           # torch in-place op: version bump -> recomputed
     y3 = K.conv_fwd(x, wk, 1, 1, 1)
-    assert rel(nchw(y3), ref()) < 2e-5 and not torch.equal(ent[2], u_before)
+    assert rel(nchw(y3), ref()) < 2e-5 and not torch.equal(ent.buf, u_before)
     w.grad = torch.ones_like(w)                               # one fused SGD step (raw-pointer update inside the library)
     opt.step()
     y4 = K.conv_fwd(x, wk, 1, 1, 1)
@@ -576,6 +576,49 @@ def test_winograd_filter_cache(K):
         assert torch.equal(K.conv_fwd(x, wk, 1, 1, 1), y4) and len(K._U_CACHE) == 0
     finally:
         K.KEEP_WINOGRAD_U = was
+
+
+def test_filter_cache_eviction(K):
+    """Who leaves the filter cache, and when: a miss over the byte cap evicts the oldest entry, a hit makes its entry the youngest, entries whose owner is gone are
+    swept by the next miss before anything live goes, and unregister + clear leave nothing. Every output has the bits of the same call without the cache."""
+    import gc
+    from pinthememory_amd import optim
+    x = nhwc(rnd(2, 128, 24, 24, seed=1))                     # test_winograd_filter_cache's shape: the smallest that takes the Winograd route and keeps a transform
+    ws = {n: torch.nn.Parameter(rnd(128, 128, 3, 3, seed=2 + i).mul(0.05).cuda().contiguous(memory_format=torch.channels_last)) for i, n in enumerate('abc')}
+    conv = lambda n: K.conv_fwd(x, ws[n].detach().permute(0, 2, 3, 1), 1, 1, 1)
+    owners = lambda: [next((n for n, w in ws.items() if w is e.owner()), None) for e in K._U_CACHE.values()]      # names, oldest entry first; None: the owner is gone
+    K.clear_filters()
+    K.unregister_filter_owners()
+    was, cap = K.KEEP_WINOGRAD_U, K._U_CACHE_BYTES
+    try:
+        K.KEEP_WINOGRAD_U = False
+        want = {n: conv(n) for n in 'abc'}
+        K.KEEP_WINOGRAD_U = None
+        opt = optim.SGD(list(ws.values()), lr=0.1, momentum=0.9, weight_decay=0.0)
+        got = [('a', conv('a'))]
+        first = next(iter(K._U_CACHE.values()))
+        assert len(K._U_CACHE) == 1 and first.owner() is ws['a'] and first.nbytes == first.buf.numel() * 4
+        K._U_CACHE_BYTES = first.nbytes * 5 // 2                  # room for two transforms, not for three
+        got += [('b', conv('b')), ('c', conv('c'))]
+        assert owners() == ['b', 'c']                             # (1) a was the oldest
+        kept_b = next(iter(K._U_CACHE.values())).buf
+        got += [('b', conv('b')), ('a', conv('a'))]
+        assert owners() == ['b', 'a']                             # (2) the hit on b made c the oldest
+        assert next(iter(K._U_CACHE.values())).buf is kept_b      # a hit never reallocates
+        opt.param_groups[0]['params'][:] = [ws['b'], ws['c']]
+        del ws['a']                                               # the youngest entry: the byte cap alone would evict b and keep it
+        gc.collect()
+        got.append(('c', conv('c')))
+        assert owners() == ['b', 'c']                             # (3) the miss swept the dead owner's entry first
+        for n, y in got:
+            assert torch.equal(y, want[n]), n                     # (4)
+        K.unregister_filter_owners()
+        K.clear_filters()
+        assert len(K._U_CACHE) == 0                               # (5)
+    finally:
+        K.KEEP_WINOGRAD_U, K._U_CACHE_BYTES = was, cap
+        K.unregister_filter_owners()
+        K.clear_filters()
 
 
 def test_layout_and_labels(K):
@@ -1241,7 +1284,7 @@ def test_bf16_filter_refresh_after_optimizer_step(K):
     K.set_conv_precision('bf16')
     was = K.KEEP_WINOGRAD_U
     K.KEEP_WINOGRAD_U = None
-    K._U_CACHE.clear()
+    K.clear_filters()
     K.unregister_filter_owners()
     try:
         cases = [(128, 64, 3, 1, 1), (96, 160, 1, 0, 1), (64, 256, 3, 2, 2)]        # (cout, cin, k, pad, dil)
@@ -1266,7 +1309,7 @@ def test_bf16_filter_refresh_after_optimizer_step(K):
         K.filter_transform_count(True)
         n0 = K.filter_transform_count()
         opt.step()                                                   # moves the weights, bumps the versions, refreshes the six kept filters
-        assert all(e[1] == w._version for e in K._U_CACHE.values() for w in ws if (e[0]() is w))
+        assert all(e.version == w._version for e in K._U_CACHE.values() for w in ws if (e.owner() is w))
         second = run()
         assert K.filter_transform_count() == n0                      # no forward call derived a filter again
         K.filter_transform_count(False)
@@ -1276,12 +1319,12 @@ def test_bf16_filter_refresh_after_optimizer_step(K):
         for a, b in zip(second, fresh):
             assert torch.equal(a, b)
         K.KEEP_WINOGRAD_U = None
-        assert K.refresh_bf16_filters() == 0                         # nothing out of date: no launch
+        assert K.refresh_filters() == 0                              # nothing out of date: no launch
     finally:
         K.filter_transform_count(False)
         K.KEEP_WINOGRAD_U = was
         K.unregister_filter_owners()
-        K._U_CACHE.clear()
+        K.clear_filters()
         K.set_conv_precision('f32')
 
 
@@ -1293,7 +1336,7 @@ def test_f32_winograd_filter_refresh_after_optimizer_step(K):
     K.set_conv_precision('f32')
     was = K.KEEP_WINOGRAD_U
     K.KEEP_WINOGRAD_U = None
-    K._U_CACHE.clear()
+    K.clear_filters()
     K.unregister_filter_owners()
     try:
         cases = [(128, 128, 3, 1, 1, 48), (256, 144, 3, 2, 2, 48), (128, 256, 3, 1, 1, 24), (64, 128, 1, 0, 1, 24)]        # (cout, cin, k, pad, dil, map)
@@ -1313,7 +1356,7 @@ def test_f32_winograd_filter_refresh_after_optimizer_step(K):
         K.filter_transform_count(True)
         n0 = K.filter_transform_count()
         opt.step()                                                   # moves the weights, bumps the versions, refreshes the kept transforms in one launch
-        assert all(e[1] == w._version for e in K._U_CACHE.values() for w in ws if (e[0]() is w))
+        assert all(e.version == w._version for e in K._U_CACHE.values() for w in ws if (e.owner() is w))
         second = run()
         assert K.filter_transform_count() == n0                      # no forward call transformed its filter again
         K.filter_transform_count(False)
@@ -1322,12 +1365,12 @@ def test_f32_winograd_filter_refresh_after_optimizer_step(K):
         for a, b in zip(second, run()):
             assert torch.equal(a, b)
         K.KEEP_WINOGRAD_U = None
-        assert K.refresh_f32_filters() == 0                          # nothing out of date: no launch
+        assert K.refresh_filters() == 0                              # nothing out of date: no launch
     finally:
         K.filter_transform_count(False)
         K.KEEP_WINOGRAD_U = was
         K.unregister_filter_owners()
-        K._U_CACHE.clear()
+        K.clear_filters()
 
 
 def test_conv_bf16_tier_mixed_edges(K):

@@ -1042,7 +1042,7 @@ def test_three_agg_steps_vs_oracle(env):
 
     def run_hip(keep_u):
         prev = K.KEEP_WINOGRAD_U
-        K._U_CACHE.clear()
+        K.clear_filters()
         try:
             net = synth.load_det_weights(env['deepv3plus'].DeepR50V3PlusD(synth.model_args(), 19, CRIT, CRIT)).cuda()
             net.dsn[3].p = 0.0
