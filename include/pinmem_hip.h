@@ -383,6 +383,17 @@ size_t pm_label_class_weights_workspace(int n);
 int pm_label_class_weights(const int64_t* labels, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* Validation sweep (train.py:847-939 per batch: Upsample -> criterion -> output.max(1)[1] -> fast_hist) in one pass over the labels, the up-sampled logits never
+ * materialised. Inputs and loss_out as pm_upsample_ce_fwd (same interpolation expression, same fixed-order reduce). Per hi-res pixel: pred = the LOWEST class index
+ * among the maxima of the interpolated logits; hist[label][pred] += 1 for 0 <= label < C (fast_hist's mask, utils/misc.py:65-70; 255 and any other value are
+ * skipped); pred, when given, is written as one byte for EVERY pixel, ignored ones included. hist: int64 [C][C], row = label, column = prediction; accumulate 0:
+ * overwritten, 1: added to (a whole validation epoch sums into one histogram without a host round trip). Integer counts and a fixed-order loss: deterministic, and
+ * independent of how the rows are dealt to blocks. The workspace query answers 0 for a shape the kernel does not take (two low-res logit rows do not fit LDS: more than
+ * ~1000 low-res columns at 19 classes), as pm_upsample_ce_field_bytes does; the call then returns PM_EUNSUPPORTED. */
+size_t pm_upsample_eval_workspace(const pm_tensor* logits, int H, int W);
+int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, int64_t* hist, int accumulate,
+                     uint8_t* pred /* nullable, [n][H][W] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- K7 memory read (memory.py:317-336 + get_score :167-189) ---------------------------------------------------
  * x: [N rows of d=256] (NHWC feature map); mem [m<=32][d]; writes qr = [qhat | P_m.M] (2d channels, input of
  * memory.output), score S [N][m] (raw cosine scores), P_m [N][m] (softmax over slots, or gumbel if noise given). */

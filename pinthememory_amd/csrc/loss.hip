@@ -803,6 +803,165 @@ extern "C" int pm_upsample_ce_bwd(const pm_tensor* logits, float inv_temp, const
 }
 
 
+// ---- validation sweep: loss + predicted class + confusion matrix of the up-sampled logits (train.py:847-939 per batch: Upsample -> criterion -> max(1)[1] -> fast_hist) ---
+// The row-staged forward with two more products per pixel. Block = EVAL rows-per-block consecutive hi-res rows of one image: rows that share a low-res row pair stage it
+// once, and when the walk moves one low-res row down the lower staged row becomes the upper one (pointer swap) and only one row is staged. Nothing in the result depends
+// on how rows are dealt to blocks: the interpolation is per pixel, the loss partial is per HI-RES ROW (reduced over its columns in the fixed order of
+// ce_fwd_rows_kernel: lane X, X + 256, ..., wave sum, four waves), and the counts are integers. Counts: C x C unsigned LDS counters per block through LDS integer adds,
+// one count row per block in the workspace, folded by integer adds into the int64 histogram (the label_count_kernel / label_weights_kernel pattern).
+namespace {
+constexpr int EVAL_MAX_ROWS = 8;                   // hi-res rows per block, at most
+constexpr size_t EVAL_MAX_LDS = 159 * 1024;        // dynamic part (two staged rows + the counters); the kernel also declares 256 B of static LDS
+constexpr int EVAL_FOLD_T = 1024;                  // fold kernel: 32 histogram entries x 32 slices of the count rows
+
+struct EvalPlan {
+  bool ok;
+  int rows, chunks;      // hi-res rows per block, blocks per image
+  size_t lds, part_bytes, bytes;
+};
+inline EvalPlan eval_plan(int n, int h, int w, int C, int H, int W) {
+  EvalPlan p{};
+  if (n < 1 || h < 1 || w < 1 || C < 1 || C > MAXC || H < 1 || W < 1) return p;
+  p.lds = ((size_t)2 * w * (C | 1) + (size_t)C * C) * sizeof(float);
+  if (p.lds > EVAL_MAX_LDS || (long)n * H > (1l << 22)) return p;
+  // about as many rows as share one low-res pair, fewer while that leaves under two blocks per CU of the largest part (256 CUs)
+  p.rows = std::max(1, std::min(EVAL_MAX_ROWS, (H + h - 1) / h));
+  while (p.rows > 1 && (long)n * ((H + p.rows - 1) / p.rows) < 512) --p.rows;
+  p.chunks = (H + p.rows - 1) / p.rows;
+  p.part_bytes = pm_align_up((size_t)n * H * 2 * sizeof(float), 256);
+  p.bytes = p.part_bytes + pm_align_up((size_t)n * p.chunks * C * C * sizeof(unsigned), 256);
+  p.ok = true;
+  return p;
+}
+
+__device__ __forceinline__ void eval_stage_row(const CEGeom& g, int C, int CP, int b, int y, float* dst) {
+  const float* src = g.logits + ((long)(b * g.h + y) * g.w) * g.lp;
+  for (int i = threadIdx.x; i < g.w * C; i += 256) {
+    const int xl = i / C, c = i - xl * C;
+    dst[xl * CP + c] = src[(long)xl * g.lp + c] * g.inv_temp;
+  }
+}
+
+template <int C_>
+__global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int rows, int chunks, float* __restrict__ part, unsigned* __restrict__ counts,
+                                                           uint8_t* __restrict__ pred) {
+  extern __shared__ float L[];
+  __shared__ float sm[EVAL_MAX_ROWS][2][4];
+  const int C = C_ > 0 ? C_ : g.C;
+  const int CP = C | 1;
+  const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
+  const int b = bid / chunks, Y0 = (bid - b * chunks) * rows, Y1 = min(g.H, Y0 + rows);
+  float* L0 = L;
+  float* L1 = L + (size_t)g.w * CP;
+  unsigned* cnt = reinterpret_cast<unsigned*>(L + (size_t)2 * g.w * CP);
+  for (int i = threadIdx.x; i < C * C; i += 256) cnt[i] = 0u;      // visible after the first row's staging barrier
+  int s0 = -1, s1 = -1;      // the low-res rows in L0, L1
+  for (int Y = Y0; Y < Y1; ++Y) {
+    const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
+    const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
+    int64_t labs[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) labs[u] = (int)threadIdx.x + 256 * u < g.W ? lrow[threadIdx.x + 256 * u] : 255;   // in flight while the rows are staged
+    if (ly.i0 != s0 || ly.i1 != s1) {      // uniform over the block
+      __syncthreads();                     // every lane has finished the previous row's reads
+      if (ly.i0 == s1) {                   // one low-res row down: the lower row becomes the upper one
+        float* t = L0;
+        L0 = L1, L1 = t;
+        s0 = s1, s1 = -1;
+      }
+      if (ly.i0 != s0) eval_stage_row(g, C, CP, b, ly.i0, L0), s0 = ly.i0;
+      if (ly.i1 != s1) eval_stage_row(g, C, CP, b, ly.i1, L1), s1 = ly.i1;
+      __syncthreads();
+    }
+    uint8_t* prow = pred ? pred + ((long)b * g.H + Y) * g.W : nullptr;
+    float lsum = 0.f, lcnt = 0.f;
+    for (int X = threadIdx.x, u = 0; X < g.W; X += 256, ++u) {
+      const int64_t lab = u < 3 ? (u == 0 ? labs[0] : (u == 1 ? labs[1] : labs[2])) : lrow[X];
+      if (lab == 255 && !prow) continue;
+      const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
+      const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
+      float v[C_ > 0 ? C_ : MAXC];
+      float mx = -INFINITY, vl = 0.f;
+      int arg = 0;
+#pragma unroll
+      for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+        if (c < C) {
+          v[c] = ly.w0 * (lx.w0 * p00[c] + lx.w1 * p01[c]) + ly.w1 * (lx.w0 * p10[c] + lx.w1 * p11[c]);
+          if (v[c] > mx) mx = v[c], arg = c;      // strict: the lowest index among the maxima, as output.max(1)[1]
+          if (c == (int)lab) vl = v[c];
+        }
+      if (prow) prow[X] = (uint8_t)arg;           // every pixel, ignored ones included
+      if (lab == 255) continue;
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+        if (c < C) se += __expf(v[c] - mx);
+      lsum += (mx + logf(se)) - vl;
+      lcnt += 1.f;
+      if (lab >= 0 && lab < C) atomicAdd(&cnt[(int)lab * C + arg], 1u);      // fast_hist's mask (utils/misc.py:65-70)
+    }
+    lsum = pm_wave_sum(lsum);
+    lcnt = pm_wave_sum(lcnt);
+    if ((threadIdx.x & 63) == 0) sm[Y - Y0][0][threadIdx.x >> 6] = lsum, sm[Y - Y0][1][threadIdx.x >> 6] = lcnt;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < Y1 - Y0) {
+    const float* s = &sm[threadIdx.x][0][0];
+    const long r = (long)b * g.H + Y0 + threadIdx.x;
+    part[r * 2] = s[0] + s[1] + s[2] + s[3];
+    part[r * 2 + 1] = s[4] + s[5] + s[6] + s[7];
+  }
+  for (int i = threadIdx.x; i < C * C; i += 256) counts[(long)bid * C * C + i] = cnt[i];
+}
+
+// hist[e] (+)= sum over the blocks' count rows: 32 entries x 32 slices of the rows per block, integer adds only
+__global__ __launch_bounds__(EVAL_FOLD_T) void eval_fold_kernel(const unsigned* __restrict__ counts, int nblk, int entries, int accumulate, int64_t* __restrict__ hist) {
+  __shared__ unsigned long long tot[32];
+  const int e = blockIdx.x * 32 + (threadIdx.x & 31), sl = threadIdx.x >> 5;
+  if (threadIdx.x < 32) tot[threadIdx.x] = 0ull;
+  __syncthreads();
+  unsigned long long a = 0ull;
+  if (e < entries)
+    for (int r = sl; r < nblk; r += EVAL_FOLD_T / 32) a += counts[(long)r * entries + e];
+  if (a) atomicAdd(&tot[threadIdx.x & 31], a);
+  __syncthreads();
+  if (threadIdx.x < 32 && e < entries) hist[e] = (accumulate ? hist[e] : 0) + (int64_t)tot[threadIdx.x];
+}
+
+template <int CC>
+void eval_launch(const CEGeom& g, const EvalPlan& p, float* part, unsigned* counts, uint8_t* pred, hipStream_t st) {
+  static pm_lds_optin optin;      // > 64 KB of dynamic LDS (rows wider than ~420 pixels x 19 classes: one Cityscapes image has 512) needs the opt-in
+  (void)optin(reinterpret_cast<const void*>(&ce_eval_rows_kernel<CC>), (int)EVAL_MAX_LDS);
+  hipLaunchKernelGGL(ce_eval_rows_kernel<CC>, dim3(g.n * p.chunks), dim3(256), p.lds, st, g, p.rows, p.chunks, part, counts, pred);
+}
+}  // namespace
+
+extern "C" size_t pm_upsample_eval_workspace(const pm_tensor* logits, int H, int W) {
+  if (!logits || !pm_is_f32(logits)) return 0;      // fp32 tensors only
+  return eval_plan(logits->n, logits->h, logits->w, logits->c, H, W).bytes;      // 0: the two low-res rows + the counters do not fit LDS
+}
+
+extern "C" int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, int64_t* hist, int accumulate,
+                                uint8_t* pred, void* ws, size_t ws_bytes, void* stream) {
+  PM_REQUIRE_F32(logits, "upsample_eval");
+  CEGeom g;
+  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_eval")) return e;
+  PM_REQUIRE(loss_out && hist, PM_EINVAL, "upsample_eval: null loss_out / hist");
+  PM_REQUIRE(accumulate == 0 || accumulate == 1, PM_EINVAL, "upsample_eval: accumulate %d is neither 0 nor 1", accumulate);
+  const EvalPlan p = eval_plan(g.n, g.h, g.w, g.C, H, W);
+  PM_REQUIRE(p.ok, PM_EUNSUPPORTED, "upsample_eval: logit rows of %d x %d classes do not fit LDS (or n x H = %d x %d rows > 2^22)", g.w, g.C, g.n, H);
+  PM_REQUIRE(ws && ws_bytes >= p.bytes, PM_EWORKSPACE, "upsample_eval: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)ws;
+  unsigned* counts = (unsigned*)((char*)ws + p.part_bytes);
+  if (g.C == 19) eval_launch<19>(g, p, part, counts, pred, st);
+  else eval_launch<0>(g, p, part, counts, pred, st);
+  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, g.n * H, loss_out);
+  hipLaunchKernelGGL(eval_fold_kernel, dim3((g.C * g.C + 31) / 32), dim3(EVAL_FOLD_T), 0, st, (const unsigned*)counts, g.n * p.chunks, g.C * g.C, accumulate, hist);
+  return pm_check_launch("upsample_eval");
+}
+
+
 // ---- weighted forms: CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d (loss.py:20-43,71-88,120-180) ---------------------------------------------------------
 // Same kernels (WT = true), same routing between them as the unweighted entry points, same field layout. Block partials are (sum w nll, sum w), image-major.
 namespace {

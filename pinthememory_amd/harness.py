@@ -454,6 +454,65 @@ def miou(hist):
     return float(torch.nanmean(iu)), iu
 
 
+# ---- the validation loop every training script runs after each epoch (train.py:847-939) ---------------------------------------
+def validate(net, batches, criterion=None, classes=19, dump=10):
+    """train.py:847-939 without the logging, the checkpointing and the distributed reduce (the caller sums `hist` across ranks where the reference
+    all-reduces iou_acc). Per batch: one eval forward that returns the head's LOW-RES logits, then one kernel that up-samples them, evaluates the
+    criterion, takes output.max(1)[1] and adds fast_hist into the running histogram (K.upsample_eval) -- the [n,19,H,W] logits are never written and
+    nothing is copied to the host before the last batch. `batches` yields (inputs, gt, ...); a [B,D,C,H,W] input is flattened (:872-875). A criterion
+    other than the plain CrossEntropyLoss(ignore_index=255), or a shape the kernel does not take, goes through resize + criterion + argmax + fast_hist
+    on the device (correct, not tuned). The loss means carry the reference's AverageMeter weighting: each batch's mean by n*H*W, ignored pixels
+    included (:880,903). The class maps of the first `dump` batches are kept (the reference's image dumps). Leaves the net in eval mode.
+    -> dict(val_loss, read_loss (None without the memory), hist int64 [C,C] on the device, mean_iu, iu, predictions: list of uint8 [n,H,W])."""
+    from .network.deepv3plus import fused_ce_ok
+    m = net.module if hasattr(net, 'module') else net
+    device = next(m.parameters()).device
+    with_memory = bool(getattr(m.args, 'memory', False))
+    fused = criterion is None or fused_ce_ok(criterion)
+    net.eval()
+    hist = torch.zeros((classes, classes), dtype=torch.int64, device=device)
+    sums = torch.zeros(3, dtype=torch.float64, device=device)      # sum of loss * pixels, of read loss * pixels, of pixels
+    predictions = []
+    was = m.eval_logits_lowres
+    m.eval_logits_lowres = True
+    try:
+        with torch.no_grad():
+            for idx, data in enumerate(batches):
+                inputs, gt = data[0], data[1]
+                if inputs.dim() == 5:
+                    inputs = inputs.reshape(-1, *inputs.shape[2:])
+                    gt = gt.reshape(-1, *inputs.shape[2:])
+                assert inputs.dim() == 4 and gt.dim() == 3 and inputs.shape[2:] == gt.shape[1:]
+                pixels = inputs.shape[0] * inputs.shape[2] * inputs.shape[3]
+                inputs, gt = inputs.to(device), gt.to(device).contiguous()
+                outputs = net(inputs)
+                low = outputs[0]
+                assert low.shape[1] == classes
+                lv = ops.nhwc(low)
+                if fused and K.upsample_eval_ok(lv, tuple(gt.shape[1:])):
+                    loss_out, _, pred = K.upsample_eval(lv, gt, 1.0, hist=hist, want_pred=idx < dump)
+                    loss = loss_out[0]
+                else:
+                    full = ops.resize(low, tuple(gt.shape[1:]))
+                    loss = F.cross_entropy(full, gt, ignore_index=255) if criterion is None else criterion(full, gt)
+                    pred = full.argmax(1)
+                    hist += fast_hist(pred, gt, classes)
+                    pred = pred.to(torch.uint8)
+                if idx < dump:
+                    predictions.append(pred)
+                sums[0] += loss.double() * pixels
+                sums[2] += pixels
+                if with_memory:
+                    query = F.normalize(outputs[-1], dim=1).permute(0, 2, 3, 1).contiguous()
+                    sums[1] += m.memory.get_score(query, gt, m.memory.m_items)[-1].double() * pixels
+    finally:
+        m.eval_logits_lowres = was
+    sums = sums.cpu()
+    mean_iu, iu = miou(hist)
+    return dict(val_loss=float(sums[0] / sums[2]), read_loss=float(sums[1] / sums[2]) if with_memory else None, hist=hist, mean_iu=mean_iu, iu=iu,
+                predictions=predictions)
+
+
 # ---- the meta-learning regime every pinmem script runs: train_memory_mldg (train.py:493-632) ----------------------------
 def put_theta(model, theta):
     """train.py:262-277: rewire every leaf module's _parameters with (non-leaf) tensors; the HIP ops take weights as

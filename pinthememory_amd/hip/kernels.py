@@ -865,6 +865,34 @@ def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image,
     return dl
 
 
+# ---- validation sweep: loss + argmax + confusion matrix of the up-sampled logits (train.py:847-939) -------------------------------
+def upsample_eval_ok(logits, label_hw):
+    """Can the validation kernel take this shape (two low-res logit rows in LDS: up to ~1000 low-res columns at 19 classes)?"""
+    return _sizes(('eval', logits.shape, logits.stride(), tuple(label_hw)), lambda: _lib().pm_upsample_eval_workspace(byref(tdesc(logits)), label_hw[0], label_hw[1])) != 0
+
+
+def upsample_eval(logits, labels, inv_temp=1.0, hist=None, want_pred=False, accumulate=True, pred=None):
+    """-> (loss_out[2], hist, pred or None): mean CE (ignore 255) and valid count as upsample_ce_fwd, the confusion matrix hist[label][prediction] (int64 [C, C]; created
+    zeroed when None, else added to -- overwritten with accumulate=False) and, with want_pred, the uint8 [n, H, W] class map (`pred`: a buffer to write it into)."""
+    n, H, W = labels.shape
+    C = logits.shape[3]
+    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous()
+    if hist is None:
+        hist = torch.zeros((C, C), dtype=torch.int64, device=logits.device)
+    assert hist.dtype == torch.int64 and hist.is_cuda and hist.is_contiguous() and tuple(hist.shape) == (C, C)
+    if pred is None and want_pred:
+        pred = torch.empty((n, H, W), dtype=torch.uint8, device=logits.device)
+    if pred is not None:
+        assert pred.dtype == torch.uint8 and pred.is_cuda and pred.is_contiguous() and tuple(pred.shape) == (n, H, W)
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    lib, ld = _lib(), tdesc(logits)
+    nb = lib.pm_upsample_eval_workspace(byref(ld), H, W)
+    ws = workspace(nb, logits.device)
+    check(lib.pm_upsample_eval(byref(ld), inv_temp, labels.data_ptr(), H, W, out.data_ptr(), hist.data_ptr(), int(bool(accumulate)), ptr(pred), ptr(ws), nb,
+                               stream()), 'pm_upsample_eval')
+    return out, hist, pred
+
+
 # ---- memory ---------------------------------------------------------------------------------------------------------
 def mem_read_fwd(x, mem, noise=None):
     n, h, w, d = x.shape

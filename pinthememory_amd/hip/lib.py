@@ -138,6 +138,8 @@ SIGNATURES = {
     'pm_upsample_wce_bwd_field': (_i, [_T, _f, _i, _i, _i, _vp, _vp, _vp, _T, _vp]),
     'pm_label_class_weights_workspace': (_sz, [_i]),
     'pm_label_class_weights': (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    'pm_upsample_eval_workspace': (_sz, [_T, _i, _i]),
+    'pm_upsample_eval': (_i, [_T, _f, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'pm_mem_read_fwd': (_i, [_T, _vp, _i, _vp, _T, _vp, _vp, _vp]),
     'pm_mem_read_fwd_pq_workspace': (_sz, [_i64, _i]),
     'pm_mem_read_fwd_pq': (_i, [_T, _vp, _i, _vp, _vp, _T, _vp, _vp, _vp, _vp, _sz, _vp]),
