@@ -41,8 +41,10 @@ typedef struct pm_tensor {      /* NHWC activation view */
 
 /* ABI version of this header (pm_version() returns the library's). The two structs below carry their own size as first member: an entry point that
  * receives a struct built against another header returns PM_EINVAL instead of reading past the caller's object (they grew in rounds 2 and 3).
- * 400 (round 4): pm_tensor carries dtype + flags (bf16 activation tier). */
-#define PM_ABI_VERSION 400
+ * 400 (round 4): pm_tensor carries dtype + flags (bf16 activation tier).
+ * 410: pm_aug_image and the augmenting input edge (pm_augment_u8, pm_labels_u8_flip_to_i64); the size of that struct is an ARGUMENT of the calls that read it,
+ * because the array lives in device memory where the library cannot look at a first member. */
+#define PM_ABI_VERSION 410
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -329,6 +331,38 @@ int pm_argmax_f64(const double* buffer, int n, int h, int w, int c, int64_t* out
  * uint8 label maps -> int64. Cuts the host->device traffic of a batch 4x (images) / 8x (labels). */
 int pm_image_u8_to_nhwc4(const uint8_t* img_nhw3, int64_t pixels, const float* mean3, const float* std3, float* out_nhwc4, void* stream);
 int pm_labels_u8_to_i64(const uint8_t* lab, int64_t n, int64_t* out, void* stream);
+
+/* ---- augmenting input edge: what the training scripts run per image on the host before ToTensor (datasets/__init__.py:63-95 `--color_aug 0.5 --gblur`, :128-144 the
+ * hard augmentation of the meta-test domains; transforms/transforms.py:179-187 RandomGaussianBlur; transforms/joint_transforms.py RandomHorizontallyFlip), on uint8
+ * pixels in HBM, quantised to uint8 after every step as PIL / skimage do:
+ *   colour: torchvision 0.10 ColorJitter on PIL -- ImageEnhance.Brightness / Contrast / Color = Image.blend(degenerate, image, factor) in float32 (truncating inside
+ *     [0, 1], clipping outside) with degenerate = black / the rounded mean of convert("L") over the whole image in its state before the op / convert("L"); hue = PIL's
+ *     RGB -> HSV, H += hue_shift mod 256, HSV -> RGB. The ops run in the image's own order; an op whose bit in `enabled` is clear is skipped.
+ *   blur (radius > 0): skimage 0.16 gaussian(multichannel=True) = scipy correlate1d along H then W in float64 on x / 255.0, edges clamped, each output
+ *     centre * w[0] + sum over j = radius .. 1 of (x[-j] + x[+j]) * w[j] (scipy's order, unfused), then (uint8)(y * 255).
+ *   flip: image and label columns mirrored.
+ * The colour bytes are PIL's; the blurred bytes are scipy's. Then ToTensor + Normalize with the arithmetic of pm_image_u8_to_nhwc4: an image with no op, radius 0 and
+ * no flip gives that entry point's bytes. */
+typedef struct pm_aug_image {   /* one per image, in DEVICE memory */
+  uint8_t order[4];             /* a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue (torchvision's fn_idx); NOT checked on the device */
+  uint8_t enabled;              /* bit i: op i runs */
+  uint8_t flip;                 /* != 0: mirror the columns */
+  uint8_t hue_shift;            /* (int)(hue_factor * 255) & 255 */
+  uint8_t reserved;
+  float brightness, contrast, saturation;      /* blend factors */
+  int32_t radius;               /* 0: no blur; else 1 .. 5 (values outside are clamped on the device) */
+  double w[6];                  /* blur weights: centre, then one side (pm_aug_blur_weights) */
+} pm_aug_image;
+/* host only: scipy.ndimage's Gaussian kernel for truncate = 4.0 -- radius = (int)(4 sigma + 0.5), w[k] = exp(-0.5 / sigma^2 * k^2) / sum over -radius .. radius, summed as
+ * numpy's add.reduce does; w6[radius + 1 ..] = 0. sigma outside (0, 1.375) needs a radius beyond 5: PM_EUNSUPPORTED. */
+int pm_aug_blur_weights(double sigma, int32_t* radius, double* w6);
+size_t pm_augment_workspace(int n);      /* one exact integer grey sum per image */
+/* img_nhw3 uint8 [n][H][W][3]; params_dev: n structs of struct_size = sizeof(pm_aug_image) bytes in device memory; out_nhwc4 float [n][H][W][4] (16-byte aligned, pad lane 0)
+ * and / or out_u8 uint8 [n][H][W][3] (the augmented pixels before ToTensor): either may be NULL, not both; neither may alias img. Deterministic (integer atomics). */
+int pm_augment_u8(const uint8_t* img_nhw3, int n, int H, int W, const pm_aug_image* params_dev, int32_t struct_size, const float* mean3, const float* std3,
+                  float* out_nhwc4, uint8_t* out_u8, void* ws, size_t ws_bytes, void* stream);
+/* pm_labels_u8_to_i64 with the columns of image i mirrored where params_dev[i].flip != 0 */
+int pm_labels_u8_flip_to_i64(const uint8_t* lab, int n, int H, int W, const pm_aug_image* params_dev, int32_t struct_size, int64_t* out, void* stream);
 
 /* ---- layout edges ------------------------------------------------------------------------------------------------ */
 int pm_nchw_to_nhwc(const float* x_nchw, int c_src, const pm_tensor* y, void* stream);   /* zero-fills y.c > c_src */

@@ -713,11 +713,89 @@ def image_u8_to_nhwc4(img_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     return out
 
 
-def labels_u8_to_i64(lab_u8):
+def labels_u8_to_i64(lab_u8, params=None):
+    """uint8 label maps -> int64. params (aug_params / upload_aug_params of the batch, lab_u8 then [N,H,W]): the columns of every image whose flip flag is set are mirrored."""
     assert lab_u8.dtype == torch.uint8 and lab_u8.is_contiguous()
     out = torch.empty(lab_u8.shape, dtype=torch.int64, device=lab_u8.device)
-    check(_lib().pm_labels_u8_to_i64(lab_u8.data_ptr(), lab_u8.numel(), out.data_ptr(), stream()), 'pm_labels_u8_to_i64')
+    if params is None:
+        check(_lib().pm_labels_u8_to_i64(lab_u8.data_ptr(), lab_u8.numel(), out.data_ptr(), stream()), 'pm_labels_u8_to_i64')
+        return out
+    n, h, w = lab_u8.shape
+    pd = upload_aug_params(params, lab_u8.device, n)
+    check(_lib().pm_labels_u8_flip_to_i64(lab_u8.data_ptr(), n, h, w, pd.data_ptr(), ctypes.sizeof(L.PmAugImage), out.data_ptr(), stream()), 'pm_labels_u8_flip_to_i64')
     return out
+
+
+# ---- augmenting input edge (csrc/augment.hip) ------------------------------------------------------------------------------
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = 0, 1, 2, 3      # torchvision's fn_idx values = bit positions of pm_aug_image.enabled
+AUG_MAX_RADIUS = 5
+
+
+def aug_blur_weights(sigma):
+    """(radius, [w0 .. w5]) of scipy.ndimage's Gaussian kernel with truncate = 4.0 (host only). sigma outside (0, 1.375) raises."""
+    r, w = ctypes.c_int32(), (ctypes.c_double * 6)()
+    check(_lib().pm_aug_blur_weights(float(sigma), byref(r), w), 'pm_aug_blur_weights')
+    return r.value, list(w)
+
+
+def aug_params(n):
+    """A host array of n pm_aug_image structs that do nothing: identity order, no op enabled, no flip, no blur."""
+    arr = (L.PmAugImage * n)()
+    for p in arr:
+        p.order[:] = (0, 1, 2, 3)
+        p.brightness = p.contrast = p.saturation = 1.0
+    return arr
+
+
+def set_aug_image(p, order=(0, 1, 2, 3), enabled=0, flip=False, hue=0.0, brightness=1.0, contrast=1.0, saturation=1.0, sigma=0.0):
+    """Fill one pm_aug_image from the quantities the host pipeline draws: hue is torchvision's hue_factor in [-0.5, 0.5] (the shift is np.uint8(hue * 255) as the
+    reference's numpy computed it: truncated toward zero, wrapped to a byte), sigma 0 = no blur."""
+    p.order[:] = [int(o) for o in order]
+    p.enabled, p.flip, p.hue_shift = int(enabled), 1 if flip else 0, int(hue * 255) & 255
+    p.brightness, p.contrast, p.saturation = float(brightness), float(contrast), float(saturation)
+    if sigma > 0:
+        p.radius, w = aug_blur_weights(sigma)
+        p.w[:] = w
+    else:
+        p.radius = 0
+        p.w[:] = [0.0] * 6
+    return p
+
+
+def upload_aug_params(params, device, n=None):
+    """Host pm_aug_image array -> the device copy the kernels read: checked here for what the device cannot report (order a permutation, radius <= 5), staged in
+    pinned memory and copied without blocking on the current stream (no host synchronisation: the prefetcher's side stream keeps running; the pinned block returns to
+    torch's host allocator, which holds it until the copy has run). A tensor that already went through here is passed on, so one upload serves image and labels."""
+    size = ctypes.sizeof(L.PmAugImage)
+    if isinstance(params, torch.Tensor):
+        assert params.is_cuda and params.dtype == torch.uint8 and params.is_contiguous() and params.numel() % size == 0, 'not an upload_aug_params tensor'
+        assert n is None or params.numel() == n * size, 'augmentation parameters for %d images, batch of %d' % (params.numel() // size, n)
+        return params
+    assert n is None or len(params) == n, 'augmentation parameters for %d images, batch of %d' % (len(params), n)
+    for i, p in enumerate(params):
+        if sorted(p.order) != [0, 1, 2, 3]:
+            raise ValueError('pm_aug_image[%d].order %s is not a permutation of 0..3' % (i, list(p.order)))
+        if not 0 <= p.radius <= AUG_MAX_RADIUS:
+            raise ValueError('pm_aug_image[%d].radius %d outside 0..%d' % (i, p.radius, AUG_MAX_RADIUS))
+    host = torch.empty(max(len(params), 1) * size, dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(host.data_ptr(), ctypes.addressof(params), len(params) * size)
+    return host.to(device, non_blocking=True)
+
+
+def augment_u8(img_u8, params, want_u8=False, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """uint8 [N,H,W,3] -> colour jitter, Gaussian blur, horizontal flip per image as `params` says (aug_params / input_edge.PhotometricAugment.sample, or their
+    upload_aug_params copy), then ToTensor + Normalize: fp32 NHWC4 [N,H,W,4] with a zero 4th channel. want_u8: also the augmented uint8 pixels, (float, uint8)."""
+    n, h, w, c = img_u8.shape
+    assert c == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.is_cuda
+    pd = upload_aug_params(params, img_u8.device, n)
+    out = torch.empty((n, h, w, 4), dtype=torch.float32, device=img_u8.device)
+    out8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=img_u8.device) if want_u8 else None
+    m, s = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    need = _lib().pm_augment_workspace(n)
+    ws = workspace(need, img_u8.device)
+    check(_lib().pm_augment_u8(img_u8.data_ptr(), n, h, w, pd.data_ptr(), ctypes.sizeof(L.PmAugImage), m, s, out.data_ptr(), ptr(out8), ws.data_ptr(), need, stream()),
+          'pm_augment_u8')
+    return (out, out8) if want_u8 else out
 
 
 def nchw_to_nhwc(x, c_pad=None):

@@ -39,6 +39,12 @@ class PmRouting(ctypes.Structure):
                 ('conv16_persistent', c_int32), ('wgrad16', c_int32), ('bf16_wgrad', c_int32), ('split', c_int32)]
 
 
+class PmAugImage(ctypes.Structure):
+    """include/pinmem_hip.h pm_aug_image: the augmentation of one image (an array of these lives in device memory)."""
+    _fields_ = [('order', ctypes.c_uint8 * 4), ('enabled', ctypes.c_uint8), ('flip', ctypes.c_uint8), ('hue_shift', ctypes.c_uint8), ('reserved', ctypes.c_uint8),
+                ('brightness', c_float), ('contrast', c_float), ('saturation', c_float), ('radius', c_int32), ('w', ctypes.c_double * 6)]
+
+
 class PmConvEpilogue(ctypes.Structure):
     _fields_ = [('struct_size', c_int64), ('bias', c_void_p), ('scale', c_void_p), ('shift', c_void_p), ('residual', c_void_p),
                 ('residual_pitch', c_int64), ('relu', c_int32), ('bn_partials', c_void_p), ('bn_partials_bytes', c_int64)]
@@ -52,7 +58,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 400          # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 410          # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -121,6 +127,10 @@ SIGNATURES = {
     'pm_argmax_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pm_image_u8_to_nhwc4': (_i, [_vp, _i64, POINTER(c_float), POINTER(c_float), _vp, _vp]),
     'pm_labels_u8_to_i64': (_i, [_vp, _i64, _vp, _vp]),
+    'pm_aug_blur_weights': (_i, [ctypes.c_double, POINTER(c_int32), POINTER(ctypes.c_double)]),
+    'pm_augment_workspace': (_sz, [_i]),
+    'pm_augment_u8': (_i, [_vp, _i, _i, _i, _vp, c_int32, POINTER(c_float), POINTER(c_float), _vp, _vp, _vp, _sz, _vp]),
+    'pm_labels_u8_flip_to_i64': (_i, [_vp, _i, _i, _i, _vp, c_int32, _vp, _vp]),
     'pm_nchw_to_nhwc': (_i, [_vp, _i, _T, _vp]),
     'pm_nhwc_to_nchw': (_i, [_T, _vp, _vp]),
     'pm_label_nearest': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),

@@ -8,6 +8,10 @@ fewer PCIe bytes -- in pinned memory; the copy runs on a side stream while the p
 the int64 widening are two small kernels on that same stream (`pm_image_u8_to_nhwc4`, `pm_labels_u8_to_i64`).
 
 `SyntheticDomainSource` is the stand-in for the loader (no datasets in this build); `DevicePrefetcher` is the product part.
+
+The photometric augmentation the reference's training scripts run per image on the host before ToTensor (`--color_aug 0.5 --gblur`, datasets/__init__.py:63-95;
+the hard ColorJitter(0.8, 0.8, 0.8, 0.3) + blur of the meta-test domains, :128-144; RandomHorizontallyFlip) runs here on the uint8 pixels already in HBM
+(`pm_augment_u8`, `pm_labels_u8_flip_to_i64`): `PhotometricAugment` draws the per-image parameters on the host, the prefetcher launches the kernels on its side stream.
 """
 import torch
 
@@ -52,13 +56,71 @@ class SyntheticDomainSource:
         return img, lab
 
 
+class PhotometricAugment:
+    """Per-image parameters of the device-side augmentation, drawn on the host with the DISTRIBUTIONS of the reference's pipeline (torchvision 0.10, which it pins):
+    ColorJitter(brightness, contrast, saturation, hue) -- factors uniform in [max(0, 1 - b), 1 + b], hue uniform in [-h, h], the four ops in a uniformly random
+    order -- applied as a whole with probability p (RandomApply); RandomGaussianBlur's sigma = 0.15 + U[0, 1) * 1.15 with `blur`; a horizontal flip with probability
+    0.5 with `flip`. Images flagged `hard` (the meta-test domains of train.py:199-211, get_meta_transforms) always get the jitter, at the `hard` strengths.
+
+    The STREAM of random numbers is this class's own, not torchvision's or `random`'s: image j since construction (counted across calls) draws from a host
+    torch.Generator seeded with (seed, j). So the result depends on (seed, position of the image in the sequence of all sampled images) alone -- the same
+    for the same seed and call sequence, and unchanged when the same images are sampled in calls of other sizes. `last` keeps the raw draws of the latest call."""
+
+    def __init__(self, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p=0.5, blur=True, flip=True, hard=(0.8, 0.8, 0.8, 0.3), seed=0):
+        self.soft, self.hard = (brightness, contrast, saturation, hue), tuple(hard)
+        assert all(v >= 0 for v in self.soft + self.hard) and self.soft[3] <= 0.5 and self.hard[3] <= 0.5, 'ColorJitter strengths: >= 0, hue <= 0.5'
+        self.p, self.blur, self.flip, self.seed = p, blur, flip, seed
+        self.count = 0          # images sampled so far
+        self.last = None
+
+    def sample(self, n, hard=None):
+        """Host array of n pm_aug_image structs (K.aug_params); hard: one bool per image, or None for none."""
+        hard = [False] * n if hard is None else [bool(h) for h in hard]
+        assert len(hard) == n
+        arr = K.aug_params(n)
+        last = dict(applied=[], factors=[], hue=[], sigma=[], flip=[], order=[])
+        for i in range(n):
+            g = torch.Generator().manual_seed((self.seed * 1000003 + self.count + i) & 0x7fffffffffffffff)
+            u = torch.rand(7, generator=g, dtype=torch.float64).tolist()
+            order = torch.randperm(4, generator=g).tolist()
+            b, c, s, h = self.hard if hard[i] else self.soft
+            applied = hard[i] or u[0] < self.p
+            factors = [max(0.0, 1.0 - v) + u[1 + k] * (1.0 + v - max(0.0, 1.0 - v)) for k, v in enumerate((b, c, s))]
+            hue = -h + u[4] * 2.0 * h
+            sigma = 0.15 + u[5] * 1.15 if self.blur else 0.0
+            flip = self.flip and u[6] < 0.5
+            enabled = sum(1 << k for k, v in enumerate((b, c, s, h)) if v > 0) if applied else 0      # a zero strength is torchvision's None: the op does not run
+            K.set_aug_image(arr[i], order, enabled, flip, hue, factors[0], factors[1], factors[2], sigma)
+            for k, v in zip(('applied', 'factors', 'hue', 'sigma', 'flip', 'order'), (applied, factors, hue, sigma, flip, order)):
+                last[k].append(v)
+        self.count += n
+        self.last = last
+        return arr
+
+
+def hard_flags(label_shape, hard_domains):
+    """One bool per image of a [B, D, H, W] label batch after the domain axis merged into the batch (image b * D + d): is d one of hard_domains?"""
+    if not hard_domains:
+        return None
+    lead = tuple(label_shape[:-2])
+    d = lead[-1] if len(lead) >= 2 else 1
+    total = 1
+    for v in lead:
+        total *= v
+    return [(i % d) in hard_domains for i in range(total)]
+
+
 class DevicePrefetcher:
     """Keeps `depth` batches in flight: H2D of the uint8 buffers and the u8 -> NHWC4 float / int64 kernels run on a side stream, an
     event hands the result to the compute stream (`next()` makes the current stream wait on it; the host never blocks on the GPU
     except to keep the source from refilling a pinned buffer whose copy is still in flight). The raw uint8 device slots are only
-    touched by the side stream, so its own order protects them; the converted tensors are handed over with `record_stream`."""
+    touched by the side stream, so its own order protects them; the converted tensors are handed over with `record_stream`.
 
-    def __init__(self, source, depth=1, device=None):
+    augment (a PhotometricAugment, default None = exactly the plain conversion): every batch is sampled for and augmented on the side stream, image and labels alike.
+    hard_domains: indices on the D axis of the source's [B, D, ...] batches whose images get the hard augmentation (the meta-test domains); an attribute the caller may
+    reassign between batches -- it is read when a batch is ISSUED, i.e. `depth` batches before that batch is returned."""
+
+    def __init__(self, source, depth=1, device=None, augment=None, hard_domains=None):
         assert torch.cuda.is_available(), 'the input edge stages into HBM: needs a GPU'
         self.src, self.depth = iter(source), depth
         self.host_ring = max(1, len(getattr(source, 'bufs', [])) or 1)          # pinned buffers the source rotates through
@@ -66,6 +128,7 @@ class DevicePrefetcher:
         self.side = torch.cuda.Stream(device=self.dev)
         self.slots, self.copied, self.ready = [None] * (depth + 1), [], []
         self.n = 0
+        self.augment, self.hard_domains = augment, hard_domains
         for _ in range(depth):
             self._issue()
 
@@ -85,8 +148,13 @@ class DevicePrefetcher:
             lab_d.copy_(lab_h.reshape(-1, h, w), non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.side)
-            x = ops.nchw(K.image_u8_to_nhwc4(img_d))
-            gt = K.labels_u8_to_i64(lab_d)
+            if self.augment is None:
+                x = ops.nchw(K.image_u8_to_nhwc4(img_d))
+                gt = K.labels_u8_to_i64(lab_d)
+            else:
+                params = K.upload_aug_params(self.augment.sample(img_d.shape[0], hard_flags(lab_h.shape, self.hard_domains)), self.dev)
+                x = ops.nchw(K.augment_u8(img_d, params))
+                gt = K.labels_u8_to_i64(lab_d, params)
             ev = torch.cuda.Event()
             ev.record(self.side)
         self.copied.append(done)
