@@ -11,6 +11,8 @@
 // ImageBasedCrossEntropyLoss2d (/root/reference/loss.py:20-43,71-88,120-180). Every pixel's terms are multiplied by w[image][label] and the divisor is a weight sum
 // (of the batch, or of each image with the per-image losses added in image order); pm_label_class_weights builds the image-based weight rows from the labels on
 // the device (loss.py:136-146), so the criterion needs neither the materialised logits nor a host round trip.
+#include <type_traits>
+
 #include "pm_common.h"
 
 namespace {
@@ -30,7 +32,12 @@ struct CEGeom {
   int per_image;
 };
 
-// interpolated logits of hi-res pixel (b, Y, X) into v[0..C)
+// The interpolation expression, written once: every kernel's per-pixel logits carry the same bits because they all come from here.
+__device__ __forceinline__ float ce_lerp(const pm_lerp& ly, const pm_lerp& lx, float a, float b, float c, float d) {
+  return ly.w0 * (lx.w0 * a + lx.w1 * b) + ly.w1 * (lx.w0 * c + lx.w1 * d);
+}
+
+// interpolated logits of hi-res pixel (b, Y, X) into v[0..C), taps from global memory
 template <int C_>
 __device__ __forceinline__ void interp_logits(const CEGeom& g, int b, const pm_lerp& ly, const pm_lerp& lx, float* v) {
   const float* r0 = g.logits + ((long)(b * g.h + ly.i0) * g.w) * g.lp;
@@ -44,7 +51,7 @@ __device__ __forceinline__ void interp_logits(const CEGeom& g, int b, const pm_l
   for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c) {
     if (c < C) {
       const float a = p00[c] * g.inv_temp, bq = p01[c] * g.inv_temp, cq = p10[c] * g.inv_temp, d = p11[c] * g.inv_temp;
-      v[c] = ly.w0 * (lx.w0 * a + lx.w1 * bq) + ly.w1 * (lx.w0 * cq + lx.w1 * d);
+      v[c] = ce_lerp(ly, lx, a, bq, cq, d);
     }
   }
 }
@@ -56,6 +63,29 @@ __device__ __forceinline__ int ce_xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
   const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + idx;
+}
+
+// Block partial: wave sums, then thread 0 adds the waves' sums in wave order: true for that thread alone, with the block's (loss sum, count or weight sum) in lsum and
+// lcnt -- the caller stores them. NW = 4: a block of four waves, one expression; NW = 0: blockDim.x / 64 waves, a loop.
+template <int N>
+__device__ __forceinline__ void ce_wave_partials(float lsum, float lcnt, float (&sm)[2][N]) {
+  lsum = pm_wave_sum(lsum);
+  lcnt = pm_wave_sum(lcnt);
+  if ((threadIdx.x & 63) == 0) sm[0][threadIdx.x >> 6] = lsum, sm[1][threadIdx.x >> 6] = lcnt;
+}
+template <int NW, int N>
+__device__ __forceinline__ bool ce_block_partial(float& lsum, float& lcnt, float (&sm)[2][N]) {
+  ce_wave_partials(lsum, lcnt, sm);
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  if constexpr (NW == 4) {
+    lsum = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
+    lcnt = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
+  } else {
+    lsum = lcnt = 0.f;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) lsum += sm[0][k], lcnt += sm[1][k];
+  }
+  return true;
 }
 
 // WT: blockIdx.y = image (the final reduce needs every image's partials apart), the x blocks stride over that image's pixels; (sum w nll, sum w) per block.
@@ -96,20 +126,62 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __re
     }
   }
   __shared__ float sm[2][4];
-  lsum = pm_wave_sum(lsum);
-  lcnt = pm_wave_sum(lcnt);
-  if ((threadIdx.x & 63) == 0) sm[0][threadIdx.x >> 6] = lsum, sm[1][threadIdx.x >> 6] = lcnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
+  if (ce_block_partial<4>(lsum, lcnt, sm)) {
     const long pb = WT ? (long)blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
-    part[pb * 2] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
-    part[pb * 2 + 1] = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
+    part[pb * 2] = lsum, part[pb * 2 + 1] = lcnt;
   }
 }
 
 // WT kernels whose block belongs to one image: that image's C weights, staged once per block (visible after the block's next barrier)
 __device__ __forceinline__ void ce_stage_weights(const CEGeom& g, int b, float* wsm) {
   if ((int)threadIdx.x < g.C) wsm[threadIdx.x] = g.wts[(long)b * g.wstride + threadIdx.x];
+}
+
+// ---- the pieces the row kernels below share, each written once: their outputs agree bit for bit because they run these expressions -----------------------------
+// Low-res rows y0 and y1 of image b, columns [x0, x0 + ncol), pre-scaled by 1/T, into L0 / L1 as [x][C | 1]; nt = block size. Both rows in one loop.
+__device__ __forceinline__ void ce_stage_rows(const CEGeom& g, int C, int CP, int b, int y0, int y1, int x0, int ncol, int nt, float* L0, float* L1) {
+  for (int i = threadIdx.x; i < ncol * C; i += nt) {
+    const int xl = i / C, c = i - xl * C;
+    L0[xl * CP + c] = g.logits[((long)(b * g.h + y0) * g.w + x0 + xl) * g.lp + c] * g.inv_temp;
+    L1[xl * CP + c] = g.logits[((long)(b * g.h + y1) * g.w + x0 + xl) * g.lp + c] * g.inv_temp;
+  }
+}
+
+// int64 label -> byte: a class below 254 as itself, 255 (ignored) as 255, everything else 254: a label no class matches (as the kernels reading int64 treat it)
+__device__ __forceinline__ unsigned char ce_label_byte(int64_t l) { return (l >= 0 && l < 254) ? (unsigned char)l : (l == 255 ? 255 : 254); }
+
+// One hi-res pixel from the staged rows (L0 / L1 hold the low-res columns from x0 on): its interpolated logits v[0..C) -- the expression of interp_logits --, their
+// maximum mx and the label's logit vl. ARGMAX: the maximum by a strict > scan (not fmaxf), returning the lowest index among the maxima as output.max(1)[1].
+template <bool ARGMAX, typename Lab>
+__device__ __forceinline__ void ce_class_step(float vc, int c, Lab lab, float& mx, float& vl, int& arg) {
+  if constexpr (ARGMAX) {
+    if (vc > mx) mx = vc, arg = c;
+  } else {
+    mx = fmaxf(mx, vc);
+  }
+  if (c == (int)lab) vl = vc;
+}
+// Sum of exp(v[c] - mx); KEEP: the terms replace v[c] (the field kernels go on to softmax - onehot). v_exp_f32 (~1 ulp per term): the libm expf was 2/3 of the
+// row-staged forward's ALU work
+template <int C_, bool KEEP>
+__device__ __forceinline__ float ce_exp_sum(float* v, float mx, int C) {
+  float se = 0.f;
+#pragma unroll
+  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+    if (c < C) {
+      if constexpr (KEEP) v[c] = __expf(v[c] - mx), se += v[c];
+      else se += __expf(v[c] - mx);
+    }
+  return se;
+}
+
+// The field kernels: w (softmax - onehot) of one pixel (v from ce_exp_sum) into A (left-tap weight: stays in the pixel's low-res column) and B (right-tap weight: owed
+// to the next column). w multiplies the difference alone: every other expression stays the unweighted one, so w = 1 leaves its bits.
+template <bool WT>
+__device__ __forceinline__ void ce_grad_tap(float p, bool hot, float wl, float wa, float wb, float& A, float& B) {
+  float gq = p - (hot ? 1.f : 0.f);
+  if constexpr (WT) gq *= wl;
+  A += wa * gq, B += wb * gq;
 }
 
 // Row-staged forward: block = one hi-res row (Y, image b). The two low-res logit rows that row interpolates between are staged in LDS
@@ -135,11 +207,7 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
   int64_t labs[3];
 #pragma unroll
   for (int u = 0; u < 3; ++u) labs[u] = (int)threadIdx.x + 256 * u < g.W ? lrow[threadIdx.x + 256 * u] : 255;   // in flight while the rows are staged
-  for (int i = threadIdx.x; i < g.w * C; i += 256) {
-    const int xl = i / C, c = i - xl * C;
-    L0[xl * CP + c] = g.logits[((long)(b * g.h + ly.i0) * g.w + xl) * g.lp + c] * g.inv_temp;
-    L1[xl * CP + c] = g.logits[((long)(b * g.h + ly.i1) * g.w + xl) * g.lp + c] * g.inv_temp;
-  }
+  ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, 256, L0, L1);
   __syncthreads();
   float lsum = 0.f, lcnt = 0.f;
   for (int X = threadIdx.x, u = 0; X < g.W; X += 256, ++u) {
@@ -150,19 +218,12 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
     }
     const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
     const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-    float v[C_ > 0 ? C_ : MAXC];
-    float mx = -INFINITY, vl = 0.f;
+    float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, vl = 0.f;
+    [[maybe_unused]] int arg = 0;
 #pragma unroll
     for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) {
-        v[c] = ly.w0 * (lx.w0 * p00[c] + lx.w1 * p01[c]) + ly.w1 * (lx.w0 * p10[c] + lx.w1 * p11[c]);
-        mx = fmaxf(mx, v[c]);
-        if (c == (int)lab) vl = v[c];
-      }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) se += __expf(v[c] - mx);   // v_exp_f32 (~1 ulp per term, as in the backward pass): the libm expf was 2/3 of this kernel's ALU work
+      if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
+    const float se = ce_exp_sum<C_, false>(v, mx, C);
     if constexpr (WT) {
       const float wl = wsm[lab];
       lsum += wl * ((mx + logf(se)) - vl);
@@ -173,24 +234,17 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
     }
   }
   __shared__ float sm[2][4];
-  lsum = pm_wave_sum(lsum);
-  lcnt = pm_wave_sum(lcnt);
-  if ((threadIdx.x & 63) == 0) sm[0][threadIdx.x >> 6] = lsum, sm[1][threadIdx.x >> 6] = lcnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[bid * 2] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
-    part[bid * 2 + 1] = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
-  }
+  if (ce_block_partial<4>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
 }
 
 // One block folds the per-block (loss sum, pixel count) partials in double: 1024 threads keep the chain of dependent loads short (the
 // 64-thread version walked 96 L2 round trips per thread: 26 us for 50 KB), then a fixed binary tree in LDS.
 constexpr int CE_FINAL_T = 1024;
-__global__ __launch_bounds__(CE_FINAL_T) void ce_final_kernel(const float* __restrict__ part, int nb, float* __restrict__ out) {
-  __shared__ double s[2][CE_FINAL_T];
+// nb (sum, count) pairs from pair index `first` on -> s[0][0], s[1][0] (valid after the call's last barrier)
+__device__ __forceinline__ void ce_fold_pairs(const float* __restrict__ part, long first, int nb, double (&s)[2][CE_FINAL_T]) {
   double a = 0.0, c = 0.0;
   for (int b = threadIdx.x; b < nb; b += CE_FINAL_T) {
-    const float2 v = *reinterpret_cast<const float2*>(part + (long)b * 2);
+    const float2 v = *reinterpret_cast<const float2*>(part + (first + b) * 2);
     a += (double)v.x, c += (double)v.y;
   }
   s[0][threadIdx.x] = a, s[1][threadIdx.x] = c;
@@ -199,6 +253,10 @@ __global__ __launch_bounds__(CE_FINAL_T) void ce_final_kernel(const float* __res
     if ((int)threadIdx.x < w) s[0][threadIdx.x] += s[0][threadIdx.x + w], s[1][threadIdx.x] += s[1][threadIdx.x + w];
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(CE_FINAL_T) void ce_final_kernel(const float* __restrict__ part, int nb, float* __restrict__ out) {
+  __shared__ double s[2][CE_FINAL_T];
+  ce_fold_pairs(part, 0, nb, s);
   if (threadIdx.x == 0) {
     out[0] = (float)(s[0][0] / s[1][0]);  // 0/0 -> NaN like torch when every pixel is ignored
     out[1] = (float)s[1][0];
@@ -212,17 +270,7 @@ __global__ __launch_bounds__(CE_FINAL_T) void ce_final_img_kernel(const float* _
   __shared__ double s[2][CE_FINAL_T];
   double loss = 0.0, den = 0.0;
   for (int b = 0; b < n; ++b) {
-    double a = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < per; i += CE_FINAL_T) {
-      const float2 v = *reinterpret_cast<const float2*>(part + ((long)b * per + i) * 2);
-      a += (double)v.x, c += (double)v.y;
-    }
-    s[0][threadIdx.x] = a, s[1][threadIdx.x] = c;
-    __syncthreads();
-    for (int w = CE_FINAL_T / 2; w >= 1; w >>= 1) {
-      if ((int)threadIdx.x < w) s[0][threadIdx.x] += s[0][threadIdx.x + w], s[1][threadIdx.x] += s[1][threadIdx.x + w];
-      __syncthreads();
-    }
+    ce_fold_pairs(part, (long)b * per, per, s);
     if (threadIdx.x == 0) {
       out[2 + b] = (float)s[1][0];
       loss += s[0][0] / s[1][0];
@@ -314,17 +362,8 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
   float* L1 = L + (size_t)g.w * CP;                                   // (+ C floats of slack behind it: bufB holds one column more than a round)
   unsigned char* lab8 = reinterpret_cast<unsigned char*>(L1 + (size_t)g.w * CP + C);
   const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
-  for (int X = tid; X < g.W; X += nt) {
-    const int64_t l = lrow[X];
-    lab8[X] = (l >= 0 && l < 254) ? (unsigned char)l : (l == 255 ? 255 : 254);   // 254: a label no class matches (as the unfused kernels treat it)
-  }
-  auto stage_rows = [&]() {
-    for (int i = tid; i < g.w * C; i += nt) {
-      const int xl = i / C, c = i - xl * C;
-      L0[xl * CP + c] = g.logits[((long)(b * g.h + ly.i0) * g.w + xl) * g.lp + c] * g.inv_temp;
-      L1[xl * CP + c] = g.logits[((long)(b * g.h + ly.i1) * g.w + xl) * g.lp + c] * g.inv_temp;
-    }
-  };
+  for (int X = tid; X < g.W; X += nt) lab8[X] = ce_label_byte(lrow[X]);
+  auto stage_rows = [&]() { ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1); };
   stage_rows();
   __syncthreads();
   constexpr int CR = C_ > 0 ? C_ : MAXC;
@@ -355,19 +394,12 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
         }
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
         const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-        float v[CR];
-        float mx = -INFINITY, vl = 0.f;
+        float v[CR], mx = -INFINITY, vl = 0.f;
+        [[maybe_unused]] int arg = 0;
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) {
-            v[c] = ly.w0 * (lx.w0 * p00[c] + lx.w1 * p01[c]) + ly.w1 * (lx.w0 * p10[c] + lx.w1 * p11[c]);   // same expression as interp_logits
-            mx = fmaxf(mx, v[c]);
-            if (c == lab) vl = v[c];
-          }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CR; ++c)
-          if (c < C) v[c] = __expf(v[c] - mx), se += v[c];
+          if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
+        const float se = ce_exp_sum<C_, true>(v, mx, C);
         float wl = 1.f;
         if constexpr (WT) {
           // generic class count: a label that is no class weighs 0 by a select, not by the branch above -- the branch tells the compiler that C > 0, it then
@@ -384,11 +416,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
           const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
           for (int c = 0; c < CR; ++c)
-            if (c < C) {
-              float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
-              if constexpr (WT) gq *= wl;      // w (softmax - onehot): every other expression stays the unweighted one, so w = 1 leaves its bits
-              A[c] += wa * gq, B[c] += wb * gq;
-            }
+            if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab, wl, wa, wb, A[c], B[c]);
         }
       }
     }
@@ -419,16 +447,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
     }
   }
   __shared__ float sm[2][4];
-  lsum = pm_wave_sum(lsum);
-  lcnt = pm_wave_sum(lcnt);
-  if ((tid & 63) == 0) sm[0][tid >> 6] = lsum, sm[1][tid >> 6] = lcnt;
-  __syncthreads();
-  if (tid == 0) {
-    float a = 0.f, c = 0.f;
-    for (int wv = 0; wv < (nt >> 6); ++wv) a += sm[0][wv], c += sm[1][wv];
-    part[bid * 2] = a;
-    part[bid * 2 + 1] = c;
-  }
+  if (ce_block_partial<0>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
 }
 
 // ---- the same sweep with the ROW half of the transposed bilinear operator folded in (round 4, second session) ------------------------------------------------
@@ -475,11 +494,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   float* accB = accA + (size_t)ws * C;
   float* edge = accB + (size_t)ws * C;                                              // [rg][nwv][CR]: B of a wave's last lane, owed to the next wave's lane 0
   unsigned char* lab8 = reinterpret_cast<unsigned char*>(edge + (size_t)rg * nwv * CR);   // [rg][Wp]
-  for (int i = tid; i < nst * C; i += nt) {
-    const int xl = i / C, c = i - xl * C;
-    L0[xl * CP + c] = g.logits[((long)(b * g.h + y) * g.w + cb + xl) * g.lp + c] * g.inv_temp;
-    L1[xl * CP + c] = g.logits[((long)(b * g.h + y1) * g.w + cb + xl) * g.lp + c] * g.inv_temp;
-  }
+  ce_stage_rows(g, C, CP, b, y, y1, cb, nst, nt, L0, L1);
   for (int i = tid; i < ws * C; i += nt) accA[i] = 0.f, accB[i] = 0.f;
   const int Ya = ce_first_ge(g.sy, y, g.h, g.H), Yb = ce_first_ge(g.sy, y + 1, g.h, g.H);
   const int Xlo = ce_first_ge(g.sx, cb, g.w, g.W), Xhi = ce_first_ge(g.sx, c0 + ncol, g.w, g.W);   // hi-res columns whose left tap is one of the lanes' columns
@@ -497,10 +512,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
     unsigned char* mylab = lab8 + (size_t)gi * Wp;
     if (rowlive) {
       const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
-      for (int X = Xlo + x; X < Xhi; X += tpr) {
-        const int64_t l = lrow[X];
-        mylab[X - Xlo] = (l >= 0 && l < 254) ? (unsigned char)l : (l == 255 ? 255 : 254);
-      }
+      for (int X = Xlo + x; X < Xhi; X += tpr) mylab[X - Xlo] = ce_label_byte(lrow[X]);
     }
     __syncthreads();                                 // labels (and, in the first round, the logit rows) are staged
     float A[CR], B[CR];
@@ -516,19 +528,12 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
         }
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
         const float *p00 = L0 + (lx.i0 - cb) * CP, *p01 = L0 + (lx.i1 - cb) * CP, *p10 = L1 + (lx.i0 - cb) * CP, *p11 = L1 + (lx.i1 - cb) * CP;
-        float v[CR];
-        float mx = -INFINITY, vl = 0.f;
+        float v[CR], mx = -INFINITY, vl = 0.f;
+        [[maybe_unused]] int arg = 0;
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) {
-            v[c] = ly.w0 * (lx.w0 * p00[c] + lx.w1 * p01[c]) + ly.w1 * (lx.w0 * p10[c] + lx.w1 * p11[c]);   // same expression as interp_logits
-            mx = fmaxf(mx, v[c]);
-            if (c == lab) vl = v[c];
-          }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CR; ++c)
-          if (c < C) v[c] = __expf(v[c] - mx), se += v[c];
+          if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
+        const float se = ce_exp_sum<C_, true>(v, mx, C);
         float wl = 1.f;
         if constexpr (WT) {
           wl = wsm[lab];
@@ -540,11 +545,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
         const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) {
-            float gq = v[c] * inv - (c == lab ? 1.f : 0.f);
-            if constexpr (WT) gq *= wl;      // as in ce_fused_rows_kernel
-            A[c] += wa * gq, B[c] += wb * gq;
-          }
+          if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab, wl, wa, wb, A[c], B[c]);
       }
     }
     if (lane == 63) {
@@ -576,16 +577,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   float* outA = FA + (((long)b * g.h + y) * g.w + c0) * C;
   float* outB = FB + (((long)b * g.h + y) * g.w + c0) * C;
   for (int i = tid; i < ncol * C; i += nt) outA[i] = accA[i], outB[i] = accB[i];
-  lsum = pm_wave_sum(lsum);
-  lcnt = pm_wave_sum(lcnt);
-  if ((tid & 63) == 0) sm2[0][tid >> 6] = lsum, sm2[1][tid >> 6] = lcnt;
-  __syncthreads();
-  if (tid == 0) {
-    float a = 0.f, c = 0.f;
-    for (int k = 0; k < (nt >> 6); ++k) a += sm2[0][k], c += sm2[1][k];
-    part[bid * 2] = a;
-    part[bid * 2 + 1] = c;
-  }
+  if (ce_block_partial<0>(lsum, lcnt, sm2)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
 }
 // backward of the interval form: dl[b][y][x][c] = (FA[b][y][x][c] + FB[b][y - 1][x][c]) x upstream scale / valid pixels / T
 template <bool WT = false>
@@ -640,6 +632,7 @@ inline void rows2_launch(const CEGeom& g, const Rows2Plan& r, float* part, float
 }
 
 inline int fwd_blocks(long total) { return (int)std::min<long>((total + 255) / 256, 4096); }
+inline int wfwd_blocks(long hw) { return (int)std::min<long>((hw + 255) / 256, 512); }      // x blocks per image of the flat weighted forward
 
 int fill(CEGeom& g, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const char* who) {
   PM_REQUIRE(logits && logits->ptr && labels && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
@@ -651,36 +644,36 @@ int fill(CEGeom& g, const pm_tensor* logits, float inv_temp, const int64_t* labe
   return PM_OK;
 }
 
-}  // namespace
-
-extern "C" size_t pm_upsample_ce_workspace(int n, int H, int W) {   // one (sum, count) pair per block of either forward kernel
-  return pm_align_up((size_t)std::max<long>(fwd_blocks((long)n * H * W), (long)n * H * 2) * 2 * sizeof(float), 256);      // interval form: <= 2 n H blocks (rows2_plan)
+// The weighted entry points' extra arguments; a null CEWeights* is the unweighted loss.
+struct CEWeights {
+  const float* w;
+  int64_t stride;
+  int per_image;
+};
+int fill_w(CEGeom& g, const CEWeights& wt, const char* who) {
+  PM_REQUIRE(wt.w, PM_EINVAL, "%s: null weights", who);
+  PM_REQUIRE(wt.stride == 0 || wt.stride >= g.C, PM_EINVAL, "%s: weight_stride %lld is neither 0 nor >= %d classes", who, (long long)wt.stride, g.C);
+  PM_REQUIRE(wt.per_image == 0 || wt.per_image == 1, PM_EINVAL, "%s: per_image %d is neither 0 nor 1", who, wt.per_image);
+  g.wts = wt.w, g.wstride = (long)wt.stride, g.per_image = wt.per_image;
+  return PM_OK;
 }
 
-extern "C" int pm_upsample_ce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_ce_fwd");
-  CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_ce_fwd")) return e;
-  PM_REQUIRE(loss_out && ws && ws_bytes >= pm_upsample_ce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_ce_fwd: workspace too small");
-  int nb = fwd_blocks((long)g.n * H * W);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);     // the two staged low-res rows
-  if (row_lds <= 48 * 1024 && (long)g.n * H <= (1 << 20) && W >= 32) {     // row-staged kernel: one block per hi-res row
-    nb = g.n * H;
-    if (g.C == 19) hipLaunchKernelGGL(ce_fwd_rows_kernel<19>, dim3(nb), dim3(256), row_lds, st, g, (float*)ws);
-    else hipLaunchKernelGGL(ce_fwd_rows_kernel<0>, dim3(nb), dim3(256), row_lds, st, g, (float*)ws);
-  } else if (g.C == 19) {
-    hipLaunchKernelGGL(ce_fwd_kernel<19>, dim3(nb), dim3(256), 0, st, g, (float*)ws);
-  } else {
-    hipLaunchKernelGGL(ce_fwd_kernel<0>, dim3(nb), dim3(256), 0, st, g, (float*)ws);
-  }
-  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)ws, nb, loss_out);
-  return pm_check_launch("upsample_ce_fwd");
+// f(class count as a constant: 19 or 0 = generic, weighted as a constant): the one place where the run-time (C == 19, weighted) pair picks a kernel instantiation
+template <class F>
+inline void ce_dispatch(int C, bool weighted, F&& f) {
+  using C19 = std::integral_constant<int, 19>;
+  using C0 = std::integral_constant<int, 0>;
+  if (C == 19) weighted ? f(C19{}, std::true_type{}) : f(C19{}, std::false_type{});
+  else weighted ? f(C0{}, std::true_type{}) : f(C0{}, std::false_type{});
 }
 
-// ---- fused forward + first backward pass (training forward: the logits carry a graph) -------------------------------------------------
-namespace {
+// Final reduce of n x per block partials (image-major when weighted). Unweighted, or weighted over the batch: loss and divisor in the order of ce_final_kernel; the
+// weighted forms then add the per-image weight sums (and, per_image, the sum of the images' own means).
+inline void ce_finish(const float* part, int per, int n, const CEWeights* wt, float* loss_out, hipStream_t st) {
+  if (!wt || !wt->per_image) hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, n * per, loss_out);
+  if (wt) hipLaunchKernelGGL(ce_final_img_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, per, n, wt->per_image, loss_out);
+}
+
 struct FusedPlan {
   int parts, threads;
   size_t lds;
@@ -696,34 +689,111 @@ inline FusedPlan fused_plan(const CEGeom& g) {
   return p;
 }
 constexpr size_t FUSED_MAX_LDS = 159 * 1024;   // dynamic part; the kernel also declares 160 B of static LDS
-template <int CC, int PP, bool WITH_T, bool WT>
+template <int CC, int PP, bool WT>
 void fused_launch_one(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
   // > 64 KB of dynamic LDS (logit rows wider than ~420 pixels x 19 classes) needs an explicit opt-in, once per kernel AND device
   static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, WITH_T, WT>), (int)FUSED_MAX_LDS);
-  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, WITH_T, WT>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, true, WT>), (int)FUSED_MAX_LDS);
+  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, true, WT>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
 }
-template <bool WITH_T, bool WT = false>
-int fused_launch(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
-#define PM_CE_LAUNCH(CC, PP) fused_launch_one<CC, PP, WITH_T, WT>(g, p, part, T, st)
-#define PM_CE_PARTS(CC)                         \
-  switch (p.parts) {                            \
-    case 1: PM_CE_LAUNCH(CC, 1); break;         \
-    case 2: PM_CE_LAUNCH(CC, 2); break;         \
-    case 4: PM_CE_LAUNCH(CC, 4); break;         \
-    case 8: PM_CE_LAUNCH(CC, 8); break;         \
-    default: PM_CE_LAUNCH(CC, 16); break;       \
-  }
-  if (g.C == 19) {
-    PM_CE_PARTS(19)
-  } else {
-    PM_CE_PARTS(0)
-  }
-#undef PM_CE_PARTS
-#undef PM_CE_LAUNCH
+int fused_launch(const CEGeom& g, const FusedPlan& p, bool weighted, float* part, float* T, hipStream_t st) {
+  ce_dispatch(g.C, weighted, [&](auto cc, auto wt) {
+    constexpr int CC = decltype(cc)::value;
+    constexpr bool WT = decltype(wt)::value;
+    switch (p.parts) {
+      case 1: fused_launch_one<CC, 1, WT>(g, p, part, T, st); break;
+      case 2: fused_launch_one<CC, 2, WT>(g, p, part, T, st); break;
+      case 4: fused_launch_one<CC, 4, WT>(g, p, part, T, st); break;
+      case 8: fused_launch_one<CC, 8, WT>(g, p, part, T, st); break;
+      default: fused_launch_one<CC, 16, WT>(g, p, part, T, st); break;
+    }
+  });
   return pm_check_launch("upsample_ce_fused");
 }
+
+// ---- one function per operation; `who` is the entry point's name (it leads every message), wt its weights or null -----------------------------------------------
+int ce_fwd(const char* who, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const CEWeights* wt, float* loss_out, void* ws,
+           size_t ws_bytes, hipStream_t st) {
+  PM_REQUIRE_F32(logits, who);
+  CEGeom g;
+  if (int e = fill(g, logits, inv_temp, labels, H, W, who)) return e;
+  if (wt)
+    if (int e = fill_w(g, *wt, who)) return e;
+  PM_REQUIRE(loss_out && ws && ws_bytes >= (wt ? pm_upsample_wce_workspace(g.n, H, W) : pm_upsample_ce_workspace(g.n, H, W)), PM_EWORKSPACE, "%s: workspace too small", who);
+  int per, n = g.n;      // block partials per image, images
+  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);     // the two staged low-res rows
+  if (row_lds <= 48 * 1024 && (long)g.n * H <= (1 << 20) && W >= 32) {     // row-staged kernel: one block per hi-res row
+    per = H;
+    ce_dispatch(g.C, wt != nullptr, [&](auto cc, auto w) {
+      hipLaunchKernelGGL((ce_fwd_rows_kernel<decltype(cc)::value, decltype(w)::value>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
+    });
+  } else if (wt) {      // flat kernel, image-major grid: the final reduce needs every image's partials apart
+    PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "%s: %d images > 65535", who, g.n);
+    per = wfwd_blocks((long)H * W);
+    ce_dispatch(g.C, true, [&](auto cc, auto) { hipLaunchKernelGGL((ce_fwd_kernel<decltype(cc)::value, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws); });
+  } else {              // flat kernel, one grid over the batch
+    per = fwd_blocks((long)g.n * H * W), n = 1;
+    ce_dispatch(g.C, false, [&](auto cc, auto) { hipLaunchKernelGGL((ce_fwd_kernel<decltype(cc)::value, false>), dim3(per), dim3(256), 0, st, g, (float*)ws); });
+  }
+  ce_finish((const float*)ws, per, n, wt, loss_out, st);
+  return pm_check_launch(who);
+}
+
+int ce_fwd_field(const char* who, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const CEWeights* wt, float* loss_out, float* field,
+                 void* ws, size_t ws_bytes, hipStream_t st) {
+  PM_REQUIRE_F32(logits, who);
+  CEGeom g;
+  if (int e = fill(g, logits, inv_temp, labels, H, W, who)) return e;
+  if (wt)
+    if (int e = fill_w(g, *wt, who)) return e;
+  PM_REQUIRE(loss_out && field && ws && ws_bytes >= (wt ? pm_upsample_wce_workspace(g.n, H, W) : pm_upsample_ce_workspace(g.n, H, W)), PM_EWORKSPACE,
+             "%s: workspace too small / null field", who);
+  if (const Rows2Plan r = rows2_plan(g); r.ok) {
+    wt ? rows2_launch<true>(g, r, (float*)ws, field, st) : rows2_launch<false>(g, r, (float*)ws, field, st);
+    ce_finish((const float*)ws, g.h * r.nseg, g.n, wt, loss_out, st);
+    return pm_check_launch(who);
+  }
+  const FusedPlan p = fused_plan(g);
+  PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * H <= (1l << 30), PM_EUNSUPPORTED, "%s: logit rows of %d x %d classes do not fit LDS", who, g.w, g.C);
+  if (int e = fused_launch(g, p, wt != nullptr, (float*)ws, field, st)) return e;
+  ce_finish((const float*)ws, H, g.n, wt, loss_out, st);
+  return pm_check_launch(who);
+}
+
+// wt: only per_image is read (the row pass reads neither labels, logits nor weights)
+int ce_bwd_field(const char* who, const pm_tensor* logits, float inv_temp, int H, int W, const CEWeights* wt, const float* loss_out, const float* gscale,
+                 const float* field, const pm_tensor* dlogits, hipStream_t st) {
+  PM_REQUIRE_F32(logits, who);
+  PM_REQUIRE_F32(dlogits, who);
+  CEGeom g;
+  static const int64_t dummy = 0;
+  if (int e = fill(g, logits, inv_temp, &dummy, H, W, who)) return e;
+  if (wt) {
+    PM_REQUIRE(wt->per_image == 0 || wt->per_image == 1, PM_EINVAL, "%s: per_image %d is neither 0 nor 1", who, wt->per_image);
+  }
+  PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "%s: bad args", who);
+  if (wt) g.per_image = wt->per_image;
+  const long total = (long)g.n * g.h * g.w * g.C;
+  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
+  float* dl = (float*)dlogits->ptr;
+  const bool rows2 = rows2_plan(g).ok;
+  ce_dispatch(0, wt != nullptr, [&](auto, auto w) {
+    constexpr bool WT = decltype(w)::value;
+    if (rows2) hipLaunchKernelGGL(ce_bwd_rows2_kernel<WT>, grid, dim3(256), 0, st, g, field, field + total, loss_out, gscale, dl, (long)dlogits->pitch);
+    else hipLaunchKernelGGL(ce_bwd_cols_kernel<WT>, grid, dim3(256), 0, st, g, field, loss_out, gscale, dl, (long)dlogits->pitch);
+  });
+  return pm_check_launch(who);
+}
+
 }  // namespace
+
+extern "C" size_t pm_upsample_ce_workspace(int n, int H, int W) {   // one (sum, count) pair per block of either forward kernel
+  return pm_align_up((size_t)std::max<long>(fwd_blocks((long)n * H * W), (long)n * H * 2) * 2 * sizeof(float), 256);      // interval form: <= 2 n H blocks (rows2_plan)
+}
+extern "C" size_t pm_upsample_wce_workspace(int n, int H, int W) {      // one (sum w nll, sum w) pair per block of any weighted forward kernel
+  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H * 2) * 2 * sizeof(float), 256);
+}
+extern "C" size_t pm_upsample_wce_loss_floats(int n) { return (size_t)2 + (size_t)std::max(n, 0); }
 
 extern "C" size_t pm_upsample_ce_field_bytes(const pm_tensor* logits, int H, int W) {
   if (!logits || !pm_is_f32(logits)) return 0;      // fp32 tensors only
@@ -736,42 +806,37 @@ extern "C" size_t pm_upsample_ce_field_bytes(const pm_tensor* logits, int H, int
   return (size_t)logits->n * H * logits->w * logits->c * sizeof(float);
 }
 
+// The unweighted and the weighted entry points (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180): same kernels (WT), same routing
+// between them, same field layout. Weighted block partials are (sum w nll, sum w), image-major.
+extern "C" int pm_upsample_ce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return ce_fwd("upsample_ce_fwd", logits, inv_temp, labels, H, W, nullptr, loss_out, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int pm_upsample_wce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                                   int per_image, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
+  const CEWeights wt{weights, weight_stride, per_image};
+  return ce_fwd("upsample_wce_fwd", logits, inv_temp, labels, H, W, &wt, loss_out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// Training forward (the logits carry a graph): the loss and the field the row pass needs, in one sweep over the labels.
 extern "C" int pm_upsample_ce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, float* field,
                                         void* ws, size_t ws_bytes, void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_ce_fwd_field");
-  CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_ce_fwd_field")) return e;
-  PM_REQUIRE(loss_out && field && ws && ws_bytes >= pm_upsample_ce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_ce_fwd_field: workspace too small / null field");
-  hipStream_t st = (hipStream_t)stream;
-  if (const Rows2Plan r = rows2_plan(g); r.ok) {
-    rows2_launch(g, r, (float*)ws, field, st);
-    hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)ws, g.n * g.h * r.nseg, loss_out);
-    return pm_check_launch("upsample_ce_fwd_field");
-  }
-  const FusedPlan p = fused_plan(g);
-  PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * H <= (1l << 30), PM_EUNSUPPORTED, "upsample_ce_fwd_field: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
-  if (int e = fused_launch<true>(g, p, (float*)ws, field, st)) return e;
-  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)ws, g.n * H, loss_out);
-  return pm_check_launch("upsample_ce_fwd_field");
+  return ce_fwd_field("upsample_ce_fwd_field", logits, inv_temp, labels, H, W, nullptr, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int pm_upsample_wce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
+                                         int per_image, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
+  const CEWeights wt{weights, weight_stride, per_image};
+  return ce_fwd_field("upsample_wce_fwd_field", logits, inv_temp, labels, H, W, &wt, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pm_upsample_ce_bwd_field(const pm_tensor* logits, float inv_temp, int H, int W, const float* loss_out, const float* gscale, const float* field,
                                         const pm_tensor* dlogits, void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_ce_bwd_field");
-  PM_REQUIRE_F32(dlogits, "upsample_ce_bwd_field");
-  CEGeom g;
-  static const int64_t dummy = 0;
-  if (int e = fill(g, logits, inv_temp, &dummy, H, W, "upsample_ce_bwd_field")) return e;      // the row pass reads neither labels nor logits
-  PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "upsample_ce_bwd_field: bad args");
-  const long total = (long)g.n * g.h * g.w * g.C;
-  if (rows2_plan(g).ok) {
-    hipLaunchKernelGGL(ce_bwd_rows2_kernel<false>, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, field + total,
-                       loss_out, gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
-    return pm_check_launch("upsample_ce_bwd_field");
-  }
-  hipLaunchKernelGGL(ce_bwd_cols_kernel<false>, dim3((unsigned)std::min<long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, g, field, loss_out,
-                     gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
-  return pm_check_launch("upsample_ce_bwd_field");
+  return ce_bwd_field("upsample_ce_bwd_field", logits, inv_temp, H, W, nullptr, loss_out, gscale, field, dlogits, (hipStream_t)stream);
+}
+extern "C" int pm_upsample_wce_bwd_field(const pm_tensor* logits, float inv_temp, int H, int W, int per_image, const float* loss_out, const float* gscale,
+                                         const float* field, const pm_tensor* dlogits, void* stream) {
+  const CEWeights wt{nullptr, 0, per_image};
+  return ce_bwd_field("upsample_wce_bwd_field", logits, inv_temp, H, W, &wt, loss_out, gscale, field, dlogits, (hipStream_t)stream);
 }
 
 // Backward without a field from the forward (the caller ran pm_upsample_ce_fwd): the field is rebuilt into the workspace by the same fused sweep
@@ -792,13 +857,13 @@ extern "C" int pm_upsample_ce_bwd(const pm_tensor* logits, float inv_temp, const
   float* field = (float*)ws;
   float* part = (float*)((char*)ws + pm_align_up(pm_upsample_ce_field_bytes(logits, H, W), 256));
   if (const Rows2Plan r = rows2_plan(g); r.ok) {
-    rows2_launch(g, r, part, field, (hipStream_t)stream);
+    rows2_launch<false>(g, r, part, field, (hipStream_t)stream);
     if (int e = pm_check_launch("upsample_ce_bwd")) return e;
-    return pm_upsample_ce_bwd_field(logits, inv_temp, H, W, loss_out, gscale, field, dlogits, stream);
+  } else {
+    const FusedPlan p = fused_plan(g);
+    PM_REQUIRE(p.lds <= FUSED_MAX_LDS, PM_EUNSUPPORTED, "upsample_ce_bwd: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
+    if (int e = fused_launch(g, p, false, part, field, (hipStream_t)stream)) return e;
   }
-  const FusedPlan p = fused_plan(g);
-  PM_REQUIRE(p.lds <= FUSED_MAX_LDS, PM_EUNSUPPORTED, "upsample_ce_bwd: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
-  if (int e = fused_launch<true>(g, p, part, field, (hipStream_t)stream)) return e;
   return pm_upsample_ce_bwd_field(logits, inv_temp, H, W, loss_out, gscale, field, dlogits, stream);
 }
 
@@ -880,29 +945,18 @@ __global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int r
       if (lab == 255 && !prow) continue;
       const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
       const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-      float v[C_ > 0 ? C_ : MAXC];
-      float mx = -INFINITY, vl = 0.f;
+      float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, vl = 0.f;
       int arg = 0;
 #pragma unroll
       for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-        if (c < C) {
-          v[c] = ly.w0 * (lx.w0 * p00[c] + lx.w1 * p01[c]) + ly.w1 * (lx.w0 * p10[c] + lx.w1 * p11[c]);
-          if (v[c] > mx) mx = v[c], arg = c;      // strict: the lowest index among the maxima, as output.max(1)[1]
-          if (c == (int)lab) vl = v[c];
-        }
+        if (c < C) ce_class_step<true>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
       if (prow) prow[X] = (uint8_t)arg;           // every pixel, ignored ones included
       if (lab == 255) continue;
-      float se = 0.f;
-#pragma unroll
-      for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-        if (c < C) se += __expf(v[c] - mx);
-      lsum += (mx + logf(se)) - vl;
+      lsum += (mx + logf(ce_exp_sum<C_, false>(v, mx, C))) - vl;
       lcnt += 1.f;
       if (lab >= 0 && lab < C) atomicAdd(&cnt[(int)lab * C + arg], 1u);      // fast_hist's mask (utils/misc.py:65-70)
     }
-    lsum = pm_wave_sum(lsum);
-    lcnt = pm_wave_sum(lcnt);
-    if ((threadIdx.x & 63) == 0) sm[Y - Y0][0][threadIdx.x >> 6] = lsum, sm[Y - Y0][1][threadIdx.x >> 6] = lcnt;
+    ce_wave_partials(lsum, lcnt, sm[Y - Y0]);
   }
   __syncthreads();
   if ((int)threadIdx.x < Y1 - Y0) {
@@ -954,103 +1008,12 @@ extern "C" int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const i
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
   unsigned* counts = (unsigned*)((char*)ws + p.part_bytes);
-  if (g.C == 19) eval_launch<19>(g, p, part, counts, pred, st);
-  else eval_launch<0>(g, p, part, counts, pred, st);
+  ce_dispatch(g.C, false, [&](auto cc, auto) { eval_launch<decltype(cc)::value>(g, p, part, counts, pred, st); });
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, g.n * H, loss_out);
   hipLaunchKernelGGL(eval_fold_kernel, dim3((g.C * g.C + 31) / 32), dim3(EVAL_FOLD_T), 0, st, (const unsigned*)counts, g.n * p.chunks, g.C * g.C, accumulate, hist);
   return pm_check_launch("upsample_eval");
 }
 
-
-// ---- weighted forms: CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d (loss.py:20-43,71-88,120-180) ---------------------------------------------------------
-// Same kernels (WT = true), same routing between them as the unweighted entry points, same field layout. Block partials are (sum w nll, sum w), image-major.
-namespace {
-inline int wfwd_blocks(long hw) { return (int)std::min<long>((hw + 255) / 256, 512); }      // x blocks per image of the flat weighted forward
-
-int fill_w(CEGeom& g, const float* weights, int64_t weight_stride, int per_image, const char* who) {
-  PM_REQUIRE(weights, PM_EINVAL, "%s: null weights", who);
-  PM_REQUIRE(weight_stride == 0 || weight_stride >= g.C, PM_EINVAL, "%s: weight_stride %lld is neither 0 nor >= %d classes", who, (long long)weight_stride, g.C);
-  PM_REQUIRE(per_image == 0 || per_image == 1, PM_EINVAL, "%s: per_image %d is neither 0 nor 1", who, per_image);
-  g.wts = weights, g.wstride = (long)weight_stride, g.per_image = per_image;
-  return PM_OK;
-}
-
-// per: block partials per image. Global form: loss and total weight in the order of the unweighted reduce, then the per-image weight sums.
-inline void wce_final(const float* part, int per, int n, int per_image, float* loss_out, hipStream_t st) {
-  if (!per_image) hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, n * per, loss_out);
-  hipLaunchKernelGGL(ce_final_img_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, per, n, per_image, loss_out);
-}
-}  // namespace
-
-extern "C" size_t pm_upsample_wce_loss_floats(int n) { return (size_t)2 + (size_t)std::max(n, 0); }
-
-extern "C" size_t pm_upsample_wce_workspace(int n, int H, int W) {      // one (sum w nll, sum w) pair per block of any weighted forward kernel
-  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H * 2) * 2 * sizeof(float), 256);
-}
-
-extern "C" int pm_upsample_wce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
-                                   int per_image, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_wce_fwd");
-  CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_wce_fwd")) return e;
-  if (int e = fill_w(g, weights, weight_stride, per_image, "upsample_wce_fwd")) return e;
-  PM_REQUIRE(loss_out && ws && ws_bytes >= pm_upsample_wce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_wce_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  int per;
-  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);
-  if (row_lds <= 48 * 1024 && (long)g.n * H <= (1 << 20) && W >= 32) {      // as pm_upsample_ce_fwd
-    per = H;
-    if (g.C == 19) hipLaunchKernelGGL((ce_fwd_rows_kernel<19, true>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
-    else hipLaunchKernelGGL((ce_fwd_rows_kernel<0, true>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
-  } else {
-    PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "upsample_wce_fwd: %d images > 65535", g.n);
-    per = wfwd_blocks((long)H * W);
-    if (g.C == 19) hipLaunchKernelGGL((ce_fwd_kernel<19, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws);
-    else hipLaunchKernelGGL((ce_fwd_kernel<0, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws);
-  }
-  wce_final((const float*)ws, per, g.n, per_image, loss_out, st);
-  return pm_check_launch("upsample_wce_fwd");
-}
-
-extern "C" int pm_upsample_wce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
-                                         int per_image, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_wce_fwd_field");
-  CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_wce_fwd_field")) return e;
-  if (int e = fill_w(g, weights, weight_stride, per_image, "upsample_wce_fwd_field")) return e;
-  PM_REQUIRE(loss_out && field && ws && ws_bytes >= pm_upsample_wce_workspace(g.n, H, W), PM_EWORKSPACE, "upsample_wce_fwd_field: workspace too small / null field");
-  hipStream_t st = (hipStream_t)stream;
-  if (const Rows2Plan r = rows2_plan(g); r.ok) {
-    rows2_launch<true>(g, r, (float*)ws, field, st);
-    wce_final((const float*)ws, g.h * r.nseg, g.n, per_image, loss_out, st);
-    return pm_check_launch("upsample_wce_fwd_field");
-  }
-  const FusedPlan p = fused_plan(g);
-  PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * H <= (1l << 30), PM_EUNSUPPORTED, "upsample_wce_fwd_field: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
-  if (int e = fused_launch<true, true>(g, p, (float*)ws, field, st)) return e;
-  wce_final((const float*)ws, H, g.n, per_image, loss_out, st);
-  return pm_check_launch("upsample_wce_fwd_field");
-}
-
-extern "C" int pm_upsample_wce_bwd_field(const pm_tensor* logits, float inv_temp, int H, int W, int per_image, const float* loss_out, const float* gscale,
-                                         const float* field, const pm_tensor* dlogits, void* stream) {
-  PM_REQUIRE_F32(logits, "upsample_wce_bwd_field");
-  PM_REQUIRE_F32(dlogits, "upsample_wce_bwd_field");
-  CEGeom g;
-  static const int64_t dummy = 0;
-  if (int e = fill(g, logits, inv_temp, &dummy, H, W, "upsample_wce_bwd_field")) return e;      // the row pass reads neither labels, logits nor weights
-  PM_REQUIRE(per_image == 0 || per_image == 1, PM_EINVAL, "upsample_wce_bwd_field: per_image %d is neither 0 nor 1", per_image);
-  PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "upsample_wce_bwd_field: bad args");
-  g.per_image = per_image;
-  const long total = (long)g.n * g.h * g.w * g.C;
-  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
-  if (rows2_plan(g).ok)
-    hipLaunchKernelGGL(ce_bwd_rows2_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, field + total, loss_out, gscale, (float*)dlogits->ptr,
-                       (long)dlogits->pitch);
-  else
-    hipLaunchKernelGGL(ce_bwd_cols_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, loss_out, gscale, (float*)dlogits->ptr, (long)dlogits->pitch);
-  return pm_check_launch("upsample_wce_bwd_field");
-}
 
 // ---- per-image class weights from the labels: ImageBasedCrossEntropyLoss2d.calculate_weights (loss.py:136-146) without the trip through the host ---------------------
 // counts: LDS integer counters per block, one row of block counts per (image, block), folded by integer adds -- order-free, so deterministic. The weight expression is

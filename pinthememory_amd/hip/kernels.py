@@ -821,20 +821,69 @@ def label_nearest(lab, size):
     return out
 
 
-# ---- fused upsample + cross entropy -----------------------------------------------------------------------------
-def upsample_ce_fwd(logits, labels, inv_temp=1.0):
-    n, H, W = labels.shape
-    out = torch.empty(2, dtype=torch.float32, device=logits.device)
-    lib = _lib()
-    nb = lib.pm_upsample_ce_workspace(n, H, W)
-    ws = workspace(nb, logits.device)
-    check(lib.pm_upsample_ce_fwd(byref(tdesc(logits)), inv_temp, labels.data_ptr(), H, W, out.data_ptr(), ptr(ws), nb, stream()), 'pm_upsample_ce_fwd')
+# ---- fused upsample + cross entropy, plain and weighted (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180) ---------------
+# One private function per operation; `w` is None or (weights, per_image) and picks the pm_upsample_ce_* or the pm_upsample_wce_* entry point. The weighted forms
+# differ in three arguments, in the size of loss_out (2 + n floats: include/pinmem_hip.h) and in the workspace formula.
+def _wce_weights(weights, logits):
+    """[C] (one row for the batch: stride 0) or [n, C] float32 weights -> (tensor kept alive, row stride)."""
+    n, C = logits.shape[0], logits.shape[3]
+    weights = weights.to(device=logits.device, dtype=torch.float32)
+    if weights.dim() == 1:
+        assert weights.shape[0] == C, 'expected %d class weights, got %s' % (C, tuple(weights.shape))
+        return weights.contiguous(), 0
+    assert weights.dim() == 2 and tuple(weights.shape) == (n, C), 'expected [%d, %d] weight rows, got %s' % (n, C, tuple(weights.shape))
+    if weights.stride(1) != 1:
+        weights = weights.contiguous()
+    return weights, (weights.stride(0) if n > 1 else C)
+
+
+def _ce_loss_out(n, device, w, out):
+    need = 2 if w is None else _lib().pm_upsample_wce_loss_floats(n)
+    if out is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
     return out
 
 
-def upsample_ce_bwd(logits, labels, loss_out, gscale, inv_temp=1.0):
+def _ce_fwd(logits, labels, inv_temp, w, out, want_field):
+    """-> loss_out, or (loss_out, field) for the training forward."""
     n, H, W = labels.shape
-    dl = new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
+    out = _ce_loss_out(n, logits.device, w, out)
+    lib, ld = _lib(), tdesc(logits)
+    field = torch.empty(lib.pm_upsample_ce_field_bytes(byref(ld), H, W) // 4, dtype=torch.float32, device=logits.device) if want_field else None
+    nb = (lib.pm_upsample_ce_workspace if w is None else lib.pm_upsample_wce_workspace)(n, H, W)
+    ws = workspace(nb, logits.device)
+    name = 'pm_upsample_%s_fwd%s' % ('ce' if w is None else 'wce', '_field' if want_field else '')
+    wargs = ()
+    if w is not None:
+        wt, stride = _wce_weights(w[0], logits)
+        wargs = (wt.data_ptr(), stride, int(bool(w[1])))
+    fargs = (field.data_ptr(),) if want_field else ()
+    check(getattr(lib, name)(byref(ld), inv_temp, labels.data_ptr(), H, W, *wargs, out.data_ptr(), *fargs, ptr(ws), nb, stream()), name)
+    return (out, field) if want_field else out
+
+
+def _ce_dlogits(logits):
+    return new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
+
+
+def _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp, per_image=None):
+    H, W = label_hw
+    dl = _ce_dlogits(logits)
+    name = 'pm_upsample_ce_bwd_field' if per_image is None else 'pm_upsample_wce_bwd_field'
+    wargs = () if per_image is None else (int(bool(per_image)),)
+    check(getattr(_lib(), name)(byref(tdesc(logits)), inv_temp, H, W, *wargs, loss_out.data_ptr(), ptr(gscale), field.data_ptr(), byref(tdesc(dl)), stream()), name)
+    return dl
+
+
+def upsample_ce_fwd(logits, labels, inv_temp=1.0):
+    return _ce_fwd(logits, labels, inv_temp, None, None, False)
+
+
+def upsample_ce_bwd(logits, labels, loss_out, gscale, inv_temp=1.0):
+    """The backward after upsample_ce_fwd: the field is rebuilt in the workspace by a second sweep over labels and logits."""
+    n, H, W = labels.shape
+    dl = _ce_dlogits(logits)
     lib, ld = _lib(), tdesc(logits)
     nb = lib.pm_upsample_ce_bwd_workspace(byref(ld), H, W)
     ws = workspace(nb, logits.device)
@@ -850,26 +899,27 @@ def upsample_ce_fused_ok(logits, label_hw):
 
 def upsample_ce_fwd_field(logits, labels, inv_temp=1.0):
     """Training forward: -> (loss_out[2], field). The field is what upsample_ce_bwd_field needs instead of a second sweep over labels and logits."""
-    n, H, W = labels.shape
-    out = torch.empty(2, dtype=torch.float32, device=logits.device)
-    lib, ld = _lib(), tdesc(logits)
-    field = torch.empty(lib.pm_upsample_ce_field_bytes(byref(ld), H, W) // 4, dtype=torch.float32, device=logits.device)
-    nb = lib.pm_upsample_ce_workspace(n, H, W)
-    ws = workspace(nb, logits.device)
-    check(lib.pm_upsample_ce_fwd_field(byref(ld), inv_temp, labels.data_ptr(), H, W, out.data_ptr(), field.data_ptr(), ptr(ws), nb, stream()),
-          'pm_upsample_ce_fwd_field')
-    return out, field
+    return _ce_fwd(logits, labels, inv_temp, None, None, True)
 
 
 def upsample_ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp=1.0):
-    H, W = label_hw
-    dl = new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
-    check(_lib().pm_upsample_ce_bwd_field(byref(tdesc(logits)), inv_temp, H, W, loss_out.data_ptr(), ptr(gscale), field.data_ptr(), byref(tdesc(dl)), stream()),
-          'pm_upsample_ce_bwd_field')
-    return dl
+    return _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp)
 
 
-# ---- weighted forms: CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d (loss.py:20-43,71-88,120-180) -------------------------
+def upsample_wce_fwd(logits, labels, weights, per_image, inv_temp=1.0, out=None):
+    """-> loss_out[2 + n]: [0] the loss, [1] the total weight sum, [2 + b] the weight sum of image b (include/pinmem_hip.h)."""
+    return _ce_fwd(logits, labels, inv_temp, (weights, per_image), out, False)
+
+
+def upsample_wce_fwd_field(logits, labels, weights, per_image, inv_temp=1.0, out=None):
+    """Training forward: -> (loss_out[2 + n], field); the field has the layout and size of upsample_ce_fwd_field's."""
+    return _ce_fwd(logits, labels, inv_temp, (weights, per_image), out, True)
+
+
+def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image, inv_temp=1.0):
+    return _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp, per_image)
+
+
 def label_class_weights(labels, classes, upper_bound=1.0, norm=False, per_batch=False, out=None):
     """ImageBasedCrossEntropyLoss2d.calculate_weights on the device: int64 labels [n,H,W] -> float32 [n, classes] weight rows, bit-equal to the numpy
     expression, without a host sync (per_batch: the batch histogram in every row). `out`: a contiguous float32 buffer of at least n * classes elements."""
@@ -885,62 +935,6 @@ def label_class_weights(labels, classes, upper_bound=1.0, norm=False, per_batch=
     check(lib.pm_label_class_weights(labels.data_ptr(), n, H, W, classes, float(upper_bound), int(bool(norm)), int(bool(per_batch)), out.data_ptr(), ptr(ws), nb,
                                      stream()), 'pm_label_class_weights')
     return out
-
-
-def _wce_weights(weights, logits):
-    """[C] (one row for the batch: stride 0) or [n, C] float32 weights -> (tensor kept alive, row stride)."""
-    n, C = logits.shape[0], logits.shape[3]
-    weights = weights.to(device=logits.device, dtype=torch.float32)
-    if weights.dim() == 1:
-        assert weights.shape[0] == C, 'expected %d class weights, got %s' % (C, tuple(weights.shape))
-        return weights.contiguous(), 0
-    assert weights.dim() == 2 and tuple(weights.shape) == (n, C), 'expected [%d, %d] weight rows, got %s' % (n, C, tuple(weights.shape))
-    if weights.stride(1) != 1:
-        weights = weights.contiguous()
-    return weights, (weights.stride(0) if n > 1 else C)
-
-
-def _wce_out(n, device, out):
-    need = _lib().pm_upsample_wce_loss_floats(n)
-    if out is None:
-        return torch.empty(need, dtype=torch.float32, device=device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
-    return out
-
-
-def upsample_wce_fwd(logits, labels, weights, per_image, inv_temp=1.0, out=None):
-    """-> loss_out[2 + n]: [0] the loss, [1] the total weight sum, [2 + b] the weight sum of image b (include/pinmem_hip.h)."""
-    n, H, W = labels.shape
-    out = _wce_out(n, logits.device, out)
-    wt, stride = _wce_weights(weights, logits)
-    lib = _lib()
-    nb = lib.pm_upsample_wce_workspace(n, H, W)
-    ws = workspace(nb, logits.device)
-    check(lib.pm_upsample_wce_fwd(byref(tdesc(logits)), inv_temp, labels.data_ptr(), H, W, wt.data_ptr(), stride, int(bool(per_image)), out.data_ptr(), ptr(ws), nb,
-                                  stream()), 'pm_upsample_wce_fwd')
-    return out
-
-
-def upsample_wce_fwd_field(logits, labels, weights, per_image, inv_temp=1.0, out=None):
-    """Training forward: -> (loss_out[2 + n], field); the field has the layout and size of upsample_ce_fwd_field's."""
-    n, H, W = labels.shape
-    out = _wce_out(n, logits.device, out)
-    wt, stride = _wce_weights(weights, logits)
-    lib, ld = _lib(), tdesc(logits)
-    field = torch.empty(lib.pm_upsample_ce_field_bytes(byref(ld), H, W) // 4, dtype=torch.float32, device=logits.device)
-    nb = lib.pm_upsample_wce_workspace(n, H, W)
-    ws = workspace(nb, logits.device)
-    check(lib.pm_upsample_wce_fwd_field(byref(ld), inv_temp, labels.data_ptr(), H, W, wt.data_ptr(), stride, int(bool(per_image)), out.data_ptr(), field.data_ptr(),
-                                        ptr(ws), nb, stream()), 'pm_upsample_wce_fwd_field')
-    return out, field
-
-
-def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image, inv_temp=1.0):
-    H, W = label_hw
-    dl = new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
-    check(_lib().pm_upsample_wce_bwd_field(byref(tdesc(logits)), inv_temp, H, W, int(bool(per_image)), loss_out.data_ptr(), ptr(gscale), field.data_ptr(),
-                                           byref(tdesc(dl)), stream()), 'pm_upsample_wce_bwd_field')
-    return dl
 
 
 # ---- validation sweep: loss + argmax + confusion matrix of the up-sampled logits (train.py:847-939) -------------------------------

@@ -708,59 +708,35 @@ def fanout(x, n):
     return _Fanout.apply(x, n)
 
 
-CE_FUSED = _os.environ.get('PM_CE_FUSED', '1') == '1'      # A/B knob: 0 = forward and backward each sweep labels and logits
-
-
 class _UpsampleCE(torch.autograd.Function):
     """mean CE(ignore 255) of bilinearly up-sampled logits vs full-resolution labels, logits never materialised. With a graph attached the
-    forward also leaves the column-reduced gradient field (K.upsample_ce_fwd_field), so the backward is one short row pass."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, inv_temp, want_grad):
-        lv = nhwc(logits)
-        labels = labels.contiguous()
-        ctx.inv_temp, ctx.hw = inv_temp, tuple(labels.shape[1:])
-        if want_grad and CE_FUSED:
-            out, field = K.upsample_ce_fwd_field(lv, labels, inv_temp)
-            ctx.fused = True
-            ctx.save_for_backward(lv, out, field)
-        else:
-            out = K.upsample_ce_fwd(lv, labels, inv_temp)
-            ctx.fused = False
-            ctx.save_for_backward(lv, labels, out)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        gs = g.reshape(1).float().contiguous()
-        if ctx.fused:
-            lv, out, field = ctx.saved_tensors
-            return nchw(K.upsample_ce_bwd_field(lv, ctx.hw, out, field, gs, ctx.inv_temp)), None, None, None
-        lv, labels, out = ctx.saved_tensors
-        return nchw(K.upsample_ce_bwd(lv, labels, out, gs, ctx.inv_temp)), None, None, None
-
-
-class _UpsampleWCE(torch.autograd.Function):
-    """_UpsampleCE with class weights: w = weights[label] ([C]) or weights[image][label] ([n, C]); per_image: the sum over images of each image's weighted mean
+    forward also leaves the column-reduced gradient field (K.upsample_ce_fwd_field), so the backward is one short row pass.
+    weights (None: the plain loss): w = weights[label] ([C]) or weights[image][label] ([n, C]); per_image: the sum over images of each image's weighted mean
     (ImageBasedCrossEntropyLoss2d), else sum w nll / sum w over the batch (CrossEntropyLoss(weight)). The weights carry no gradient."""
 
     @staticmethod
-    def forward(ctx, logits, labels, weights, per_image, inv_temp, want_grad):
+    def forward(ctx, logits, labels, inv_temp, want_grad, weights=None, per_image=False):
         lv = nhwc(logits)
         labels = labels.contiguous()
-        ctx.inv_temp, ctx.hw, ctx.per_image = inv_temp, tuple(labels.shape[1:]), per_image
-        if want_grad:
-            out, field = K.upsample_wce_fwd_field(lv, labels, weights, per_image, inv_temp)
-            ctx.save_for_backward(lv, out, field)
+        ctx.inv_temp, ctx.hw, ctx.per_image = inv_temp, tuple(labels.shape[1:]), (None if weights is None else per_image)
+        if not want_grad:
+            return (K.upsample_ce_fwd(lv, labels, inv_temp) if weights is None else K.upsample_wce_fwd(lv, labels, weights, per_image, inv_temp))[0]
+        if weights is None:
+            out, field = K.upsample_ce_fwd_field(lv, labels, inv_temp)
         else:
-            out = K.upsample_wce_fwd(lv, labels, weights, per_image, inv_temp)
+            out, field = K.upsample_wce_fwd_field(lv, labels, weights, per_image, inv_temp)
+        ctx.save_for_backward(lv, out, field)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
         gs = g.reshape(1).float().contiguous()
         lv, out, field = ctx.saved_tensors
-        return nchw(K.upsample_wce_bwd_field(lv, ctx.hw, out, field, gs, ctx.per_image, ctx.inv_temp)), None, None, None, None, None
+        if ctx.per_image is None:
+            dl = K.upsample_ce_bwd_field(lv, ctx.hw, out, field, gs, ctx.inv_temp)
+        else:
+            dl = K.upsample_wce_bwd_field(lv, ctx.hw, out, field, gs, ctx.per_image, ctx.inv_temp)
+        return nchw(dl), None, None, None, None, None
 
 
 class _MemRead(torch.autograd.Function):
@@ -941,7 +917,7 @@ def upsample_wce(logits, labels, weights, per_image, inv_temp=1.0):
     per_image = bool(per_image)
     if not K.upsample_ce_fused_ok(nhwc(logits), tuple(labels.shape[1:])):      # as upsample_ce: rows too wide for the fused kernels' LDS
         return weighted_ce(resize(logits, tuple(labels.shape[1:])) * float(inv_temp), labels, weights, per_image)
-    return _UpsampleWCE.apply(logits, labels, weights.detach(), per_image, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
+    return _UpsampleCE.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad), weights.detach(), per_image)
 
 
 def mem_read(x, mem, noise=None):
