@@ -250,7 +250,7 @@ int pm_bn_apply_mask_affine(const pm_tensor* x, const float* mean, const float* 
                             int relu, const pm_tensor* y, uint8_t* mask /*nullable*/, void* stream);
 /* pm_bn_bwd_apply (below) on dyz = dy masked by those bytes, for ANY x of the mask's shape with its own statistics: together with
  * pm_bn_bwd_reduce_mask(gmask = NULL) the backward of BN + residual + ReLU -- and of the downsample BatchNorm behind it -- without a stored masked gradient.
- * Bit-identical to pm_bn_bwd_apply(dy = gmask, relu = 0). fp32 tensors only. */
+ * Bit-identical to pm_bn_bwd_apply(dy = gmask, relu = 0). fp32 tensors only. PM_EINVAL, before any launch, for a `sums` that is not 16-byte aligned. */
 int pm_bn_bwd_apply_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                          const float* sums, float count, const pm_tensor* dx, void* stream);
 /* backward: dyz = dy * mask, sums[2*C] = sum(dyz) | sum(dyz * xhat).  relu: 0 no activation (mask = 1); 1 mask = y > 0 read from the
@@ -262,7 +262,8 @@ int pm_bn_bwd_reduce(const pm_tensor* dy, const pm_tensor* y /*relu == 1 only*/,
                      float* sums, void* ws, size_t ws_bytes, void* stream);
 /* dx = gamma*invstd*(dyz - sum_dy/count - xhat*sum_dy_xhat/count); dres = dyz (nullable); count = global element count.
  * count <= 0: the count is read from the device at sums[2*C] (SyncBatchNorm all-reduces [sums | local count] in one exchange, so ranks
- * with uneven batches normalise by the true global count, as torch.nn.SyncBatchNorm does). */
+ * with uneven batches normalise by the true global count, as torch.nn.SyncBatchNorm does).
+ * PM_EINVAL, before any launch, for a `sums` that is not 16-byte aligned (both dtypes): the pass reads it 16 bytes at a time. */
 int pm_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y /*relu == 1 only*/, const pm_tensor* x, const float* mean, const float* invstd,
                     const float* gamma, const float* beta /*relu == 2 only*/, const float* sums, float count, int relu, const pm_tensor* dx,
                     const pm_tensor* dres /*nullable*/, void* stream);
@@ -298,7 +299,8 @@ int pm_maxpool3x3s2_bwd(const pm_tensor* dy, const uint8_t* argmax, const pm_ten
  * Forward: pm_maxpool3x3s2_fwd of relu(bn(x)), x the raw convolution output -- each tap is normalised and clamped before the comparison, so y and argmax (ties
  * among clamped zeros included) are those of pooling the stored activation.
  * Backward: pm_bn_bwd_reduce / pm_bn_bwd_apply with relu = 2 whose incoming gradient is pm_maxpool3x3s2_bwd(dy_pooled, argmax), gathered per pixel inside the
- * pass instead of read from a tensor. Bit-identical to the separate kernels; workspace of pm_bn_workspace(x); count as pm_bn_bwd_apply. */
+ * pass instead of read from a tensor. Bit-identical to the separate kernels; workspace of pm_bn_workspace(x); count as pm_bn_bwd_apply.
+ * pm_bn_bwd_apply_pool: PM_EINVAL, before any launch, for a `sums` that is not 16-byte aligned. */
 int pm_maxpool3x3s2_bn_relu_fwd(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* y,
                                 uint8_t* argmax, void* stream);
 int pm_bn_bwd_reduce_pool(const pm_tensor* dy_pooled, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,

@@ -1,45 +1,145 @@
-// K4: BatchNorm2d over NHWC fp32 (train statistics, apply + ReLU + residual, backward), HBM-bound.
+// K4: BatchNorm2d over NHWC activations of both tiers (train statistics, apply + ReLU + residual, backward), HBM-bound.
 // Replaces mynn.Norm2d (/root/reference/network/mynn.py:8-14) == nn.BatchNorm2d / SyncBatchNorm everywhere it is
 // used (Resnet.py:146-151,405,456; deepv3plus.py:73,79,88,399,405,410,413,421; memory.py:76,105).
 // Statistics are shifted sums (shift = first pixel of each channel) -> (mean, M2, count), combined in double in a
 // fixed order: one pass over the activation, no catastrophic cancellation, deterministic, mergeable across ranks.
+// One body per piece for fp32 and bf16 tensors: a lane moves 16 bytes (Elem<T>::V channels), values are widened to fp32 in registers and travel as float[V];
+// every statistic / reduction / accumulator is fp32 (second stages in double); bf16 results are rounded (nearest even) once, on the way out.
+#include <type_traits>
+
 #include "pm_common.h"
 
 namespace {
 
-constexpr int CB = 64;    // channels per block
-constexpr int RL = 16;    // row lanes per block (256 threads = 16 float4 groups x 16 rows)
-
-// y = (x - mean) * invstd * gamma + beta, evaluated the same way in the forward pass and wherever the backward pass rebuilds the
-// ReLU mask from x (two explicit FMAs: bit-identical in both places whatever the compiler would contract).
-__device__ __forceinline__ float bn_affine(float v, float mu, float is, float ga, float be) { return pm_bn_affine(v, mu, is, ga, be); }
-
-inline int chunk_rows(long P, int C) {  // pixels per block: >= 2048 blocks over (pixel chunks x 64-channel groups), >= 64 rows each
-  const long colblocks = std::max<long>(1, (C + CB - 1) / CB);
-  const long want = std::max<long>(512, 2048 / colblocks);   // narrow tensors (64 channels) need more pixel chunks to fill the GPU
-  long r = (P + want - 1) / want;
-  r = std::max<long>(r, 64);
-  return (int)((r + RL - 1) / RL * RL);
+// ---- the element trait: what differs between the tiers -----------------------------------------------------------------------------
+template <typename T>
+struct Elem;
+template <>
+struct Elem<float> {
+  static constexpr int V = 4;      // channels per 16-byte lane access
+  static __device__ __forceinline__ void ld(const float* p, float* v) {
+    const float4 a = PM_LD4(p);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+  }
+  static __device__ __forceinline__ void st(float* p, const float* v) { PM_ST4(p, make_float4(v[0], v[1], v[2], v[3])); }
+  static __device__ __forceinline__ float widen(float v) { return v; }
+  static int gpr(int) { return 16; }      // lane groups per pixel row: 16 float4 groups x 16 row lanes
+  static int check(const pm_tensor* t, const char* who) {
+    PM_REQUIRE_F32(t, who);      // a mixed-type call ends here
+    PM_REQUIRE(t && t->ptr && pm_vec4(t), PM_EINVAL, "%s: tensor must be 16B aligned, pitch %% 4 == 0 and C %% 4 == 0", who);
+    return PM_OK;
+  }
+};
+template <>
+struct Elem<pm_bf16> {
+  static constexpr int V = 8;
+  static __device__ __forceinline__ void ld(const pm_bf16* p, float* v) { pm_ld8(p, v); }
+  static __device__ __forceinline__ void st(pm_bf16* p, const float* v) { pm_st8(p, v); }
+  static __device__ __forceinline__ float widen(pm_bf16 v) { return pm_bf16_to_f32(v); }
+  static int gpr(int C) { return C <= 64 ? 8 : 16; }      // 8 for tensors of <= 64 channels: no idle half-waves on the 64-channel maps of layer1
+  static int check(const pm_tensor* t, const char* who) {
+    PM_REQUIRE(t && t->ptr && pm_vec8(t), PM_EINVAL, "%s: bf16 tensors must be 16B aligned with pitch %% 8 == 0 and C %% 8 == 0", who);
+    return PM_OK;
+  }
+};
+// V per-channel fp32 parameters (mean, invstd, gamma, beta, sums)
+template <int V>
+__device__ __forceinline__ void ldp(const float* p, float* v) {
+  if constexpr (V == 4) Elem<float>::ld(p, v);
+  else pm_ld8f(p, v);
+}
+// thread -> (pixel, V channels), f(pixel, channel) a __device__ lambda
+template <typename T, typename F>
+int ew_launch(long pixels, int c, hipStream_t st, const char* name, F f) {
+  if constexpr (Elem<T>::V == 8) {
+    return pm_ew16_launch(pixels, c, st, name, f);
+  } else {      // pm_ew_launch(true, ...) without its scalar twin
+    if (pixels * c == 0) return PM_OK;
+    hipLaunchKernelGGL((pm_ew_kernel<true, F>), dim3(pm_ew_grid(pixels * c / 4)), dim3(256), 0, st, pixels, c, f);
+    return pm_check_launch(name);
+  }
 }
 
-// partial[blk][c][2] : sum(x - K[c]), sum((x - K[c])^2) over the block's pixel chunk
-__global__ __launch_bounds__(256) void bn_stats_partial(const float* __restrict__ x, long pitch, long P, int C, int rows, float* __restrict__ part) {
-  __shared__ float sm[RL][CB][2];
-  const int g = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int c = blockIdx.y * CB + g * 4;
-  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
-  float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-  if (c < C) {
-    const float4 k = PM_LD4(x + c);
-    for (long p = p0 + r; p < p1; p += RL) {
-      const float4 v = PM_LD4(x + p * pitch + c);
-      const float d0 = v.x - k.x, d1 = v.y - k.y, d2 = v.z - k.z, d3 = v.w - k.w;
-      s1[0] += d0, s1[1] += d1, s1[2] += d2, s1[3] += d3;
-      s2[0] += d0 * d0, s2[1] += d1 * d1, s2[2] += d2 * d2, s2[3] += d3 * d3;
-    }
-  }
+// ---- elementwise expressions ----------------------------------------------------------------------------------------------------------
+// y = (x - mean) * invstd * gamma + beta, evaluated the same way in the forward pass and wherever the backward pass rebuilds the
+// ReLU mask from x (two explicit FMAs: bit-identical in both places whatever the compiler would contract).
+template <int V>
+__device__ __forceinline__ void bn_affine(const float* v, const float* mu, const float* is, const float* ga, const float* be, float* o) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) sm[r][g * 4 + j][0] = s1[j], sm[r][g * 4 + j][1] = s2[j];
+  for (int j = 0; j < V; ++j) o[j] = pm_bn_affine(v[j], mu[j], is[j], ga[j], be[j]);
+}
+// the ReLU passes g where the activation o was positive (o: the forward output, or bn_affine of x)
+template <int V>
+__device__ __forceinline__ void relu_mask(const float* o, float* g) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) g[j] = o[j] > 0.f ? g[j] : 0.f;
+}
+// ... or where bit j of the byte bn_apply left for the group is set (positive_bits)
+template <int V>
+__device__ __forceinline__ void relu_mask_bits(unsigned mb, float* g) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) g[j] = ((mb >> j) & 1u) ? g[j] : 0.f;
+}
+template <int V>
+__device__ __forceinline__ unsigned positive_bits(const float* o) {
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < V; ++j) m |= o[j] > 0.f ? (1u << j) : 0u;
+  return m;
+}
+template <int V>
+__device__ __forceinline__ void relu(float* o) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) o[j] = fmaxf(o[j], 0.f);
+}
+// count <= 0 on the host: the element count lives on the device at sums[2 * C] -- SyncBatchNorm all-reduces it with the two sums, so ranks with
+// different batch sizes normalise by the true global count (torch.nn.SyncBatchNorm gathers the counts the same way)
+__device__ __forceinline__ float bn_inv_n(bool dev_count, const float* sums, int C, float host_inv_n) { return dev_count ? 1.f / sums[2 * C] : host_inv_n; }
+// dx = (g - sum(g) / n - xhat * sum(g xhat) / n) * invstd * gamma, with k1 = s1 * inv_n, k2 = s2 * inv_n, sg = is * ga -- hoisted by the caller or written in place.
+// A macro: as a function the three products are evaluated before the rest, and that order alone costs the bf16 generic pass two VGPRs (64 against 62).
+#define BN_DX(g, v, mu, is, k1, k2, sg) (((g) - (k1) - ((v) - (mu)) * (is) * (k2)) * (sg))
+
+// ---- reductions -------------------------------------------------------------------------------------------------------------------------
+// GPR lane groups per pixel row, RL = 256 / GPR row lanes, CB channels per block
+template <int V, int GPR>
+struct Geo {
+  static constexpr int RL = 256 / GPR, CB = GPR * V;
+};
+struct Plan {
+  int gpr, rows, nb, colblocks;      // rows: pixels per block: >= 2048 blocks over (pixel chunks x channel groups), >= 64 rows each
+};
+template <typename T>
+Plan bn_plan(long P, int C) {
+  Plan p;
+  p.gpr = Elem<T>::gpr(C);
+  const int RL = 256 / p.gpr, CB = p.gpr * Elem<T>::V;
+  p.colblocks = pm_cdiv(C, CB);
+  const long want = std::max<long>(512, 2048 / std::max<long>(1, p.colblocks));   // narrow tensors (64 channels) need more pixel chunks to fill the GPU
+  const long r = std::max<long>((P + want - 1) / want, 64);
+  p.rows = (int)((r + RL - 1) / RL * RL);
+  p.nb = pm_cdiv(P, p.rows);
+  return p;
+}
+template <typename T>
+size_t bn_workspace(const pm_tensor* x) {
+  return pm_align_up((size_t)bn_plan<T>(pm_pixels(x), x->c).nb * x->c * 2 * sizeof(float), 256);
+}
+// launch(integral_constant<int, GPR>) for the plan's GPR
+template <typename T, typename L>
+void with_gpr(int gpr, L launch) {
+  if constexpr (Elem<T>::V == 8) {
+    if (gpr == 8) return launch(std::integral_constant<int, 8>{});
+  }
+  launch(std::integral_constant<int, 16>{});
+}
+
+// block-level reduce of per-thread (s1[V], s2[V]) over the row lanes, in row-lane order -> part[blk][c][2]
+template <int V, int GPR>
+__device__ __forceinline__ void block_reduce_store(const float* s1, const float* s2, int g, int r, int C, float* __restrict__ part) {
+  constexpr int RL = Geo<V, GPR>::RL, CB = Geo<V, GPR>::CB;
+  __shared__ float sm[RL][CB][2];
+#pragma unroll
+  for (int j = 0; j < V; ++j) sm[r][g * V + j][0] = s1[j], sm[r][g * V + j][1] = s2[j];
   __syncthreads();
   if (threadIdx.x < CB * 2) {
     const int cc = threadIdx.x >> 1, w = threadIdx.x & 1;
@@ -49,6 +149,32 @@ __global__ __launch_bounds__(256) void bn_stats_partial(const float* __restrict_
     const int ch = blockIdx.y * CB + cc;
     if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
   }
+}
+
+// partial[blk][c][2] : sum(x - K[c]), sum((x - K[c])^2) over the block's pixel chunk, K = the first pixel (shifted sums: no cancellation)
+template <typename T, int GPR>
+__global__ __launch_bounds__(256) void bn_stats_partial(const T* __restrict__ x, long pitch, long P, int C, int rows, float* __restrict__ part) {
+  constexpr int V = Elem<T>::V;
+  const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
+  const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
+  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
+  float s1[V], s2[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
+  if (c < C) {
+    float k[V];
+    Elem<T>::ld(x + c, k);
+    for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
+      float v[V];
+      Elem<T>::ld(x + p * pitch + c, v);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float d = v[j] - k[j];
+        s1[j] += d, s2[j] += d * d;
+      }
+    }
+  }
+  block_reduce_store<V, GPR>(s1, s2, g, r, C, part);
 }
 
 // Second stage: 4 channels x 64 lanes per block; each lane sums a strided subset of the block partials in double, the 64
@@ -72,10 +198,24 @@ __device__ __forceinline__ void final_sums(const float* __restrict__ part, int n
   }
 }
 
-// FIN: local statistics (no process group) -- mean / invstd and the running-moment update of bn_finalize_kernel happen here, on the
-// same float values the two-kernel path hands over through `moments` (bit-identical), one launch less per BN layer.
+// The tail of every statistics kernel: channel c's (mean m, M2 m2, count n) leave as moments (mean | M2 | count, the SyncBatchNorm exchange format), or (FIN) as
+// mean / invstd plus the running-moment update, on the same float values the moments would hand over (bit-identical), one launch less per BN layer.
 template <bool FIN>
-__global__ __launch_bounds__(256) void bn_stats_final(const float* __restrict__ part, int nb, const float* __restrict__ x, long P, int C, float* __restrict__ moments,
+__device__ __forceinline__ void bn_finish(int c, int C, float m, float m2, float n, float* __restrict__ moments, float eps, float* __restrict__ mean,
+                                          float* __restrict__ invstd, float* running_mean, float* running_var, float momentum) {
+  if constexpr (!FIN) {
+    moments[c] = m, moments[C + c] = m2, moments[2 * C + c] = n;
+  } else {
+    const float var = m2 / n;
+    mean[c] = m;
+    invstd[c] = 1.f / sqrtf(var + eps);
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    if (running_var && n > 1.f) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2 / (n - 1.f));   // n == 1: no unbiased estimate (0 / 0)
+  }
+}
+
+template <typename T, bool FIN>
+__global__ __launch_bounds__(256) void bn_stats_final(const float* __restrict__ part, int nb, const T* __restrict__ x, long P, int C, float* __restrict__ moments,
                                                       float eps, float* __restrict__ mean, float* __restrict__ invstd, float* running_mean, float* running_var,
                                                       float momentum) {
   const int c = blockIdx.x * FC + (threadIdx.x & (FC - 1)), lane = threadIdx.x / FC;
@@ -83,32 +223,16 @@ __global__ __launch_bounds__(256) void bn_stats_final(const float* __restrict__ 
   final_sums(part, nb, C, c, lane, s1, s2);
   if (lane != 0 || c >= C) return;
   const double n = (double)P;
-  const float m = (float)((double)x[c] + s1 / n), m2 = (float)fmax(s2 - s1 * s1 / n, 0.0), nf = (float)n;
-  if constexpr (!FIN) {
-    moments[c] = m;
-    moments[C + c] = m2;
-    moments[2 * C + c] = nf;
-  } else {
-    const float var = m2 / nf;
-    mean[c] = m;
-    invstd[c] = 1.f / sqrtf(var + eps);
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    if (running_var && nf > 1.f) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2 / (nf - 1.f));   // n == 1: no unbiased estimate (0 / 0)
-  }
+  const float m = (float)((double)Elem<T>::widen(x[c]) + s1 / n), m2 = (float)fmax(s2 - s1 * s1 / n, 0.0);
+  bn_finish<FIN>(c, C, m, m2, (float)n, moments, eps, mean, invstd, running_mean, running_var, momentum);
 }
 
 __global__ void bn_finalize_kernel(const float* __restrict__ moments, int C, float eps, float* __restrict__ mean, float* __restrict__ invstd,
                                    float* running_mean, float* running_var, float momentum) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float m = moments[c], m2 = moments[C + c], n = moments[2 * C + c];
-  const float var = m2 / n;
-  mean[c] = m;
-  invstd[c] = 1.f / sqrtf(var + eps);
-  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-  if (running_var && n > 1.f) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2 / (n - 1.f));
+  bn_finish<true>(c, C, moments[c], moments[C + c], moments[2 * C + c], nullptr, eps, mean, invstd, running_mean, running_var, momentum);
 }
-
 
 // Merge of the (mean, M2) slab partials a convolution epilogue emitted for its own output (conv_igemm.hip, staged epilogue): rows in slabs
 // of 32, part[slab][c][2]. Block = 4 channels x 64 lanes; lane l accumulates, in double, A = sum n_b mean_b and B = sum (M2_b + n_b mean_b^2)
@@ -139,102 +263,69 @@ __global__ __launch_bounds__(256) void bn_partials_final(const float* __restrict
 #pragma unroll 1
   for (int i = 0; i < FL; ++i) A += red[i][ci][0], B += red[i][ci][1];
   const double n = (double)rows, gm = A / n;
-  const float m = (float)gm, m2 = (float)fmax(B - n * gm * gm, 0.0), nf = (float)n;
-  if constexpr (MOM) {
-    moments[c] = m, moments[C + c] = m2, moments[2 * C + c] = nf;
-  } else {
-    const float var = m2 / nf;
-    mean[c] = m;
-    invstd[c] = 1.f / sqrtf(var + eps);
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    if (running_var && nf > 1.f) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2 / (nf - 1.f));
-  }
+  bn_finish<!MOM>(c, C, (float)gm, (float)fmax(B - n * gm * gm, 0.0), (float)n, moments, eps, mean, invstd, running_mean, running_var, momentum);
 }
+
+// The incoming gradient of a backward pass: a tensor, or (the stem) what pm_maxpool3x3s2_bwd would have written, gathered per pixel from the gradient of the
+// 3x3 / s2 max pool that followed the activation and its argmax bytes (pm_maxpool_gather4: the same values in the same order), so that the full-resolution
+// gradient is never written.
+template <typename T>
+struct TensorGrad {
+  const T* dy;
+  long pitch;
+  __device__ __forceinline__ void load(long p, int c, float* d) const { Elem<T>::ld(dy + p * pitch + c, d); }
+};
+struct PoolGrad {
+  const float* dyp;
+  long pitch;
+  int Ho, Wo;
+  const uint8_t* arg;
+  int H, W, C;
+  __device__ __forceinline__ void load(long p, int c, float* d) const {
+    const float4 g = pm_maxpool_gather4(dyp, pitch, Ho, Wo, arg, H, W, C, p, c);
+    d[0] = g.x, d[1] = g.y, d[2] = g.z, d[3] = g.w;
+  }
+};
 
 // backward reductions: partial[blk][c][2] = sum(dyz), sum(dyz * xhat), dyz = dy masked by the ReLU of the forward pass.
 // RELU 0: no activation. 1: mask = y > 0 read from the forward output (needed when a residual was added before the ReLU).
-// 2: mask rebuilt from x (y = relu(bn(x)), no residual) -- one tensor less to read. GOUT: also store dyz (the gradient of the
-// residual branch), so that the apply pass reads one tensor (dyz) instead of two (dy, y).
-// 3: mask from the byte per float4 group bn_apply left behind (bit e = output e of the group was positive): 1 / 16 of the bytes of reading y.
-template <int RELU, bool GOUT>
-__global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ dy, long dpitch, const float* __restrict__ y, long ypitch,
-                                                      const float* __restrict__ x, long xpitch, const float* __restrict__ mean,
-                                                      const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float* __restrict__ gout, long gpitch, long P, int C, int rows, float* __restrict__ part) {
-  __shared__ float sm[RL][CB][2];
-  const int g = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int c = blockIdx.y * CB + g * 4;
+// 2: mask rebuilt from x (y = relu(bn(x)), no residual) -- one tensor less to read.
+// 3: mask from the byte per 16-byte group bn_apply left behind (bit e = output e of the group was positive): 1 / 16 of the bytes of reading y.
+// GOUT: also store dyz (the gradient of the residual branch), so that the apply pass reads one tensor (dyz) instead of two (dy, y).
+template <typename T, int GPR, int RELU, bool GOUT, typename SRC>
+__global__ __launch_bounds__(256) void bn_bwd_partial(SRC dy, const T* __restrict__ y, long ypitch, const uint8_t* __restrict__ mask, const T* __restrict__ x, long xpitch,
+                                                      const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, T* __restrict__ gout, long gpitch, long P, int C, int rows, float* __restrict__ part) {
+  constexpr int V = Elem<T>::V;
+  const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
+  const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
   const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
-  float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  float s1[V], s2[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
   if (c < C) {
-    const float4 mu = PM_LD4(mean + c), is = PM_LD4(invstd + c);
-    float4 ga = make_float4(0.f, 0.f, 0.f, 0.f), be = ga;
-    if (RELU == 2) ga = PM_LD4(gamma + c), be = PM_LD4(beta + c);
-    for (long p = p0 + r; p < p1; p += RL) {
-      float4 d = PM_LD4(dy + p * dpitch + c);
-      const float4 v = PM_LD4(x + p * xpitch + c);
+    float mu[V], is[V], ga[V], be[V];
+    ldp<V>(mean + c, mu), ldp<V>(invstd + c, is);
+    if (RELU == 2) ldp<V>(gamma + c, ga), ldp<V>(beta + c, be);
+    for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
+      float d[V], v[V], o[V];
+      dy.load(p, c, d);
+      Elem<T>::ld(x + p * xpitch + c, v);
       if (RELU == 1) {
-        const float4 o = PM_LD4(y + p * ypitch + c);
-        d.x = o.x > 0.f ? d.x : 0.f, d.y = o.y > 0.f ? d.y : 0.f, d.z = o.z > 0.f ? d.z : 0.f, d.w = o.w > 0.f ? d.w : 0.f;
+        Elem<T>::ld(y + p * ypitch + c, o);
+        relu_mask<V>(o, d);
       } else if (RELU == 3) {
-        const unsigned mb = reinterpret_cast<const unsigned char*>(y)[p * (C >> 2) + (c >> 2)];
-        d.x = (mb & 1u) ? d.x : 0.f, d.y = (mb & 2u) ? d.y : 0.f, d.z = (mb & 4u) ? d.z : 0.f, d.w = (mb & 8u) ? d.w : 0.f;
+        relu_mask_bits<V>(mask[p * (C / V) + c / V], d);
       } else if (RELU == 2) {
-        d.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? d.x : 0.f, d.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? d.y : 0.f;
-        d.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? d.z : 0.f, d.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? d.w : 0.f;
+        bn_affine<V>(v, mu, is, ga, be, o);
+        relu_mask<V>(o, d);
       }
-      if (GOUT) PM_ST4(gout + p * gpitch + c, d);
-      s1[0] += d.x, s1[1] += d.y, s1[2] += d.z, s1[3] += d.w;
-      s2[0] += d.x * ((v.x - mu.x) * is.x), s2[1] += d.y * ((v.y - mu.y) * is.y);
-      s2[2] += d.z * ((v.z - mu.z) * is.z), s2[3] += d.w * ((v.w - mu.w) * is.w);
+      if (GOUT) Elem<T>::st(gout + p * gpitch + c, d);
+#pragma unroll
+      for (int j = 0; j < V; ++j) s1[j] += d[j], s2[j] += d[j] * ((v[j] - mu[j]) * is[j]);
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sm[r][g * 4 + j][0] = s1[j], sm[r][g * 4 + j][1] = s2[j];
-  __syncthreads();
-  if (threadIdx.x < CB * 2) {
-    const int cc = threadIdx.x >> 1, w = threadIdx.x & 1;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < RL; ++i) s += sm[i][cc][w];
-    const int ch = blockIdx.y * CB + cc;
-    if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
-  }
-}
-// bn_bwd_partial<2, false> whose incoming gradient is not a tensor: dy of pixel p is gathered from the gradient of the 3x3 / s2 max pool that followed the activation
-// (pm_maxpool_gather4: the values pm_maxpool3x3s2_bwd would have stored, in the same order), so the full-resolution gradient is never written. Same accumulation order.
-__global__ __launch_bounds__(256) void bn_bwd_partial_pool(const float* __restrict__ dyp, long dpitch, int Ho, int Wo, const uint8_t* __restrict__ arg, int H, int W,
-                                                           const float* __restrict__ x, long xpitch, const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta, long P, int C, int rows,
-                                                           float* __restrict__ part) {
-  __shared__ float sm[RL][CB][2];
-  const int g = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int c = blockIdx.y * CB + g * 4;
-  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
-  float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-  if (c < C) {
-    const float4 mu = PM_LD4(mean + c), is = PM_LD4(invstd + c), ga = PM_LD4(gamma + c), be = PM_LD4(beta + c);
-    for (long p = p0 + r; p < p1; p += RL) {
-      float4 d = pm_maxpool_gather4(dyp, dpitch, Ho, Wo, arg, H, W, C, p, c);
-      const float4 v = PM_LD4(x + p * xpitch + c);
-      d.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? d.x : 0.f, d.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? d.y : 0.f;
-      d.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? d.z : 0.f, d.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? d.w : 0.f;
-      s1[0] += d.x, s1[1] += d.y, s1[2] += d.z, s1[3] += d.w;
-      s2[0] += d.x * ((v.x - mu.x) * is.x), s2[1] += d.y * ((v.y - mu.y) * is.y);
-      s2[2] += d.z * ((v.z - mu.z) * is.z), s2[3] += d.w * ((v.w - mu.w) * is.w);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sm[r][g * 4 + j][0] = s1[j], sm[r][g * 4 + j][1] = s2[j];
-  __syncthreads();
-  if (threadIdx.x < CB * 2) {
-    const int cc = threadIdx.x >> 1, w = threadIdx.x & 1;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < RL; ++i) s += sm[i][cc][w];
-    const int ch = blockIdx.y * CB + cc;
-    if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
-  }
+  block_reduce_store<V, GPR>(s1, s2, g, r, C, part);
 }
 __global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ part, int nb, int C, float* __restrict__ sums) {
   const int c = blockIdx.x * FC + (threadIdx.x & (FC - 1)), lane = threadIdx.x / FC;
@@ -246,8 +337,7 @@ __global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ pa
 }
 
 // Chan et al. merge of per-rank (mean | M2 | count) rows gathered over the process group: [W][3C] -> [3C], in double.
-// FIN: mean / invstd and the running-moment update of bn_finalize_kernel in the same launch, on the float values the two-kernel path
-// would hand over through `out` (bit-identical), so that SyncBatchNorm costs one launch less per layer.
+// FIN: SyncBatchNorm costs one launch less per layer (bn_finish).
 template <bool FIN>
 __global__ void bn_merge_kernel(const float* __restrict__ parts, int W, int C, float* __restrict__ out, float eps, float* __restrict__ mean,
                                 float* __restrict__ invstd, float* running_mean, float* running_var, float momentum) {
@@ -264,16 +354,7 @@ __global__ void bn_merge_kernel(const float* __restrict__ parts, int W, int C, f
     const double cnt = parts[(long)r * 3 * C + 2 * C + c], d = (double)parts[(long)r * 3 * C + c] - gmean;
     m2d += (double)parts[(long)r * 3 * C + C + c] + cnt * d * d;
   }
-  const float m = (float)gmean, m2 = (float)m2d, nf = (float)n;
-  if constexpr (!FIN) {
-    out[c] = m, out[C + c] = m2, out[2 * C + c] = nf;
-  } else {
-    const float var = m2 / nf;
-    mean[c] = m;
-    invstd[c] = 1.f / sqrtf(var + eps);
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    if (running_var && nf > 1.f) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2 / (nf - 1.f));   // n == 1: no unbiased estimate (0 / 0)
-  }
+  bn_finish<FIN>(c, C, (float)gmean, (float)m2d, (float)n, out, eps, mean, invstd, running_mean, running_var, momentum);
 }
 
 // every BatchNorm of a network folded in one launch (eval-mode forward): table[i] = {gamma, beta, running_mean, running_var} device
@@ -300,52 +381,312 @@ __global__ void bn_fold_kernel(const float* __restrict__ g, const float* __restr
   shift[c] = b[c] - rm[c] * s + (cb ? cb[c] * s : 0.f);
 }
 
-int check_bn(const pm_tensor* x, const char* who) {
-  PM_REQUIRE_F32(x, who);      // the bf16 forms are dispatched before this check (act16.hip); a mixed-type call ends here
-  PM_REQUIRE(x && x->ptr && pm_vec4(x), PM_EINVAL, "%s: tensor must be 16B aligned, pitch %% 4 == 0 and C %% 4 == 0", who);
+// ---- the bf16 elementwise passes with the per-channel constants in REGISTERS --------------------------------------------------------------
+// thread = one 8-channel group (fixed) x a strided set of pixels. The generic driver re-loads mean / invstd / gamma / beta (/ sums) -- 128-192 bytes of L1
+// traffic -- for every 16-byte group of activations it moves, which held these passes at 4.0-4.4 TB/s where their fp32 twins reach 5.6 (twice the tensor bytes
+// per parameter load). Taken when the channel groups divide the block (C = 64 ... 2048).
+constexpr int V8 = 8;
+template <bool RES, bool MASK, bool RELU>
+__global__ __launch_bounds__(256) void bn16_apply_fixed_kernel(const pm_bf16* __restrict__ x, long xp, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, const pm_bf16* __restrict__ res, long rp,
+                                                               pm_bf16* __restrict__ y, long yp, uint8_t* __restrict__ mask, long pixels, int cg) {
+  const int grp = threadIdx.x % cg, pl = threadIdx.x / cg, ppb = 256 / cg, ch = grp * V8;
+  float sc[V8], sh[V8];
+  {
+    float mu[V8], is[V8], ga[V8], be[V8];
+    pm_ld8f(mean + ch, mu), pm_ld8f(invstd + ch, is), pm_ld8f(gamma + ch, ga), pm_ld8f(beta + ch, be);
+#pragma unroll
+    for (int e = 0; e < V8; ++e) sc[e] = is[e] * ga[e], sh[e] = fmaf(-mu[e], sc[e], be[e]);      // pm_bn_affine(v) == fmaf(v, sc, sh): the same two FMAs
+  }
+  for (long p = (long)blockIdx.x * ppb + pl; p < pixels; p += (long)gridDim.x * ppb) {
+    float v[V8], o[V8];
+    pm_ld8(x + p * xp + ch, v);
+#pragma unroll
+    for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], sc[e], sh[e]);
+    if constexpr (RES) {
+      float q[V8];
+      pm_ld8(res + p * rp + ch, q);
+#pragma unroll
+      for (int e = 0; e < V8; ++e) o[e] += q[e];
+    }
+    if constexpr (MASK) mask[p * cg + grp] = (unsigned char)positive_bits<V8>(o);
+    if constexpr (RELU) relu<V8>(o);
+    pm_st8(y + p * yp + ch, o);
+  }
+}
+
+// MODE 0: no ReLU (dy is already the masked gradient); 1: mask = forward output > 0; 2: mask rebuilt from x
+template <int MODE, bool DRES>
+__global__ __launch_bounds__(256) void bn16_bwd_apply_fixed_kernel(const pm_bf16* __restrict__ dy, long dp, const pm_bf16* __restrict__ yo, long op, const pm_bf16* __restrict__ x,
+                                                                   long xp, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, const float* __restrict__ sums, float host_inv_n, int dev_count, int C,
+                                                                   pm_bf16* __restrict__ dx, long dxp, pm_bf16* __restrict__ dres, long drp, long pixels, int cg) {
+  const int grp = threadIdx.x % cg, pl = threadIdx.x / cg, ppb = 256 / cg, ch = grp * V8;
+  float mu[V8], is[V8], k1[V8], k2[V8], sg[V8], sc[V8], sh[V8];
+  {
+    const float inv_n = bn_inv_n(dev_count, sums, C, host_inv_n);
+    float ga[V8], s1[V8], s2[V8];
+    pm_ld8f(mean + ch, mu), pm_ld8f(invstd + ch, is), pm_ld8f(gamma + ch, ga), pm_ld8f(sums + ch, s1), pm_ld8f(sums + C + ch, s2);
+#pragma unroll
+    for (int e = 0; e < V8; ++e) k1[e] = s1[e] * inv_n, k2[e] = s2[e] * inv_n, sg[e] = is[e] * ga[e];
+    if constexpr (MODE == 2) {
+      float be[V8];
+      pm_ld8f(beta + ch, be);
+#pragma unroll
+      for (int e = 0; e < V8; ++e) sc[e] = sg[e], sh[e] = fmaf(-mu[e], sg[e], be[e]);
+    }
+  }
+  for (long p = (long)blockIdx.x * ppb + pl; p < pixels; p += (long)gridDim.x * ppb) {
+    float g[V8], v[V8], o[V8], r[V8];
+    pm_ld8(dy + p * dp + ch, g);
+    pm_ld8(x + p * xp + ch, v);
+    if constexpr (MODE == 1) {
+      pm_ld8(yo + p * op + ch, o);
+      relu_mask<V8>(o, g);
+    }
+    if constexpr (MODE == 2) {
+#pragma unroll
+      for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], sc[e], sh[e]);
+      relu_mask<V8>(o, g);
+    }
+    if constexpr (DRES) pm_st8(dres + p * drp + ch, g);
+#pragma unroll
+    for (int e = 0; e < V8; ++e) r[e] = BN_DX(g[e], v[e], mu[e], is[e], k1[e], k2[e], sg[e]);      // the generic kernel's expression, constants hoisted
+    pm_st8(dx + p * dxp + ch, r);
+  }
+}
+inline bool fixed_ok(int c) { const int cg = c / V8; return c % V8 == 0 && cg >= 1 && cg <= 256 && 256 % cg == 0; }
+inline int fixed_grid(long pixels, int c) { const int ppb = 256 / (c / V8); return (int)std::min<long>((pixels + ppb - 1) / ppb, 256 * 16); }
+
+// ---- host side: one function per pass, both element types ------------------------------------------------------------------------------------
+#define BN_BY_DTYPE(x, f, ...) (pm_is_bf16(x) ? f<pm_bf16>(__VA_ARGS__) : f<float>(__VA_ARGS__))
+
+// moments != NULL: mean | M2 | count; else finalise
+template <typename T>
+int bn_stats(const char* who, const pm_tensor* x, float* moments, float eps, float* mean, float* invstd, float* running_mean, float* running_var, float momentum,
+             void* ws, size_t ws_bytes, hipStream_t st) {
+  if (int e = Elem<T>::check(x, who)) return e;
+  PM_REQUIRE(ws && ws_bytes >= bn_workspace<T>(x), PM_EWORKSPACE, "%s: workspace too small", who);
+  const long P = pm_pixels(x);
+  const int C = x->c;
+  PM_REQUIRE(P > 0, PM_EINVAL, "%s: empty tensor", who);
+  // torch.nn.BatchNorm2d in training mode: "Expected more than 1 value per channel when training" (B = 1 through ASPP's image-pooling branch)
+  PM_REQUIRE(moments || P > 1, PM_EINVAL, "%s: expected more than 1 value per channel when training, got %ld", who, P);
+  const Plan pl = bn_plan<T>(P, C);
+  const T* px = (const T*)x->ptr;
+  with_gpr<T>(pl.gpr, [&](auto G) {
+    hipLaunchKernelGGL((bn_stats_partial<T, decltype(G)::value>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, px, (long)x->pitch, P, C, pl.rows, (float*)ws);
+  });
+  if (moments)
+    hipLaunchKernelGGL((bn_stats_final<T, false>), dim3(pm_cdiv(C, FC)), dim3(256), 0, st, (const float*)ws, pl.nb, px, P, C, moments, 0.f, (float*)nullptr,
+                       (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f);
+  else
+    hipLaunchKernelGGL((bn_stats_final<T, true>), dim3(pm_cdiv(C, FC)), dim3(256), 0, st, (const float*)ws, pl.nb, px, P, C, (float*)nullptr, eps, mean, invstd,
+                       running_mean, running_var, momentum);
+  return pm_check_launch(who);
+}
+
+// RAFF: the residual is itself a BatchNorm output that was never stored -- bn_affine(r, ...) of the raw tensor r with its own (mean, invstd, gamma, beta),
+// the two FMAs pm_bn_apply would have evaluated before storing it (an fp32 store and reload is lossless: same bits), added exactly where a stored residual is.
+// mask: one byte per 16-byte channel group.
+template <typename T, bool RAFF = false>
+int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res, const float* rmean,
+             const float* rinvstd, const float* rgamma, const float* rbeta, int relu_on, const pm_tensor* y, uint8_t* mask, hipStream_t st) {
+  constexpr int V = Elem<T>::V;
+  if (int e = Elem<T>::check(x, who)) return e;
+  if (int e = Elem<T>::check(y, who)) return e;
+  PM_REQUIRE(pm_same_shape(x, y) && mean && invstd && gamma && beta, PM_EINVAL, "%s: bad args", who);
+  if (res) {
+    if (int e = Elem<T>::check(res, who)) return e;
+    PM_REQUIRE(pm_same_shape(x, res), PM_EINVAL, "%s: residual shape mismatch", who);
+  }
+  PM_REQUIRE(!RAFF || (res && rmean && rinvstd && rgamma && rbeta), PM_EINVAL, "%s: bad args", who);
+  const T *px = (const T*)x->ptr, *pr = res ? (const T*)res->ptr : nullptr;
+  T* py = (T*)y->ptr;
+  const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, P = pm_pixels(x);
+  const int cg = x->c / V;
+  if constexpr (V == V8) {
+    if (fixed_ok(x->c) && P > 0) {
+      const dim3 grid(fixed_grid(P, x->c));
+#define BN16_APPLY(R, M, L) hipLaunchKernelGGL((bn16_apply_fixed_kernel<R, M, L>), grid, dim3(256), 0, st, px, a, mean, invstd, gamma, beta, pr, b, py, c, mask, P, cg)
+      if (pr && mask && relu_on) BN16_APPLY(true, true, true);
+      else if (pr && relu_on) BN16_APPLY(true, false, true);
+      else if (pr && mask) BN16_APPLY(true, true, false);
+      else if (pr) BN16_APPLY(true, false, false);
+      else if (mask && relu_on) BN16_APPLY(false, true, true);
+      else if (relu_on) BN16_APPLY(false, false, true);
+      else if (mask) BN16_APPLY(false, true, false);
+      else BN16_APPLY(false, false, false);
+#undef BN16_APPLY
+      return pm_check_launch(who);
+    }
+  }
+  return ew_launch<T>(P, x->c, st, who, [=] __device__(long p, int ch) {
+    float v[V], mu[V], is[V], ga[V], be[V], o[V];
+    Elem<T>::ld(px + p * a + ch, v);
+    ldp<V>(mean + ch, mu), ldp<V>(invstd + ch, is), ldp<V>(gamma + ch, ga), ldp<V>(beta + ch, be);
+    bn_affine<V>(v, mu, is, ga, be, o);
+    if (pr) {
+      float q[V];
+      Elem<T>::ld(pr + p * b + ch, q);
+      if constexpr (RAFF) {
+        float rm[V], ri[V], rg[V], rb[V];
+        ldp<V>(rmean + ch, rm), ldp<V>(rinvstd + ch, ri), ldp<V>(rgamma + ch, rg), ldp<V>(rbeta + ch, rb);
+        bn_affine<V>(q, rm, ri, rg, rb, q);
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] += q[j];
+    }
+    if (mask) mask[p * cg + ch / V] = (unsigned char)positive_bits<V>(o);
+    if (relu_on) relu<V>(o);
+    Elem<T>::st(py + p * c + ch, o);
+  });
+}
+
+// dy: the incoming gradient (its own checks are the caller's). relu 0 ... 3 as bn_bwd_partial; the pooled gradient always takes mode 2 without gmask.
+template <typename T, typename SRC>
+int bn_bwd_reduce(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                  const float* beta, int relu_mode, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (int e = Elem<T>::check(x, who)) return e;
+  PM_REQUIRE(mean && invstd && sums, PM_EINVAL, "%s: bad args", who);
+  PM_REQUIRE(relu_mode >= 0 && relu_mode <= 3, PM_EINVAL, "%s: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x, 3 mask bytes)", who, relu_mode);
+  PM_REQUIRE(relu_mode != 1 || (y && Elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
+  PM_REQUIRE(relu_mode != 2 || (gamma && beta), PM_EINVAL, "%s: relu mode 2 needs gamma and beta", who);
+  PM_REQUIRE(relu_mode != 3 || mask, PM_EINVAL, "%s: relu mode 3 needs the mask bytes", who);
+  PM_REQUIRE(!gmask || (relu_mode != 0 && Elem<T>::check(gmask, who) == PM_OK && pm_same_shape(gmask, x)), PM_EINVAL, "%s: gmask needs a ReLU mode and the shape of x", who);
+  PM_REQUIRE(ws && ws_bytes >= bn_workspace<T>(x), PM_EWORKSPACE, "%s: workspace too small", who);
+  const long P = pm_pixels(x);
+  const int C = x->c;
+  const Plan pl = bn_plan<T>(P, C);
+  const T *py = relu_mode == 1 ? (const T*)y->ptr : nullptr, *px = (const T*)x->ptr;
+  const long yp = relu_mode == 1 ? y->pitch : 0, gp = gmask ? gmask->pitch : 0;
+  T* pg = gmask ? (T*)gmask->ptr : nullptr;
+  with_gpr<T>(pl.gpr, [&](auto G) {
+    auto go = [&](auto R, auto O) {
+      hipLaunchKernelGGL((bn_bwd_partial<T, decltype(G)::value, decltype(R)::value, decltype(O)::value, SRC>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, dy, py, yp, mask, px, (long)x->pitch, mean, invstd, gamma,
+                         beta, pg, gp, P, C, pl.rows, (float*)ws);
+    };
+    using std::false_type;
+    using std::true_type;
+    if constexpr (std::is_same<SRC, PoolGrad>::value) go(std::integral_constant<int, 2>{}, false_type{});
+    else if (relu_mode == 0) go(std::integral_constant<int, 0>{}, false_type{});
+    else if (relu_mode == 1 && gmask) go(std::integral_constant<int, 1>{}, true_type{});
+    else if (relu_mode == 1) go(std::integral_constant<int, 1>{}, false_type{});
+    else if (relu_mode == 2 && gmask) go(std::integral_constant<int, 2>{}, true_type{});
+    else if (relu_mode == 2) go(std::integral_constant<int, 2>{}, false_type{});
+    else if (gmask) go(std::integral_constant<int, 3>{}, true_type{});
+    else go(std::integral_constant<int, 3>{}, false_type{});
+  });
+  hipLaunchKernelGGL(bn_bwd_final, dim3(pm_cdiv(C, FC)), dim3(256), 0, st, (const float*)ws, pl.nb, C, sums);
+  return pm_check_launch(who);
+}
+
+// MODE < 0: the ReLU mode (0, 1, 2) is the run-time `relu_mode`; MODE 2 / 3: fixed at compile time (the pooled gradient / the mask bytes), no other branch is compiled.
+template <typename T, int MODE, typename SRC>
+int bn_bwd_apply(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                 const float* beta, const float* sums, float count, int relu_mode, const pm_tensor* dx, const pm_tensor* dres, hipStream_t st) {
+  constexpr int V = Elem<T>::V;
+  if (int e = Elem<T>::check(x, who)) return e;
+  if (int e = Elem<T>::check(dx, who)) return e;
+  PM_REQUIRE(pm_same_shape(dx, x) && mean && invstd && gamma && sums, PM_EINVAL, "%s: bad args", who);
+  PM_REQUIRE(pm_aligned16(sums), PM_EINVAL, "%s: sums must be 16-byte aligned (sections of a shared exchange start at multiples of 4 floats)", who);
+  if (MODE >= 0) relu_mode = MODE;
+  PM_REQUIRE(MODE >= 0 || (relu_mode >= 0 && relu_mode <= 2), PM_EINVAL, "%s: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x)", who, relu_mode);
+  PM_REQUIRE(relu_mode != 1 || (y && Elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
+  PM_REQUIRE(relu_mode != 2 || beta, PM_EINVAL, "%s: relu mode 2 needs beta", who);
+  PM_REQUIRE(relu_mode != 3 || mask, PM_EINVAL, "%s: relu mode 3 needs the mask bytes", who);
+  PM_REQUIRE(!dres || (Elem<T>::check(dres, who) == PM_OK && pm_same_shape(dres, x)), PM_EINVAL, "%s: dres shape mismatch", who);
+  const T *po = relu_mode == 1 ? (const T*)y->ptr : nullptr, *px = (const T*)x->ptr;
+  T *pdx = (T*)dx->ptr, *pdr = dres ? (T*)dres->ptr : nullptr;
+  const long b = relu_mode == 1 ? y->pitch : 0, c = x->pitch, d = dx->pitch, e2 = dres ? dres->pitch : 0, P = pm_pixels(x);
+  const int C = x->c, cg = C / V;
+  const bool dev_count = !(count > 0.f), from_x = relu_mode == 2;
+  const float host_inv_n = dev_count ? 0.f : 1.f / count;
+  if constexpr (V == V8 && MODE < 0) {
+    if (fixed_ok(C) && P > 0) {
+      const dim3 grid(fixed_grid(P, C));
+#define BN16_BAPPLY(M, D)                                                                                                                                             \
+  hipLaunchKernelGGL((bn16_bwd_apply_fixed_kernel<M, D>), grid, dim3(256), 0, st, dy.dy, dy.pitch, po, b, px, c, mean, invstd, gamma, beta, sums, host_inv_n, dev_count ? 1 : 0, \
+                     C, pdx, d, pdr, e2, P, cg)
+      if (relu_mode == 0) { if (pdr) BN16_BAPPLY(0, true); else BN16_BAPPLY(0, false); }
+      else if (relu_mode == 1) { if (pdr) BN16_BAPPLY(1, true); else BN16_BAPPLY(1, false); }
+      else { if (pdr) BN16_BAPPLY(2, true); else BN16_BAPPLY(2, false); }
+#undef BN16_BAPPLY
+      return pm_check_launch(who);
+    }
+  }
+  return ew_launch<T>(P, C, st, who, [=] __device__(long p, int ch) {
+    const float inv_n = bn_inv_n(dev_count, sums, C, host_inv_n);
+    float g[V], v[V], mu[V], is[V], ga[V], s1[V], s2[V], r[V];
+    dy.load(p, ch, g);
+    if (MODE < 0 && po) {
+      float o[V];
+      Elem<T>::ld(po + p * b + ch, o);
+      relu_mask<V>(o, g);
+    }
+    if constexpr (MODE == 3) relu_mask_bits<V>(mask[p * cg + ch / V], g);
+    Elem<T>::ld(px + p * c + ch, v);
+    ldp<V>(mean + ch, mu), ldp<V>(invstd + ch, is), ldp<V>(gamma + ch, ga);
+    if (MODE == 2 || (MODE < 0 && from_x)) {
+      float be[V], o[V];
+      ldp<V>(beta + ch, be);
+      bn_affine<V>(v, mu, is, ga, be, o);
+      relu_mask<V>(o, g);
+    }
+    if (MODE < 0 && pdr) Elem<T>::st(pdr + p * e2 + ch, g);
+    ldp<V>(sums + ch, s1), ldp<V>(sums + C + ch, s2);
+#pragma unroll
+    for (int j = 0; j < V; ++j) r[j] = BN_DX(g[j], v[j], mu[j], is[j], s1[j] * inv_n, s2[j] * inv_n, is[j] * ga[j]);
+    Elem<T>::st(pdx + p * d + ch, r);
+  });
+}
+
+// the incoming gradient as a tensor of x's type and shape
+template <typename T>
+int tensor_grad(const char* who, const pm_tensor* dy, const pm_tensor* x, TensorGrad<T>* g) {
+  if (int e = Elem<T>::check(dy, who)) return e;
+  PM_REQUIRE(pm_same_shape(dy, x), PM_EINVAL, "%s: dy must have the shape of x", who);
+  g->dy = (const T*)dy->ptr, g->pitch = dy->pitch;
+  return PM_OK;
+}
+template <typename T>
+int bn_bwd_reduce_tensor(const char* who, const pm_tensor* dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, int relu_mode, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, hipStream_t st) {
+  TensorGrad<T> g;
+  if (int e = tensor_grad<T>(who, dy, x, &g)) return e;
+  return bn_bwd_reduce<T>(who, g, y, mask, x, mean, invstd, gamma, beta, relu_mode, gmask, sums, ws, ws_bytes, st);
+}
+template <typename T>
+int bn_bwd_apply_tensor(const char* who, const pm_tensor* dy, const pm_tensor* y, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
+                        const float* beta, const float* sums, float count, int relu_mode, const pm_tensor* dx, const pm_tensor* dres, hipStream_t st) {
+  TensorGrad<T> g;
+  if (int e = tensor_grad<T>(who, dy, x, &g)) return e;
+  return bn_bwd_apply<T, -1>(who, g, y, nullptr, x, mean, invstd, gamma, beta, sums, count, relu_mode, dx, dres, st);
+}
+// the stem: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x (fp32)
+int pool_grad(const char* who, const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, PoolGrad* g) {
+  PM_REQUIRE(dyp && argmax && x, PM_EINVAL, "%s: null", who);
+  if (int e = Elem<float>::check(dyp, who)) return e;
+  if (int e = Elem<float>::check(x, who)) return e;
+  PM_REQUIRE(dyp->n == x->n && dyp->c == x->c && dyp->h == (x->h + 2 - 3) / 2 + 1 && dyp->w == (x->w + 2 - 3) / 2 + 1, PM_EINVAL,
+             "%s: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x", who);
+  *g = PoolGrad{(const float*)dyp->ptr, (long)dyp->pitch, dyp->h, dyp->w, argmax, x->h, x->w, x->c};
   return PM_OK;
 }
 
 }  // namespace
 
-extern "C" size_t pm_bn_workspace(const pm_tensor* x) {
-  if (pm_is_bf16(x)) return pm16_bn_workspace(x);
-  const long P = pm_pixels(x);
-  const int nb = pm_cdiv(P, chunk_rows(P, x->c));
-  return pm_align_up((size_t)nb * x->c * 2 * sizeof(float), 256);
-}
+extern "C" size_t pm_bn_workspace(const pm_tensor* x) { return BN_BY_DTYPE(x, bn_workspace, x); }
 
 extern "C" int pm_bn_stats(const pm_tensor* x, float* moments, void* ws, size_t ws_bytes, void* stream) {
   PM_REQUIRE(x && moments, PM_EINVAL, "bn_stats: null");
-  if (pm_is_bf16(x)) return pm16_bn_stats(x, moments, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f, ws, ws_bytes, (hipStream_t)stream);
-  if (int e = check_bn(x, "bn_stats")) return e;
-  PM_REQUIRE(moments && ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_stats: workspace too small");
-  const long P = pm_pixels(x);
-  PM_REQUIRE(P > 0, PM_EINVAL, "bn_stats: empty tensor");
-  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_stats_partial, dim3(nb, pm_cdiv(x->c, CB)), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, P, x->c, rows, (float*)ws);
-  hipLaunchKernelGGL(bn_stats_final<false>, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, (const float*)x->ptr, P, x->c, moments, 0.f,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f);
-  return pm_check_launch("bn_stats");
+  return BN_BY_DTYPE(x, bn_stats, "bn_stats", x, moments, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_stats_finalize(const pm_tensor* x, float eps, float* mean, float* invstd, float* running_mean, float* running_var, float momentum,
                                     void* ws, size_t ws_bytes, void* stream) {
   PM_REQUIRE(x && mean && invstd, PM_EINVAL, "bn_stats_finalize: bad args");
-  if (pm_is_bf16(x)) return pm16_bn_stats(x, nullptr, eps, mean, invstd, running_mean, running_var, momentum, ws, ws_bytes, (hipStream_t)stream);
-  if (int e = check_bn(x, "bn_stats_finalize")) return e;
-  PM_REQUIRE(ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_stats_finalize: workspace too small");
-  const long P = pm_pixels(x);
-  PM_REQUIRE(P > 0, PM_EINVAL, "bn_stats_finalize: empty tensor");
-  // torch.nn.BatchNorm2d in training mode: "Expected more than 1 value per channel when training" (B = 1 through ASPP's image-pooling branch)
-  PM_REQUIRE(P > 1, PM_EINVAL, "bn_stats_finalize: expected more than 1 value per channel when training, got %ld", P);
-  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_stats_partial, dim3(nb, pm_cdiv(x->c, CB)), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, P, x->c, rows, (float*)ws);
-  hipLaunchKernelGGL(bn_stats_final<true>, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, (const float*)x->ptr, P, x->c, (float*)nullptr, eps,
-                     mean, invstd, running_mean, running_var, momentum);
-  return pm_check_launch("bn_stats_finalize");
+  return BN_BY_DTYPE(x, bn_stats, "bn_stats_finalize", x, nullptr, eps, mean, invstd, running_mean, running_var, momentum, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_finalize(const float* moments, int c, float eps, float* mean, float* invstd, float* running_mean, float* running_var,
@@ -404,96 +745,25 @@ extern "C" int pm_bn_apply(const pm_tensor* x, const float* mean, const float* i
   return pm_bn_apply_mask(x, mean, invstd, gamma, beta, res, relu, y, nullptr, stream);
 }
 
-namespace {
-
-// RAFF: the residual is itself a BatchNorm output that was never stored -- bn_affine(r, ...) of the raw tensor r with its own (mean, invstd, gamma, beta),
-// the two FMAs pm_bn_apply would have evaluated before storing it (an fp32 store and reload is lossless: same bits), added exactly where a stored residual is.
-template <bool RAFF>
-int bn_apply_launch(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res, const float* rmean,
-                    const float* rinvstd, const float* rgamma, const float* rbeta, int relu, const pm_tensor* y, uint8_t* mask, hipStream_t stream) {
-  const float *px = (const float*)x->ptr, *pr = res ? (const float*)res->ptr : nullptr;
-  float* py = (float*)y->ptr;
-  const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, cq = x->c >> 2;
-  return pm_ew_launch(true, pm_pixels(x), x->c, stream, "bn_apply", [=] __device__(long p, int ch) {
-    const float4 v = PM_LD4(px + p * a + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
-    float4 o = make_float4(bn_affine(v.x, mu.x, is.x, ga.x, be.x), bn_affine(v.y, mu.y, is.y, ga.y, be.y), bn_affine(v.z, mu.z, is.z, ga.z, be.z),
-                           bn_affine(v.w, mu.w, is.w, ga.w, be.w));
-    if (pr) {
-      float4 q = PM_LD4(pr + p * b + ch);
-      if constexpr (RAFF) {
-        const float4 rm = PM_LD4(rmean + ch), ri = PM_LD4(rinvstd + ch), rg = PM_LD4(rgamma + ch), rb = PM_LD4(rbeta + ch);
-        q = make_float4(bn_affine(q.x, rm.x, ri.x, rg.x, rb.x), bn_affine(q.y, rm.y, ri.y, rg.y, rb.y), bn_affine(q.z, rm.z, ri.z, rg.z, rb.z),
-                        bn_affine(q.w, rm.w, ri.w, rg.w, rb.w));
-      }
-      o.x += q.x, o.y += q.y, o.z += q.z, o.w += q.w;
-    }
-    if (mask) mask[p * cq + (ch >> 2)] = (unsigned char)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
-    if (relu) o.x = fmaxf(o.x, 0.f), o.y = fmaxf(o.y, 0.f), o.z = fmaxf(o.z, 0.f), o.w = fmaxf(o.w, 0.f);
-    PM_ST4(py + p * c + ch, o);
-  });
-}
-
-}  // namespace
-
 extern "C" int pm_bn_apply_mask(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res,
                                 int relu, const pm_tensor* y, uint8_t* mask, void* stream) {
   PM_REQUIRE(x && y, PM_EINVAL, "bn_apply: null");
-  if (pm_is_bf16(x)) return pm16_bn_apply_mask(x, mean, invstd, gamma, beta, res, relu, y, mask, (hipStream_t)stream);      // all tensors bf16; mask: one byte per 8 channels
-  if (int e = check_bn(x, "bn_apply")) return e;
-  if (int e = check_bn(y, "bn_apply")) return e;
-  PM_REQUIRE(pm_same_shape(x, y) && mean && invstd && gamma && beta, PM_EINVAL, "bn_apply: bad args");
-  if (res) {
-    if (int e = check_bn(res, "bn_apply")) return e;
-    PM_REQUIRE(pm_same_shape(x, res), PM_EINVAL, "bn_apply: residual shape mismatch");
-  }
-  return bn_apply_launch<false>(x, mean, invstd, gamma, beta, res, nullptr, nullptr, nullptr, nullptr, relu, y, mask, (hipStream_t)stream);
+  return BN_BY_DTYPE(x, bn_apply, "bn_apply", x, mean, invstd, gamma, beta, res, nullptr, nullptr, nullptr, nullptr, relu, y, mask, (hipStream_t)stream);
 }
 
 // pm_bn_apply_mask whose residual is bn(r) of a second raw tensor (the downsample branch of a stage's first Bottleneck): the normalised residual is never stored.
 extern "C" int pm_bn_apply_mask_affine(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* r,
                                        const float* r_mean, const float* r_invstd, const float* r_gamma, const float* r_beta, int relu, const pm_tensor* y,
                                        uint8_t* mask, void* stream) {
-  PM_REQUIRE(x && y && r, PM_EINVAL, "bn_apply_mask_affine: null");
-  if (int e = check_bn(x, "bn_apply_mask_affine")) return e;      // fp32 only: the bf16 tier stores its normalised residual
-  if (int e = check_bn(y, "bn_apply_mask_affine")) return e;
-  if (int e = check_bn(r, "bn_apply_mask_affine")) return e;
-  PM_REQUIRE(pm_same_shape(x, y) && pm_same_shape(x, r) && mean && invstd && gamma && beta && r_mean && r_invstd && r_gamma && r_beta, PM_EINVAL,
-             "bn_apply_mask_affine: bad args");
-  return bn_apply_launch<true>(x, mean, invstd, gamma, beta, r, r_mean, r_invstd, r_gamma, r_beta, relu, y, mask, (hipStream_t)stream);
+  PM_REQUIRE(x && y && r, PM_EINVAL, "bn_apply_mask_affine: null");      // fp32 only: the bf16 tier stores its normalised residual
+  return bn_apply<float, true>("bn_apply_mask_affine", x, mean, invstd, gamma, beta, r, r_mean, r_invstd, r_gamma, r_beta, relu, y, mask, (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_bwd_reduce(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                                 const float* beta, int relu, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, void* stream) {
   PM_REQUIRE(dy && x, PM_EINVAL, "bn_bwd_reduce: null");
   PM_REQUIRE(relu >= 0 && relu <= 2, PM_EINVAL, "bn_bwd_reduce: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x)", relu);
-  if (pm_is_bf16(x)) return pm16_bn_bwd_reduce(dy, y, nullptr, x, mean, invstd, gamma, beta, relu, gmask, sums, ws, ws_bytes, (hipStream_t)stream);
-  if (int e = check_bn(dy, "bn_bwd_reduce")) return e;
-  if (int e = check_bn(x, "bn_bwd_reduce")) return e;
-  PM_REQUIRE(pm_same_shape(dy, x) && mean && invstd && sums, PM_EINVAL, "bn_bwd_reduce: bad args");
-  PM_REQUIRE(relu >= 0 && relu <= 2, PM_EINVAL, "bn_bwd_reduce: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x)", relu);
-  PM_REQUIRE(relu != 1 || (y && pm_vec4(y) && pm_same_shape(y, x)), PM_EINVAL, "bn_bwd_reduce: relu mode 1 needs the forward output");
-  PM_REQUIRE(relu != 2 || (gamma && beta), PM_EINVAL, "bn_bwd_reduce: relu mode 2 needs gamma and beta");
-  PM_REQUIRE(!gmask || (relu != 0 && pm_vec4(gmask) && pm_same_shape(gmask, x)), PM_EINVAL, "bn_bwd_reduce: gmask needs a ReLU mode and the shape of x");
-  PM_REQUIRE(ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_bwd_reduce: workspace too small");
-  const long P = pm_pixels(x);
-  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(nb, pm_cdiv(x->c, CB));
-  const float *pdy = (const float*)dy->ptr, *py = relu == 1 ? (const float*)y->ptr : nullptr, *px = (const float*)x->ptr;
-  const long yp = relu == 1 ? y->pitch : 0;
-  float* pg = gmask ? (float*)gmask->ptr : nullptr;
-  const long gp = gmask ? gmask->pitch : 0;
-#define PM_BN_BWD_PARTIAL(R, G)                                                                                                                         \
-  hipLaunchKernelGGL((bn_bwd_partial<R, G>), grid, dim3(256), 0, st, pdy, (long)dy->pitch, py, yp, px, (long)x->pitch, mean, invstd, gamma, beta, pg, gp, P, \
-                     x->c, rows, (float*)ws)
-  if (relu == 0) PM_BN_BWD_PARTIAL(0, false);
-  else if (relu == 1 && gmask) PM_BN_BWD_PARTIAL(1, true);
-  else if (relu == 1) PM_BN_BWD_PARTIAL(1, false);
-  else if (gmask) PM_BN_BWD_PARTIAL(2, true);
-  else PM_BN_BWD_PARTIAL(2, false);
-#undef PM_BN_BWD_PARTIAL
-  hipLaunchKernelGGL(bn_bwd_final, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, x->c, sums);
-  return pm_check_launch("bn_bwd_reduce");
+  return BN_BY_DTYPE(x, bn_bwd_reduce_tensor, "bn_bwd_reduce", dy, y, nullptr, x, mean, invstd, gamma, beta, relu, gmask, sums, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // BN + residual + ReLU backward reduce with the ReLU mask taken from pm_bn_apply_mask's bytes instead of the forward output: sums and the masked
@@ -501,71 +771,15 @@ extern "C" int pm_bn_bwd_reduce(const pm_tensor* dy, const pm_tensor* y, const p
 extern "C" int pm_bn_bwd_reduce_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd,
                                      const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, void* stream) {
   PM_REQUIRE(dy && x && mask, PM_EINVAL, "bn_bwd_reduce_mask: null");
-  if (pm_is_bf16(x)) return pm16_bn_bwd_reduce(dy, nullptr, mask, x, mean, invstd, nullptr, nullptr, 3, gmask, sums, ws, ws_bytes, (hipStream_t)stream);
-  if (int e = check_bn(dy, "bn_bwd_reduce_mask")) return e;
-  if (int e = check_bn(x, "bn_bwd_reduce_mask")) return e;
-  PM_REQUIRE(pm_same_shape(dy, x) && mean && invstd && sums && mask, PM_EINVAL, "bn_bwd_reduce_mask: bad args");
-  PM_REQUIRE(!gmask || (pm_vec4(gmask) && pm_same_shape(gmask, x)), PM_EINVAL, "bn_bwd_reduce_mask: gmask must have the shape of x");
-  PM_REQUIRE(ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_bwd_reduce_mask: workspace too small");
-  const long P = pm_pixels(x);
-  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(nb, pm_cdiv(x->c, CB));
-  float* pg = gmask ? (float*)gmask->ptr : nullptr;
-  const long gp = gmask ? gmask->pitch : 0;
-  if (gmask)
-    hipLaunchKernelGGL((bn_bwd_partial<3, true>), grid, dim3(256), 0, st, (const float*)dy->ptr, (long)dy->pitch, reinterpret_cast<const float*>(mask), 0l,
-                       (const float*)x->ptr, (long)x->pitch, mean, invstd, (const float*)nullptr, (const float*)nullptr, pg, gp, P, x->c, rows, (float*)ws);
-  else
-    hipLaunchKernelGGL((bn_bwd_partial<3, false>), grid, dim3(256), 0, st, (const float*)dy->ptr, (long)dy->pitch, reinterpret_cast<const float*>(mask), 0l,
-                       (const float*)x->ptr, (long)x->pitch, mean, invstd, (const float*)nullptr, (const float*)nullptr, pg, gp, P, x->c, rows, (float*)ws);
-  hipLaunchKernelGGL(bn_bwd_final, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, x->c, sums);
-  return pm_check_launch("bn_bwd_reduce_mask");
+  return BN_BY_DTYPE(x, bn_bwd_reduce_tensor, "bn_bwd_reduce_mask", dy, nullptr, mask, x, mean, invstd, nullptr, nullptr, 3, gmask, sums, ws, ws_bytes,
+                     (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                                const float* beta, const float* sums, float count, int relu, const pm_tensor* dx, const pm_tensor* dres, void* stream) {
   PM_REQUIRE(dy && x && dx, PM_EINVAL, "bn_bwd_apply: null");
-  if (pm_is_bf16(x)) return pm16_bn_bwd_apply(dy, y, x, mean, invstd, gamma, beta, sums, count, relu, dx, dres, (hipStream_t)stream);
-  if (int e = check_bn(dy, "bn_bwd_apply")) return e;
-  if (int e = check_bn(x, "bn_bwd_apply")) return e;
-  if (int e = check_bn(dx, "bn_bwd_apply")) return e;
-  PM_REQUIRE(pm_same_shape(dy, x) && pm_same_shape(dx, x) && mean && invstd && gamma && sums, PM_EINVAL, "bn_bwd_apply: bad args");
   PM_REQUIRE(relu >= 0 && relu <= 2, PM_EINVAL, "bn_bwd_apply: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x)", relu);
-  PM_REQUIRE(relu != 1 || (y && pm_vec4(y) && pm_same_shape(y, x)), PM_EINVAL, "bn_bwd_apply: relu mode 1 needs the forward output");
-  PM_REQUIRE(relu != 2 || beta, PM_EINVAL, "bn_bwd_apply: relu mode 2 needs beta");
-  PM_REQUIRE(!dres || (pm_vec4(dres) && pm_same_shape(dres, x)), PM_EINVAL, "bn_bwd_apply: dres shape mismatch");
-  const float *pd = (const float*)dy->ptr, *po = relu == 1 ? (const float*)y->ptr : nullptr, *px = (const float*)x->ptr;
-  float *pdx = (float*)dx->ptr, *pdr = dres ? (float*)dres->ptr : nullptr;
-  const long a = dy->pitch, b = relu == 1 ? y->pitch : 0, c = x->pitch, d = dx->pitch, e2 = dres ? dres->pitch : 0;
-  const bool from_x = relu == 2;
-  const int C = x->c;
-  // count <= 0: the element count lives on the device at sums[2 * C] -- SyncBatchNorm all-reduces it with the two sums, so ranks with
-  // different batch sizes normalise by the true global count (torch.nn.SyncBatchNorm gathers the counts the same way)
-  const bool dev_count = !(count > 0.f);
-  const float host_inv_n = dev_count ? 0.f : 1.f / count;
-  return pm_ew_launch(true, pm_pixels(x), C, (hipStream_t)stream, "bn_bwd_apply", [=] __device__(long p, int ch) {
-    const float inv_n = dev_count ? 1.f / sums[2 * C] : host_inv_n;
-    float4 g = PM_LD4(pd + p * a + ch);
-    if (po) {
-      const float4 o = PM_LD4(po + p * b + ch);
-      g.x = o.x > 0.f ? g.x : 0.f, g.y = o.y > 0.f ? g.y : 0.f, g.z = o.z > 0.f ? g.z : 0.f, g.w = o.w > 0.f ? g.w : 0.f;
-    }
-    const float4 v = PM_LD4(px + p * c + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch);
-    if (from_x) {
-      const float4 be = PM_LD4(beta + ch);
-      g.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f, g.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-      g.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f, g.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-    }
-    if (pdr) PM_ST4(pdr + p * e2 + ch, g);
-    const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
-    float4 r;
-    r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);
-    r.y = (g.y - s1.y * inv_n - (v.y - mu.y) * is.y * (s2.y * inv_n)) * (is.y * ga.y);
-    r.z = (g.z - s1.z * inv_n - (v.z - mu.z) * is.z * (s2.z * inv_n)) * (is.z * ga.z);
-    r.w = (g.w - s1.w * inv_n - (v.w - mu.w) * is.w * (s2.w * inv_n)) * (is.w * ga.w);
-    PM_ST4(pdx + p * d + ch, r);
-  });
+  return BN_BY_DTYPE(x, bn_bwd_apply_tensor, "bn_bwd_apply", dy, y, x, mean, invstd, gamma, beta, sums, count, relu, dx, dres, (hipStream_t)stream);
 }
 
 // pm_bn_bwd_apply on dyz = dy masked by pm_bn_apply_mask's bytes (bit e of byte [pixel][ch / 4]: the ReLU passed element e), for ANY x of that shape: the BatchNorm the
@@ -574,84 +788,25 @@ extern "C" int pm_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y, const pm
 extern "C" int pm_bn_bwd_apply_mask(const pm_tensor* dy, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                                     const float* sums, float count, const pm_tensor* dx, void* stream) {
   PM_REQUIRE(dy && x && dx && mask, PM_EINVAL, "bn_bwd_apply_mask: null");
-  if (int e = check_bn(dy, "bn_bwd_apply_mask")) return e;
-  if (int e = check_bn(x, "bn_bwd_apply_mask")) return e;
-  if (int e = check_bn(dx, "bn_bwd_apply_mask")) return e;
-  PM_REQUIRE(pm_same_shape(dy, x) && pm_same_shape(dx, x) && mean && invstd && gamma && sums, PM_EINVAL, "bn_bwd_apply_mask: bad args");
-  const float *pd = (const float*)dy->ptr, *px = (const float*)x->ptr;
-  float* pdx = (float*)dx->ptr;
-  const long a = dy->pitch, c = x->pitch, d = dx->pitch;
-  const int C = x->c, cq = C >> 2;
-  const bool dev_count = !(count > 0.f);      // as pm_bn_bwd_apply: the global count at sums[2 * C]
-  const float host_inv_n = dev_count ? 0.f : 1.f / count;
-  return pm_ew_launch(true, pm_pixels(x), C, (hipStream_t)stream, "bn_bwd_apply_mask", [=] __device__(long p, int ch) {
-    const float inv_n = dev_count ? 1.f / sums[2 * C] : host_inv_n;
-    float4 g = PM_LD4(pd + p * a + ch);
-    const unsigned mb = mask[p * cq + (ch >> 2)];
-    g.x = (mb & 1u) ? g.x : 0.f, g.y = (mb & 2u) ? g.y : 0.f, g.z = (mb & 4u) ? g.z : 0.f, g.w = (mb & 8u) ? g.w : 0.f;
-    const float4 v = PM_LD4(px + p * c + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch);
-    const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
-    float4 r;
-    r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);
-    r.y = (g.y - s1.y * inv_n - (v.y - mu.y) * is.y * (s2.y * inv_n)) * (is.y * ga.y);
-    r.z = (g.z - s1.z * inv_n - (v.z - mu.z) * is.z * (s2.z * inv_n)) * (is.z * ga.z);
-    r.w = (g.w - s1.w * inv_n - (v.w - mu.w) * is.w * (s2.w * inv_n)) * (is.w * ga.w);
-    PM_ST4(pdx + p * d + ch, r);
-  });
+  TensorGrad<float> g;
+  if (int e = tensor_grad<float>("bn_bwd_apply_mask", dy, x, &g)) return e;
+  return bn_bwd_apply<float, 3>("bn_bwd_apply_mask", g, nullptr, mask, x, mean, invstd, gamma, nullptr, sums, count, 3, dx, nullptr, (hipStream_t)stream);
 }
 
 // ---- the stem's BN + ReLU backward behind a 3x3 / s2 max pool, straight from the pooled gradient ------------------------------------------------------------------
 // pm_bn_bwd_reduce / pm_bn_bwd_apply with relu = 2 (mask rebuilt from x) where dy is what pm_maxpool3x3s2_bwd(dyp, argmax) would have written: each pass gathers
 // it per pixel from the pooled gradient and the argmax bytes (a quarter of the pixels), so neither the full-resolution activation nor its gradient exists.
-namespace {
-int check_pool_bn(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const char* who) {
-  PM_REQUIRE(dyp && argmax && x, PM_EINVAL, "%s: null", who);
-  if (int e = check_bn(dyp, who)) return e;
-  if (int e = check_bn(x, who)) return e;
-  PM_REQUIRE(dyp->n == x->n && dyp->c == x->c && dyp->h == (x->h + 2 - 3) / 2 + 1 && dyp->w == (x->w + 2 - 3) / 2 + 1, PM_EINVAL,
-             "%s: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x", who);
-  return PM_OK;
-}
-}  // namespace
-
 extern "C" int pm_bn_bwd_reduce_pool(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                                      const float* beta, float* sums, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = check_pool_bn(dyp, argmax, x, "bn_bwd_reduce_pool")) return e;
-  PM_REQUIRE(mean && invstd && gamma && beta && sums, PM_EINVAL, "bn_bwd_reduce_pool: bad args");
-  PM_REQUIRE(ws && ws_bytes >= pm_bn_workspace(x), PM_EWORKSPACE, "bn_bwd_reduce_pool: workspace too small");
-  const long P = pm_pixels(x);
-  const int rows = chunk_rows(P, x->c), nb = pm_cdiv(P, rows);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_bwd_partial_pool, dim3(nb, pm_cdiv(x->c, CB)), dim3(256), 0, st, (const float*)dyp->ptr, (long)dyp->pitch, dyp->h, dyp->w, argmax, x->h, x->w,
-                     (const float*)x->ptr, (long)x->pitch, mean, invstd, gamma, beta, P, x->c, rows, (float*)ws);
-  hipLaunchKernelGGL(bn_bwd_final, dim3(pm_cdiv(x->c, FC)), dim3(256), 0, st, (const float*)ws, nb, x->c, sums);
-  return pm_check_launch("bn_bwd_reduce_pool");
+  PoolGrad g;
+  if (int e = pool_grad("bn_bwd_reduce_pool", dyp, argmax, x, &g)) return e;
+  return bn_bwd_reduce<float>("bn_bwd_reduce_pool", g, nullptr, nullptr, x, mean, invstd, gamma, beta, 2, nullptr, sums, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pm_bn_bwd_apply_pool(const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                                     const float* beta, const float* sums, float count, const pm_tensor* dx, void* stream) {
-  if (int e = check_pool_bn(dyp, argmax, x, "bn_bwd_apply_pool")) return e;
+  PoolGrad g;
+  if (int e = pool_grad("bn_bwd_apply_pool", dyp, argmax, x, &g)) return e;
   PM_REQUIRE(dx, PM_EINVAL, "bn_bwd_apply_pool: null");
-  if (int e = check_bn(dx, "bn_bwd_apply_pool")) return e;
-  PM_REQUIRE(pm_same_shape(dx, x) && mean && invstd && gamma && beta && sums, PM_EINVAL, "bn_bwd_apply_pool: bad args");
-  const float *pd = (const float*)dyp->ptr, *px = (const float*)x->ptr;
-  float* pdx = (float*)dx->ptr;
-  const long a = dyp->pitch, c = x->pitch, d = dx->pitch;
-  const int C = x->c, H = x->h, W = x->w, Ho = dyp->h, Wo = dyp->w;
-  const bool dev_count = !(count > 0.f);      // as pm_bn_bwd_apply: the global count at sums[2 * C]
-  const float host_inv_n = dev_count ? 0.f : 1.f / count;
-  return pm_ew_launch(true, pm_pixels(x), C, (hipStream_t)stream, "bn_bwd_apply_pool", [=] __device__(long p, int ch) {
-    const float inv_n = dev_count ? 1.f / sums[2 * C] : host_inv_n;
-    float4 g = pm_maxpool_gather4(pd, a, Ho, Wo, argmax, H, W, C, p, ch);
-    const float4 v = PM_LD4(px + p * c + ch), mu = PM_LD4(mean + ch), is = PM_LD4(invstd + ch), ga = PM_LD4(gamma + ch), be = PM_LD4(beta + ch);
-    g.x = bn_affine(v.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f, g.y = bn_affine(v.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-    g.z = bn_affine(v.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f, g.w = bn_affine(v.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-    const float4 s1 = PM_LD4(sums + ch), s2 = PM_LD4(sums + C + ch);
-    float4 r;
-    r.x = (g.x - s1.x * inv_n - (v.x - mu.x) * is.x * (s2.x * inv_n)) * (is.x * ga.x);
-    r.y = (g.y - s1.y * inv_n - (v.y - mu.y) * is.y * (s2.y * inv_n)) * (is.y * ga.y);
-    r.z = (g.z - s1.z * inv_n - (v.z - mu.z) * is.z * (s2.z * inv_n)) * (is.z * ga.z);
-    r.w = (g.w - s1.w * inv_n - (v.w - mu.w) * is.w * (s2.w * inv_n)) * (is.w * ga.w);
-    PM_ST4(pdx + p * d + ch, r);
-  });
+  return bn_bwd_apply<float, 2>("bn_bwd_apply_pool", g, nullptr, nullptr, x, mean, invstd, gamma, beta, sums, count, 2, dx, nullptr, (hipStream_t)stream);
 }

@@ -69,17 +69,8 @@ int pm_bf16_cast_weights_s2(const float* w, int Cout, int kh, int kw, int Cin, i
 int pm_bf16_transpose_taps(const float* x, long pitch, int C, int N, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad, int dil, void* out,
                            hipStream_t st);
 
-// ---- bf16 activation tier (act16.hip): the bf16 forms of the elementwise / reduction entry points; the extern "C" functions dispatch on dtype ------
+// ---- bf16 activation tier (act16.hip): the bf16 forms of the elementwise / pooling / resize entry points; the extern "C" functions dispatch on dtype (BatchNorm: bn.hip) ------
 typedef unsigned short pm_bf16;
-int pm16_bn_stats(const pm_tensor* x, float* moments, float eps, float* mean, float* invstd, float* running_mean, float* running_var, float momentum, void* ws,
-                  size_t ws_bytes, hipStream_t st);      // moments != NULL: mean | M2 | count ; else finalise
-size_t pm16_bn_workspace(const pm_tensor* x);
-int pm16_bn_apply_mask(const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res, int relu,
-                       const pm_tensor* y, uint8_t* mask, hipStream_t st);
-int pm16_bn_bwd_reduce(const pm_tensor* dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
-                       const float* beta, int relu, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, hipStream_t st);
-int pm16_bn_bwd_apply(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                      const float* sums, float count, int relu, const pm_tensor* dx, const pm_tensor* dres, hipStream_t st);
 int pm16_add_n(const pm_tensor* const* xs, int n, const pm_tensor* y, hipStream_t st);
 int pm16_copy(const pm_tensor* x, const pm_tensor* y, hipStream_t st);
 int pm16_maxpool_fwd(const pm_tensor* x, const pm_tensor* y, uint8_t* argmax, hipStream_t st);
@@ -352,3 +343,25 @@ static inline bool pm_same_shape(const pm_tensor* a, const pm_tensor* b) { retur
 static inline bool pm_vec4(const pm_tensor* t) { return pm_vec_ok(t) && t->c % 4 == 0; }
 #define PM_LD4(ptr) (*reinterpret_cast<const float4*>(ptr))
 #define PM_ST4(ptr, v) (*reinterpret_cast<float4*>(ptr) = (v))
+
+// eight fp32 values (two 16-byte loads): per-channel parameters next to an eight-channel bf16 access
+__device__ __forceinline__ void pm_ld8f(const float* p, float* v) {
+  const float4 a = PM_LD4(p), b = PM_LD4(p + 4);
+  v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+}
+// the elementwise driver of the bf16 tier: thread -> (pixel, 8 channels)
+template <typename F>
+__global__ __launch_bounds__(256) void pm_ew16_kernel(long pixels, int cg, F f) {
+  const long total = pixels * cg;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long p = i / cg;
+    f(p, (int)(i - p * cg) * 8);
+  }
+}
+template <typename F>
+static inline int pm_ew16_launch(long pixels, int c, hipStream_t st, const char* name, F f) {
+  if (pixels * c == 0) return PM_OK;
+  const long work = pixels * (c / 8);
+  hipLaunchKernelGGL((pm_ew16_kernel<F>), dim3((int)std::min<long>((work + 255) / 256, 256 * 16)), dim3(256), 0, st, pixels, c / 8, f);
+  return pm_check_launch(name);
+}

@@ -492,6 +492,19 @@ def bn_apply_res_affine(x, mean, invstd, gamma, beta, r, r_mean, r_invstd, r_gam
     return (y, mask) if want_mask else y
 
 
+def _bwd_sums(x, with_count, sums):
+    """Where a backward reduce pass writes: `sums` (a slot of a buffer several layers share, ops._BnSums) or a new float[2c (+ 1)]; with_count: [2c] = this rank's
+    element count (SyncBatchNorm all-reduces it together with the sums)."""
+    c = x.shape[3]
+    n = 2 * c + (1 if with_count else 0)
+    if sums is None:
+        sums = torch.empty(n, dtype=torch.float32, device=x.device)
+    assert sums.numel() == n and sums.is_contiguous()
+    if with_count:
+        sums[2 * c:].fill_(float(x.shape[0] * x.shape[1] * x.shape[2]))
+    return sums
+
+
 def bn_bwd_apply_mask(dy, mask, x, mean, invstd, gamma, sums, count):
     """bn_bwd_apply(dy * mask, relu=0) with the mask read from bn_apply(want_mask=True)'s bytes; x: any tensor of that shape with its own statistics (fp32)."""
     dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
@@ -500,12 +513,9 @@ def bn_bwd_apply_mask(dy, mask, x, mean, invstd, gamma, sums, count):
     return dx
 
 
-def bn_bwd_reduce_mask(dy, mask, x, mean, invstd, want_gmask=True, with_count=False):
+def bn_bwd_reduce_mask(dy, mask, x, mean, invstd, want_gmask=True, with_count=False, sums=None):
     """bn_bwd_reduce(relu=1) with the ReLU mask read from bn_apply(want_mask=True)'s bytes instead of the forward output."""
-    c = x.shape[3]
-    sums = torch.empty(2 * c + (1 if with_count else 0), dtype=torch.float32, device=x.device)
-    if with_count:
-        sums[2 * c:].fill_(float(x.shape[0] * x.shape[1] * x.shape[2]))
+    sums = _bwd_sums(x, with_count, sums)
     xd = tdesc(x)
     lib = _lib()
     nb = _sizes(('bn', x.shape, x.dtype), lambda: lib.pm_bn_workspace(byref(xd)))
@@ -526,14 +536,11 @@ def scale_shift_act(x, scale, shift, residual=None, relu=False):
     return y
 
 
-def bn_bwd_reduce(dy, y, x, mean, invstd, relu, gamma=None, beta=None, want_gmask=False, with_count=False):
+def bn_bwd_reduce(dy, y, x, mean, invstd, relu, gamma=None, beta=None, want_gmask=False, with_count=False, sums=None):
     """relu: 0 / False none, 1 / True mask from the forward output y, 2 mask rebuilt from x (needs gamma, beta). -> (sums, dy * mask or None).
-    with_count: sums gets a third section [2c] = this rank's element count (SyncBatchNorm all-reduces it together with the sums)."""
+    with_count: sums gets a third section [2c] = this rank's element count. sums: write there instead of allocating (_bwd_sums)."""
     relu = int(relu)
-    c = x.shape[3]
-    sums = torch.empty(2 * c + (1 if with_count else 0), dtype=torch.float32, device=x.device)
-    if with_count:
-        sums[2 * c:].fill_(float(x.shape[0] * x.shape[1] * x.shape[2]))
+    sums = _bwd_sums(x, with_count, sums)
     xd = tdesc(x)
     lib = _lib()
     nb = _sizes(('bn', x.shape, x.dtype), lambda: lib.pm_bn_workspace(byref(xd)))
@@ -604,25 +611,32 @@ def maxpool_bn_relu_fwd(x, mean, invstd, gamma, beta):
     return y, arg
 
 
-def bn_relu_bwd_pool(dyp, arg, x, mean, invstd, gamma, beta, with_count=False, reduce_sums=None):
-    """Backward of relu(bn(x)) followed by the 3x3 / s2 max pool, from the pooled gradient dyp and the argmax bytes: -> (dx, local sums [sum dy | sum dy xhat (| count)]).
-    = maxpool_bwd, bn_bwd_reduce(relu=2), bn_bwd_apply(relu=2) without the full-resolution gradient. reduce_sums: SyncBatchNorm's all-reduce of the sums (with_count)."""
-    c = x.shape[3]
-    sums = torch.empty(2 * c + (1 if with_count else 0), dtype=torch.float32, device=x.device)
-    if with_count:
-        sums[2 * c:].fill_(float(x.shape[0] * x.shape[1] * x.shape[2]))
-    xd, dd = tdesc(x), tdesc(dyp)
+def bn_bwd_reduce_pool(dyp, arg, x, mean, invstd, gamma, beta, with_count=False, sums=None):
+    """bn_bwd_reduce(relu=2) whose incoming gradient is maxpool_bwd(dyp, arg), gathered inside the pass: -> local sums [sum dy | sum dy xhat (| count)] (fp32)."""
+    sums = _bwd_sums(x, with_count, sums)
+    xd = tdesc(x)
     lib = _lib()
     nb = _sizes(('bn', x.shape, x.dtype), lambda: lib.pm_bn_workspace(byref(xd)))
     ws = workspace(nb, x.device)
-    check(lib.pm_bn_bwd_reduce_pool(byref(dd), arg.data_ptr(), byref(xd), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), sums.data_ptr(), ptr(ws), nb,
-                                    stream()), 'pm_bn_bwd_reduce_pool')
-    total = reduce_sums(sums) if reduce_sums is not None else sums
-    count = -1.0 if with_count else float(x.shape[0] * x.shape[1] * x.shape[2])
+    check(lib.pm_bn_bwd_reduce_pool(byref(tdesc(dyp)), arg.data_ptr(), byref(xd), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), sums.data_ptr(),
+                                    ptr(ws), nb, stream()), 'pm_bn_bwd_reduce_pool')
+    return sums
+
+
+def bn_bwd_apply_pool(dyp, arg, x, mean, invstd, gamma, beta, sums, count):
+    """bn_bwd_apply(relu=2) on the same gathered gradient -> dx; sums / count as bn_bwd_apply."""
     dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    check(lib.pm_bn_bwd_apply_pool(byref(dd), arg.data_ptr(), byref(xd), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), total.data_ptr(), count,
-                                   byref(tdesc(dx)), stream()), 'pm_bn_bwd_apply_pool')
-    return dx, sums
+    check(_lib().pm_bn_bwd_apply_pool(byref(tdesc(dyp)), arg.data_ptr(), byref(tdesc(x)), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                      sums.data_ptr(), float(count), byref(tdesc(dx)), stream()), 'pm_bn_bwd_apply_pool')
+    return dx
+
+
+def bn_relu_bwd_pool(dyp, arg, x, mean, invstd, gamma, beta, with_count=False):
+    """Backward of relu(bn(x)) followed by the 3x3 / s2 max pool, from the pooled gradient dyp and the argmax bytes: -> (dx, local sums [sum dy | sum dy xhat (| count)]).
+    = maxpool_bwd, bn_bwd_reduce(relu=2), bn_bwd_apply(relu=2) without the full-resolution gradient, on this rank alone (ops._Stem puts the exchange between the two)."""
+    sums = bn_bwd_reduce_pool(dyp, arg, x, mean, invstd, gamma, beta, with_count)
+    count = -1.0 if with_count else float(x.shape[0] * x.shape[1] * x.shape[2])
+    return bn_bwd_apply_pool(dyp, arg, x, mean, invstd, gamma, beta, sums, count), sums
 
 
 def maxpool_bwd(dy, arg, x_shape):

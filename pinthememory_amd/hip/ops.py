@@ -192,101 +192,107 @@ def wait_commit():
         torch.cuda.current_stream().wait_event(ev)
 
 
-BN_FUSED_FINALIZE = _os.environ.get('PM_BN_FUSED', '1') == '1'      # A/B knob: 0 = separate bn_stats / bn_finalize launches
-
-
-RELU_MASK_BYTES = _os.environ.get('PM_BN_MASK', '1') == '1'      # A/B knob: 0 = the residual BatchNorms' backward re-reads the forward output for its ReLU mask
-
-
-MERGE_SYNCBN = _os.environ.get('PM_MERGE_SYNCBN', '1') == '1'      # A/B knob: 0 = one exchange per BatchNorm (rounds 1-5)
+def _same_exchange(groups, widths):
+    """Do these BatchNorm layers share an exchange? Every one a SyncBatchNorm of the same process group (more than one rank, or forced collectives) and width."""
+    return D.is_dist() and all(g is not None and g is groups[0] for g in groups) and len(set(widths)) == 1
 
 
 def _bn_train_stats_multi(ys, bns, partials):
-    """Batch statistics of SEVERAL independent SyncBatchNorms of equal width in ONE exchange (ASPP's five branches, a stage's first block's bn3 +
-    downsample.1): local moments of each, one all-gather of their concatenation, one merge + finalise per layer. -> [(mean, invstd)]; running moments updated in place.
-    Same arithmetic per layer as _bn_train_fwd's SyncBN branch (the merge kernel sees the same per-rank moments in the same rank order)."""
-    c = ys[0].shape[3]
-    moms = []
-    for y, part in zip(ys, partials):
-        pixels = y.shape[0] * y.shape[1] * y.shape[2]
-        moms.append(K.bn_partials_moments(part, pixels, c) if part is not None else K.bn_stats(y))
+    """Batch statistics of independent BatchNorm layers -> [(mean, invstd)]; running moments updated in place.
+    partials[i]: the (mean, M2) slab partials the producing convolution's epilogue emitted for ys[i] (K.conv_fwd(bn_partials=...)), or None: with them no kernel
+    re-reads ys[i] for its statistics.
+    Local statistics: one finalising launch per layer. SyncBatchNorm: local moments of each layer, ONE all-gather of their concatenation for layers that share an
+    exchange (ASPP's five branches, a stage's first block's bn3 + downsample.1), one merge + finalise per layer -- per layer the arithmetic of a lone exchange (the
+    merge kernel sees the same per-rank moments in the same rank order). Layers that cannot travel together are served one by one."""
     n = len(ys)
-    flat, world = D.gather_moments(torch.cat(moms), bns[0].group)
+    if n > 1 and not _same_exchange([b.group for b in bns], [y.shape[3] for y in ys]):
+        return [_bn_train_stats(y, bn, part) for y, bn, part in zip(ys, bns, partials)]
+    pixels = [y.shape[0] * y.shape[1] * y.shape[2] for y in ys]
+    if bns[0].group is None:
+        y, bn, part = ys[0], bns[0], partials[0]
+        if part is not None:
+            return [K.bn_partials_finalize(part, pixels[0], y.shape[3], bn.eps, bn.running_mean, bn.running_var, bn.momentum)]
+        return [K.bn_stats_finalize(y, bn.eps, bn.running_mean, bn.running_var, bn.momentum)]
+    c = ys[0].shape[3]
+    moms = [K.bn_partials_moments(part, px, c) if part is not None else K.bn_stats(y) for y, part, px in zip(ys, partials, pixels)]
+    flat, world = D.gather_moments(moms[0] if n == 1 else torch.cat(moms), bns[0].group)      # SyncBN: stats, all-gather, merge + finalise, apply
     parts = flat.view(world, n, 3 * c)
     return [K.bn_merge_finalize(parts[:, i].contiguous().view(-1), world, c, bn.eps, bn.running_mean, bn.running_var, bn.momentum) for i, bn in enumerate(bns)]
 
 
-def _mergeable(bns, ys):
-    """One exchange for these layers? Every one a SyncBatchNorm of the same process group and width, more than one rank, the fused finalise on."""
-    return (MERGE_SYNCBN and BN_FUSED_FINALIZE and D.is_dist() and len(bns) > 1 and all(b.group is not None and b.group is bns[0].group for b in bns)
-            and len({y.shape[3] for y in ys}) == 1)
-
-
 def _bn_train_stats(y, bn, partials=None):
-    """Batch statistics of y (merged across ranks for SyncBN) -> (mean, invstd); running moments updated in place.
-    partials: the (mean, M2) slab partials the producing convolution's epilogue emitted for y (K.conv_fwd(bn_partials=...)), or None:
-    with them no kernel re-reads y for its statistics."""
-    c = y.shape[3]
-    pixels = y.shape[0] * y.shape[1] * y.shape[2]
-    if bn.group is None and BN_FUSED_FINALIZE:
-        if partials is not None:
-            mean, invstd = K.bn_partials_finalize(partials, pixels, c, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
-        else:
-            mean, invstd = K.bn_stats_finalize(y, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
-    elif bn.group is not None and D.is_dist() and BN_FUSED_FINALIZE:
-        mom = K.bn_partials_moments(partials, pixels, c) if partials is not None else K.bn_stats(y)
-        flat, world = D.gather_moments(mom, bn.group)                  # SyncBN: stats, all-gather, merge + finalise, apply
-        mean, invstd = K.bn_merge_finalize(flat, world, c, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
-    else:
-        mom = K.bn_partials_moments(partials, pixels, c) if partials is not None else K.bn_stats(y)
-        if bn.group is not None:
-            mom = D.merge_moments(mom, c, bn.group)
-        mean, invstd = K.bn_finalize(mom, c, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
-    return mean, invstd
+    """Batch statistics of y (merged across ranks for SyncBN) -> (mean, invstd): the one-layer case of _bn_train_stats_multi."""
+    return _bn_train_stats_multi([y], [bn], [partials])[0]
 
 
-def _bn_train_fwd(y, gamma, beta, bn, residual, relu, out=None, partials=None, want_mask=False):
+def _bn_train_fwd(y, gamma, beta, bn, residual, relu, out=None, partials=None):
     """Batch statistics (_bn_train_stats) -> normalise + residual + ReLU. Returns (o, mean, invstd)."""
     mean, invstd = _bn_train_stats(y, bn, partials)
-    if want_mask:      # BN + residual + ReLU: one byte per float4 group tells the backward which gradients the ReLU passes (1 / 16 of re-reading the output)
-        o, mask = K.bn_apply(y, mean, invstd, gamma, beta, residual=residual, relu=relu, out=out, want_mask=True)
-        return o, mean, invstd, mask
     return K.bn_apply(y, mean, invstd, gamma, beta, residual=residual, relu=relu, out=out), mean, invstd
+
+
+class _BnSums:
+    """The backward sums of n BatchNorm layers of width c that share an exchange: slot i = [sum dy | sum dy * xhat (| count)] of layer i, 2c (+ 1) floats. A BatchNorm
+    backward is three phases over these slots --
+      reduce:   K.bn_bwd_reduce / K.bn_bwd_reduce_mask / K.bn_bwd_reduce_pool(sums=slot(i)) writes layer i's local sums, and its count under SyncBatchNorm;
+      exchange: ONE all-reduce over all slots (nothing without a process group). The global count travels with the sums (uneven batches);
+      apply:    K.bn_bwd_apply / K.bn_bwd_apply_mask / K.bn_bwd_apply_pool(total(i), count(y)).
+    dgamma / dbeta are THIS rank's sums (torch.nn.SyncBatchNorm returns the local grad_weight / grad_bias and lets DDP average them); only the input gradient needs
+    the sums over all ranks. Slots start at multiples of 4 floats: the apply passes read them 16 bytes at a time."""
+
+    def __init__(self, n, c, group, device):
+        self.c, self.group, self.with_count = c, group, group is not None
+        self.len = 2 * c + (1 if self.with_count else 0)
+        self.stride = (self.len + 3) // 4 * 4
+        self.local = torch.empty((n - 1) * self.stride + self.len, dtype=torch.float32, device=device)
+        self.summed = self.local
+
+    def slot(self, i):
+        return self.local[i * self.stride:i * self.stride + self.len]
+
+    def exchange(self):
+        if self.group is not None:
+            self.summed = D.all_reduce_sum_copy(self.local, self.group)      # out of place: the local sums are the parameter gradients
+
+    def total(self, i):
+        return self.summed[i * self.stride:i * self.stride + self.len]
+
+    def count(self, y):
+        """The count argument of the apply pass: the local element count, or -1 (on the device, behind the sums) under SyncBatchNorm."""
+        return -1.0 if self.with_count else float(y.shape[0] * y.shape[1] * y.shape[2])
+
+    def grads(self, i):
+        """-> (dgamma, dbeta) of layer i"""
+        s = self.slot(i)
+        return s[self.c:2 * self.c], s[:self.c]
 
 
 def _bn_train_bwd(dv, o, y, mean, invstd, gamma, beta, relu, group, want_dres, has_res, mask=None):
     """-> (dy, dres, dgamma, dbeta): gradient of the conv output, of the residual input, and of the affine parameters.
     ReLU mask: rebuilt from the conv output when no residual entered the activation (the forward output is not read at all);
-    otherwise taken from the forward output once, in the reduce pass, which then hands the masked gradient (= dres) to the apply pass."""
-    c = y.shape[3]
+    otherwise taken from the mask bytes (or the forward output) once, in the reduce pass, which then hands the masked gradient (= dres) to the apply pass."""
     mode = 0 if not relu else (1 if has_res else 2)
     hand_over = mode == 1 and want_dres
+    S = _BnSums(1, y.shape[3], group, y.device)
     if hand_over and mask is not None:
-        sums, gm = K.bn_bwd_reduce_mask(dv, mask, y, mean, invstd, want_gmask=True, with_count=group is not None)
+        _, gm = K.bn_bwd_reduce_mask(dv, mask, y, mean, invstd, want_gmask=True, with_count=S.with_count, sums=S.slot(0))
     else:
-        sums, gm = K.bn_bwd_reduce(dv, o, y, mean, invstd, mode, gamma, beta, want_gmask=hand_over, with_count=group is not None)
-    local = sums
-    if group is not None:
-        # dgamma / dbeta are THIS rank's sums (torch.nn.SyncBatchNorm returns the local grad_weight / grad_bias and lets DDP average them);
-        # only the input gradient needs the sums over all ranks
-        sums = D.all_reduce_sum_copy(local, group)  # [sum dy | sum dy * xhat | count]: the global count travels with the sums (uneven batches); out of place
-    count = float(y.shape[0] * y.shape[1] * y.shape[2]) if group is None else -1.0
+        _, gm = K.bn_bwd_reduce(dv, o, y, mean, invstd, mode, gamma, beta, want_gmask=hand_over, with_count=S.with_count, sums=S.slot(0))
+    S.exchange()
     if hand_over:
-        dy, _ = K.bn_bwd_apply(gm, None, y, mean, invstd, gamma, sums, count, 0, False)
-        dres = gm
+        dy, dres = K.bn_bwd_apply(gm, None, y, mean, invstd, gamma, S.total(0), S.count(y), 0, False)[0], gm
     else:
-        dy, dres = K.bn_bwd_apply(dv, o, y, mean, invstd, gamma, sums, count, mode, want_dres, beta)
-    return dy, dres, local[c:2 * c], local[:c]
+        dy, dres = K.bn_bwd_apply(dv, o, y, mean, invstd, gamma, S.total(0), S.count(y), mode, want_dres, beta)
+    return (dy, dres, *S.grads(0))
 
 
 def _bn_bwd_masked(dv, mask, y, mean, invstd, gamma, group):
     """-> (dy, dgamma, dbeta) of a BatchNorm whose output gradient is dv masked by `mask` (bn_apply(want_mask=True)'s bytes): what _bn_train_bwd computes from the
     stored masked gradient, without storing it. y / mean / invstd / gamma: the BatchNorm the mask came from, or the downsample BatchNorm behind the same ReLU. fp32."""
-    c = y.shape[3]
-    local, _ = K.bn_bwd_reduce_mask(dv, mask, y, mean, invstd, want_gmask=False, with_count=group is not None)
-    sums = local if group is None else D.all_reduce_sum_copy(local, group)
-    count = float(y.shape[0] * y.shape[1] * y.shape[2]) if group is None else -1.0
-    return K.bn_bwd_apply_mask(dv, mask, y, mean, invstd, gamma, sums, count), local[c:2 * c], local[:c]
+    S = _BnSums(1, y.shape[3], group, y.device)
+    K.bn_bwd_reduce_mask(dv, mask, y, mean, invstd, want_gmask=False, with_count=S.with_count, sums=S.slot(0))
+    S.exchange()
+    return (K.bn_bwd_apply_mask(dv, mask, y, mean, invstd, gamma, S.total(0), S.count(y)), *S.grads(0))
 
 
 class _Bottleneck(torch.autograd.Function):
@@ -305,35 +311,28 @@ class _Bottleneck(torch.autograd.Function):
         y2 = K.conv_fwd(o1, k2, *geoms[1], keep_v=kv, bn_partials=ps)      # Winograd layers keep the transformed input for the weight gradient
         o2, m2, i2 = _bn_train_fwd(y2, g2, b2, bns[1], None, True, partials=ps[1])
         y3 = K.conv_fwd(o2, k3, *geoms[2], bn_partials=ps)
-        merged = False
+        m3 = None
         if wd is not None:
             kd = K.krsc(wd)
             yd = K.conv_fwd(xv, kd, *geoms[3], bn_partials=ps)
-            merged = _mergeable([bns[3], bns[2]], [yd, y3])
             # fp32: the normalised downsample output is never stored -- bn3's apply pass evaluates it from yd (K.bn_apply_res_affine). The bf16 tier keeps its two launches.
             fold = y3.dtype == torch.float32 and yd.dtype == torch.float32
-            if merged:      # SyncBN: the two independent statistics exchanges of the block's tail travel as one
+            if fold or _same_exchange([bns[3].group, bns[2].group], [yd.shape[3], y3.shape[3]]):
+                # both statistics before either apply pass; under SyncBN the two independent exchanges of the block's tail travel as one
                 (md, idd), (m3, i3) = _bn_train_stats_multi([yd, y3], [bns[3], bns[2]], [ps[3], ps[2]])
                 res = None if fold else K.bn_apply(yd, md, idd, gd, bd, residual=None, relu=False)
-            elif fold:
-                md, idd = _bn_train_stats(yd, bns[3], ps[3])
-                m3, i3 = _bn_train_stats(y3, bns[2], ps[2])
-                res = None
             else:
                 res, md, idd = _bn_train_fwd(yd, gd, bd, bns[3], None, False, partials=ps[3])
         else:
             kd = yd = md = idd = None
             res = xv
+        if m3 is None:
+            m3, i3 = _bn_train_stats(y3, bns[2], ps[2])
+        # BN + residual + ReLU: one byte per 16-byte channel group tells the backward which gradients the ReLU passes (1 / 16 of re-reading the output)
         if res is None:
             out, mask3 = K.bn_apply_res_affine(y3, m3, i3, g3, b3, yd, md, idd, gd, bd, relu=True, want_mask=True)
-            if not RELU_MASK_BYTES:
-                mask3 = None
-        elif merged:
-            out, mask3 = K.bn_apply(y3, m3, i3, g3, b3, residual=res, relu=True, want_mask=True) if RELU_MASK_BYTES else (K.bn_apply(y3, m3, i3, g3, b3, residual=res, relu=True), None)
-        elif RELU_MASK_BYTES:
-            out, m3, i3, mask3 = _bn_train_fwd(y3, g3, b3, bns[2], res, True, partials=ps[2], want_mask=True)
         else:
-            (out, m3, i3), mask3 = _bn_train_fwd(y3, g3, b3, bns[2], res, True, partials=ps[2]), None
+            out, mask3 = K.bn_apply(y3, m3, i3, g3, b3, residual=res, relu=True, want_mask=True)
         ctx.geoms, ctx.groups, ctx.has_ds, ctx.deferred = geoms, [b.group for b in bns], wd is not None, deferred
         ctx.save_for_backward(xv, k1, k2, k3, kd, y1, o1, y2, o2, y3, yd, out, m1, i1, m2, i2, m3, i3, md, idd, g1, g2, g3, gd, b1, b2, b3, kv[0], mask3)
         return nchw(out)
@@ -344,22 +343,17 @@ class _Bottleneck(torch.autograd.Function):
         ge, gr, df = ctx.geoms, ctx.groups, ctx.deferred
         dv = _grad_view(dout)
         pair = None
-        if ctx.has_ds and MERGE_SYNCBN and D.is_dist() and gr[2] is not None and gr[3] is gr[2] and y3.shape[3] == yd.shape[3]:
+        if ctx.has_ds and _same_exchange([gr[2], gr[3]], [y3.shape[3], yd.shape[3]]):
             # SyncBN, first block of a stage: bn3's masked gradient (= the skip gradient) is known after bn3's REDUCE pass, before its exchange -- so the downsample
             # BatchNorm's reduce pass runs on it right away and the two sum exchanges travel as ONE all-reduce; then both apply passes.
-            c3 = y3.shape[3]
-            if mask3 is not None:
-                s3, gm = K.bn_bwd_reduce_mask(dv, mask3, y3, m3, i3, want_gmask=True, with_count=True)
-            else:
-                s3, gm = K.bn_bwd_reduce(dv, out, y3, m3, i3, 1, g3, b3, want_gmask=True, with_count=True)
-            sd, _ = K.bn_bwd_reduce(gm, None, yd, md, idd, 0, gd, None, want_gmask=False, with_count=True)
-            both = D.all_reduce_sum_copy(torch.cat([s3, sd]), gr[2])
-            g3sum, gdsum = both[:s3.numel()], both[s3.numel():]
-            dy3, _ = K.bn_bwd_apply(gm, None, y3, m3, i3, g3, g3sum, -1.0, 0, False)
-            dres, dg3, db3 = gm, s3[c3:2 * c3], s3[:c3]
-            dyd, _ = K.bn_bwd_apply(gm, None, yd, md, idd, gd, gdsum, -1.0, 0, False, None)
-            pair = (dyd, sd[c3:2 * c3], sd[:c3])
-        elif mask3 is not None and dv.dtype == torch.float32 and K.CONV_PREC != 2:
+            S = _BnSums(2, y3.shape[3], gr[2], y3.device)
+            _, gm = K.bn_bwd_reduce_mask(dv, mask3, y3, m3, i3, want_gmask=True, with_count=True, sums=S.slot(0))
+            K.bn_bwd_reduce(gm, None, yd, md, idd, 0, gd, None, want_gmask=False, with_count=True, sums=S.slot(1))
+            S.exchange()
+            dy3, _ = K.bn_bwd_apply(gm, None, y3, m3, i3, g3, S.total(0), -1.0, 0, False)
+            dyd, _ = K.bn_bwd_apply(gm, None, yd, md, idd, gd, S.total(1), -1.0, 0, False, None)
+            dres, (dg3, db3), pair = gm, S.grads(0), (dyd, *S.grads(1))
+        elif dv.dtype == torch.float32 and K.CONV_PREC != 2:
             # fp32: the masked gradient dv * mask3 (bn3's input gradient AND the skip gradient) is never stored -- every reader takes (dv, mask3). ('bf16_operands' sends
             # conv1's data gradient to the bf16 kernels, whose epilogue takes no masked add: that configuration keeps the stored form.)
             dy3, dg3, db3 = _bn_bwd_masked(dv, mask3, y3, m3, i3, g3, gr[2])
@@ -520,16 +514,17 @@ class _Stem(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         xv, wk, y, mean, invstd, gamma, beta, arg, vk = ctx.saved_tensors
-        c = y.shape[3]
-        grp = ctx.group
-        dy, local = K.bn_relu_bwd_pool(_grad_view(dout), arg, y, mean, invstd, gamma, beta, with_count=grp is not None,
-                                       reduce_sums=(lambda s: D.all_reduce_sum_copy(s, grp)) if grp is not None else None)
+        dv = _grad_view(dout)
+        S = _BnSums(1, y.shape[3], ctx.group, y.device)
+        K.bn_bwd_reduce_pool(dv, arg, y, mean, invstd, gamma, beta, with_count=S.with_count, sums=S.slot(0))
+        S.exchange()
+        dy = K.bn_bwd_apply_pool(dv, arg, y, mean, invstd, gamma, beta, S.total(0), S.count(y))
         dx = nchw(K.conv_bwd_data(dy, wk, tuple(xv.shape), *ctx.geom, dtype=xv.dtype)) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             dwk, _ = _wgrad(xv, dy, tuple(wk.shape), ctx.geom, wino_v=vk)
             dw = dwk.permute(0, 3, 1, 2)
-        return dx, dw, local[c:2 * c], local[:c], None, None
+        return (dx, dw, *S.grads(0), None, None)
 
 
 def stem_tail(x, w, conv, bn):
@@ -568,17 +563,18 @@ class _ConvBnActN(torch.autograd.Function):
         n = ctx.n
         sv = ctx.saved_tensors
         xvs, wks, ys, os_, means, invs, gammas, betas, kvs = (sv[i * n:(i + 1) * n] for i in range(9))
-        c = ys[0].shape[3]
-        red = [K.bn_bwd_reduce(_grad_view(douts[i]), os_[i], ys[i], means[i], invs[i], 2, gammas[i], betas[i], want_gmask=False, with_count=True) for i in range(n)]
-        tot = D.all_reduce_sum_copy(torch.cat([r[0] for r in red]), ctx.group)
-        ln = red[0][0].numel()
+        S = _BnSums(n, ys[0].shape[3], ctx.group, ys[0].device)
+        for i in range(n):
+            K.bn_bwd_reduce(_grad_view(douts[i]), os_[i], ys[i], means[i], invs[i], 2, gammas[i], betas[i], want_gmask=False, with_count=True, sums=S.slot(i))
+        S.exchange()
         dxs, dws, dgs, dbs = [], [], [], []
         for i in range(n):
-            dy, _ = K.bn_bwd_apply(_grad_view(douts[i]), os_[i], ys[i], means[i], invs[i], gammas[i], tot[i * ln:(i + 1) * ln], -1.0, 2, False, betas[i])
+            dy, _ = K.bn_bwd_apply(_grad_view(douts[i]), os_[i], ys[i], means[i], invs[i], gammas[i], S.total(i), -1.0, 2, False, betas[i])
             dxs.append(nchw(K.conv_bwd_data(dy, wks[i], tuple(xvs[i].shape), *ctx.geoms[i], dtype=xvs[i].dtype)) if ctx.needs_input_grad[5 + i] else None)
             dwk, _ = _wgrad(xvs[i], dy, tuple(wks[i].shape), ctx.geoms[i], deferred=ctx.deferreds[i], wino_v=kvs[i])
             dws.append(dwk.permute(0, 3, 1, 2))
-            dgs.append(red[i][0][c:2 * c]), dbs.append(red[i][0][:c])
+            dg, db = S.grads(i)
+            dgs.append(dg), dbs.append(db)
         return (None, None, None, None, None, *dxs, *dws, *dgs, *dbs)
 
 
@@ -586,10 +582,8 @@ def conv_bn_act_n(xs, seqs, outs):
     """[conv_bn_act(x, seq[0], seq[1], relu=True, out=o)] for independent (x, Sequential(conv, bn, relu)) branches; ONE SyncBatchNorm exchange per direction when the
     branches qualify (training, gradients on, more than one rank, equal width, no conv bias), the per-branch path otherwise."""
     convs, bns_m = [q[0] for q in seqs], [q[1] for q in seqs]
-    ok = MERGE_SYNCBN and BN_FUSED_FINALIZE and D.is_dist() and torch.is_grad_enabled() and all(b.training for b in bns_m) and all(cv.bias is None for cv in convs)
-    if ok:
-        groups = [D.bn_group(b) for b in bns_m]
-        ok = all(g is not None and g is groups[0] for g in groups) and len({cv.out_channels for cv in convs}) == 1
+    ok = (torch.is_grad_enabled() and all(b.training for b in bns_m) and all(cv.bias is None for cv in convs)
+          and _same_exchange([D.bn_group(b) for b in bns_m], [cv.out_channels for cv in convs]))
     if not ok:
         return [conv_bn_act(x, cv, bn, relu=True, out=o) for x, cv, bn, o in zip(xs, convs, bns_m, outs)]
     states = [BNState(b) for b in bns_m]      # (registers each layer's num_batches_tracked increment: once, here)
