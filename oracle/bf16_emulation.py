@@ -1,6 +1,6 @@
 """Oracle tooling (test infrastructure; only tests/ may import it): the CPU oracle with the STORAGE ROUNDING of the bf16 tier emulated.
 
-The bf16 tier (BASELINE configs[2], pinthememory_amd/csrc/act16.hip + conv16.hip) keeps every activation and activation gradient between layers as bf16 (8 mantissa
+The bf16 tier (BASELINE configs[2], pinthememory_amd/csrc: the bf16 instantiations of bn.hip / pool_resize.hip / misc.hip + conv16.hip) keeps every activation and activation gradient between layers as bf16 (8 mantissa
 bits, round to nearest even), rounds the convolution operands (activations and weights) to bf16 and does all arithmetic in fp32. What that storage costs in accuracy is
 a property of the NETWORK (ReLU units within 2^-9 of zero take the other branch, BatchNorm divides by a standard deviation that can be far smaller than the rounded
 mean), not of the kernels -- so the tier's assembled gradients are judged against THIS emulation: the same stock-torch oracle in float64 arithmetic with a rounding to

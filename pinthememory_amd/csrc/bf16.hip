@@ -9,6 +9,8 @@
 //   pm_bf16_transpose_taps x[N][H][W][C] fp32 -> xt[T][C][N*Ho*Wo] bf16: per tap the input pixel each output pixel sees (0 outside the
 //                          image), pixel-contiguous; and dy[P][Cout] -> dyt[Cout][P]. The weight gradient dw[co][(t, ci)] = sum_p
 //                          dyt[co][p] xt[t][ci][p] is then a plain k-contiguous GEMM over pixels for the same kernel.
+// The conversions of bf16 ACTIVATIONS live here too: pm16_to_f32 / pm16_pad_rows (the mixed-type call sites of the convolution entry points) and pm_cast (the
+// edges of the tier: the memory module and the losses stay fp32).
 // Replaces nothing in the reference by itself: it is the operand edge of nn.Conv2d under the bf16 tier (Resnet.py:145-150, deepv3plus.py:72-81,398-424).
 #include "pm_common.h"
 
@@ -195,6 +197,42 @@ __global__ __launch_bounds__(256) void cast_weights_s2_kernel(const float* __res
   }
 }
 
+// ---- bf16 ACTIVATIONS at the edges of the tier -------------------------------------------------------------------------------------------------------------
+constexpr int V = 8;                       // channels per 16-byte lane access
+// bf16 rows -> fp32 rows / bf16 rows padded with zero channels: thread = (pixel, 8 channels of the OUTPUT)
+__global__ __launch_bounds__(256) void to_f32_kernel(const pm_bf16* __restrict__ x, long pitch, int C, long P, float* __restrict__ out, long op) {
+  const int cg = (C + V - 1) / V;
+  const long total = P * cg;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long p = i / cg;
+    const int c = (int)(i - p * cg) * V;
+    if (c + V <= C && ((pitch | op) & 7) == 0) {
+      float v[V];
+      pm_ld8(x + p * pitch + c, v);
+      PM_ST4(out + p * op + c, make_float4(v[0], v[1], v[2], v[3]));
+      PM_ST4(out + p * op + c + 4, make_float4(v[4], v[5], v[6], v[7]));
+    } else {
+      for (int e = 0; e < V && c + e < C; ++e) out[p * op + c + e] = pm_bf16_to_f32(x[p * pitch + c + e]);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void pad_rows_kernel(const pm_bf16* __restrict__ x, long pitch, int C, int Cp, long P, pm_bf16* __restrict__ out) {
+  const int cg = Cp / V;
+  const long total = P * cg;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long p = i / cg;
+    const int c = (int)(i - p * cg) * V;
+    uint4 q = make_uint4(0u, 0u, 0u, 0u);
+    if (c + V <= C && (pitch & 7) == 0) q = *reinterpret_cast<const uint4*>(x + p * pitch + c);
+    else {
+      unsigned short e8[V];
+      for (int e = 0; e < V; ++e) e8[e] = c + e < C ? x[p * pitch + c + e] : (unsigned short)0;
+      q.x = e8[0] | ((unsigned)e8[1] << 16), q.y = e8[2] | ((unsigned)e8[3] << 16), q.z = e8[4] | ((unsigned)e8[5] << 16), q.w = e8[6] | ((unsigned)e8[7] << 16);
+    }
+    *reinterpret_cast<uint4*>(out + p * Cp + c) = q;
+  }
+}
+
 }  // namespace
 
 int pm_bf16_cast_weights_s2(const float* w, int Cout, int kh, int kw, int Cin, int Cp, const PmS2Classes* cl, hipStream_t st) {
@@ -259,4 +297,40 @@ int pm_bf16_transpose_taps(const float* x, long pitch, int C, int N, int H, int 
   hipLaunchKernelGGL(transpose_taps_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)(kh * kw)), dim3(256), 0, st, x, pitch, C, g, P,
                      (unsigned short*)out);
   return pm_check_launch("bf16_transpose_taps");
+}
+
+int pm16_to_f32(const pm_bf16* x, long pitch, int C, long P, float* out, long out_pitch, hipStream_t st) {
+  const long total = P * ((C + V - 1) / V);
+  if (total == 0) return PM_OK;
+  hipLaunchKernelGGL(to_f32_kernel, dim3(pm_grid_for(total)), dim3(256), 0, st, x, pitch, C, P, out, out_pitch);
+  return pm_check_launch("bf16_to_f32");
+}
+int pm16_pad_rows(const pm_bf16* x, long pitch, int C, int Cp, long P, pm_bf16* out, hipStream_t st) {
+  const long total = P * (Cp / V);
+  if (total == 0) return PM_OK;
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(pm_grid_for(total)), dim3(256), 0, st, x, pitch, C, Cp, P, out);
+  return pm_check_launch("bf16_pad_rows");
+}
+
+// dtype conversion between two views of the same shape (the edges of the tier: the memory module and the losses stay fp32)
+extern "C" int pm_cast(const pm_tensor* x, const pm_tensor* y, void* stream) {
+  PM_REQUIRE(x && y && x->ptr && y->ptr && pm_same_shape(x, y), PM_EINVAL, "cast: shape mismatch");
+  hipStream_t st = (hipStream_t)stream;
+  const long P = pm_pixels(x);
+  if (pm_is_bf16(x) && pm_is_f32(y)) return pm16_to_f32((const pm_bf16*)x->ptr, x->pitch, x->c, P, (float*)y->ptr, y->pitch, st);
+  if (pm_is_f32(x) && pm_is_bf16(y)) {
+    const float* px = (const float*)x->ptr;
+    pm_bf16* py = (pm_bf16*)y->ptr;
+    const long a = x->pitch, c = y->pitch;
+    const int C = x->c;
+    if (C % 8 == 0 && pm_vec_ok(x) && y->pitch % 8 == 0 && pm_aligned16(y->ptr))      // 16-byte rows on both sides (any pitches: channel slices of wider buffers)
+      return pm_ew16_launch(P, C, st, "cast", [=] __device__(long p, int ch) {
+        float v[V];
+        pm_ld8f(px + p * a + ch, v);
+        pm_st8(py + p * c + ch, v);
+      });
+    return pm_ew_launch(false, P, C, st, "cast", [=] __device__(long p, int ch) { py[p * c + ch] = pm_f32_to_bf16(px[p * a + ch]); });      // odd shapes: element by element
+  }
+  PM_REQUIRE(false, PM_EUNSUPPORTED, "cast: dtype %d -> %d", x->dtype, y->dtype);
+  return PM_OK;
 }

@@ -3,62 +3,13 @@
 // used (Resnet.py:146-151,405,456; deepv3plus.py:73,79,88,399,405,410,413,421; memory.py:76,105).
 // Statistics are shifted sums (shift = first pixel of each channel) -> (mean, M2, count), combined in double in a
 // fixed order: one pass over the activation, no catastrophic cancellation, deterministic, mergeable across ranks.
-// One body per piece for fp32 and bf16 tensors: a lane moves 16 bytes (Elem<T>::V channels), values are widened to fp32 in registers and travel as float[V];
+// One body per piece for fp32 and bf16 tensors: a lane moves 16 bytes (pm_elem<T>::V channels), values are widened to fp32 in registers and travel as float[V];
 // every statistic / reduction / accumulator is fp32 (second stages in double); bf16 results are rounded (nearest even) once, on the way out.
 #include <type_traits>
 
 #include "pm_common.h"
 
 namespace {
-
-// ---- the element trait: what differs between the tiers -----------------------------------------------------------------------------
-template <typename T>
-struct Elem;
-template <>
-struct Elem<float> {
-  static constexpr int V = 4;      // channels per 16-byte lane access
-  static __device__ __forceinline__ void ld(const float* p, float* v) {
-    const float4 a = PM_LD4(p);
-    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float* v) { PM_ST4(p, make_float4(v[0], v[1], v[2], v[3])); }
-  static __device__ __forceinline__ float widen(float v) { return v; }
-  static int gpr(int) { return 16; }      // lane groups per pixel row: 16 float4 groups x 16 row lanes
-  static int check(const pm_tensor* t, const char* who) {
-    PM_REQUIRE_F32(t, who);      // a mixed-type call ends here
-    PM_REQUIRE(t && t->ptr && pm_vec4(t), PM_EINVAL, "%s: tensor must be 16B aligned, pitch %% 4 == 0 and C %% 4 == 0", who);
-    return PM_OK;
-  }
-};
-template <>
-struct Elem<pm_bf16> {
-  static constexpr int V = 8;
-  static __device__ __forceinline__ void ld(const pm_bf16* p, float* v) { pm_ld8(p, v); }
-  static __device__ __forceinline__ void st(pm_bf16* p, const float* v) { pm_st8(p, v); }
-  static __device__ __forceinline__ float widen(pm_bf16 v) { return pm_bf16_to_f32(v); }
-  static int gpr(int C) { return C <= 64 ? 8 : 16; }      // 8 for tensors of <= 64 channels: no idle half-waves on the 64-channel maps of layer1
-  static int check(const pm_tensor* t, const char* who) {
-    PM_REQUIRE(t && t->ptr && pm_vec8(t), PM_EINVAL, "%s: bf16 tensors must be 16B aligned with pitch %% 8 == 0 and C %% 8 == 0", who);
-    return PM_OK;
-  }
-};
-// V per-channel fp32 parameters (mean, invstd, gamma, beta, sums)
-template <int V>
-__device__ __forceinline__ void ldp(const float* p, float* v) {
-  if constexpr (V == 4) Elem<float>::ld(p, v);
-  else pm_ld8f(p, v);
-}
-// thread -> (pixel, V channels), f(pixel, channel) a __device__ lambda
-template <typename T, typename F>
-int ew_launch(long pixels, int c, hipStream_t st, const char* name, F f) {
-  if constexpr (Elem<T>::V == 8) {
-    return pm_ew16_launch(pixels, c, st, name, f);
-  } else {      // pm_ew_launch(true, ...) without its scalar twin
-    if (pixels * c == 0) return PM_OK;
-    hipLaunchKernelGGL((pm_ew_kernel<true, F>), dim3(pm_ew_grid(pixels * c / 4)), dim3(256), 0, st, pixels, c, f);
-    return pm_check_launch(name);
-  }
-}
 
 // ---- elementwise expressions ----------------------------------------------------------------------------------------------------------
 // y = (x - mean) * invstd * gamma + beta, evaluated the same way in the forward pass and wherever the backward pass rebuilds the
@@ -111,8 +62,8 @@ struct Plan {
 template <typename T>
 Plan bn_plan(long P, int C) {
   Plan p;
-  p.gpr = Elem<T>::gpr(C);
-  const int RL = 256 / p.gpr, CB = p.gpr * Elem<T>::V;
+  p.gpr = pm_elem<T>::gpr(C);
+  const int RL = 256 / p.gpr, CB = p.gpr * pm_elem<T>::V;
   p.colblocks = pm_cdiv(C, CB);
   const long want = std::max<long>(512, 2048 / std::max<long>(1, p.colblocks));   // narrow tensors (64 channels) need more pixel chunks to fill the GPU
   const long r = std::max<long>((P + want - 1) / want, 64);
@@ -127,7 +78,7 @@ size_t bn_workspace(const pm_tensor* x) {
 // launch(integral_constant<int, GPR>) for the plan's GPR
 template <typename T, typename L>
 void with_gpr(int gpr, L launch) {
-  if constexpr (Elem<T>::V == 8) {
+  if constexpr (pm_elem<T>::V == 8) {
     if (gpr == 8) return launch(std::integral_constant<int, 8>{});
   }
   launch(std::integral_constant<int, 16>{});
@@ -154,7 +105,7 @@ __device__ __forceinline__ void block_reduce_store(const float* s1, const float*
 // partial[blk][c][2] : sum(x - K[c]), sum((x - K[c])^2) over the block's pixel chunk, K = the first pixel (shifted sums: no cancellation)
 template <typename T, int GPR>
 __global__ __launch_bounds__(256) void bn_stats_partial(const T* __restrict__ x, long pitch, long P, int C, int rows, float* __restrict__ part) {
-  constexpr int V = Elem<T>::V;
+  constexpr int V = pm_elem<T>::V;
   const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
   const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
   const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
@@ -163,10 +114,10 @@ __global__ __launch_bounds__(256) void bn_stats_partial(const T* __restrict__ x,
   for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
   if (c < C) {
     float k[V];
-    Elem<T>::ld(x + c, k);
+    pm_elem<T>::ld(x + c, k);
     for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
       float v[V];
-      Elem<T>::ld(x + p * pitch + c, v);
+      pm_elem<T>::ld(x + p * pitch + c, v);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const float d = v[j] - k[j];
@@ -223,7 +174,7 @@ __global__ __launch_bounds__(256) void bn_stats_final(const float* __restrict__ 
   final_sums(part, nb, C, c, lane, s1, s2);
   if (lane != 0 || c >= C) return;
   const double n = (double)P;
-  const float m = (float)((double)Elem<T>::widen(x[c]) + s1 / n), m2 = (float)fmax(s2 - s1 * s1 / n, 0.0);
+  const float m = (float)((double)pm_elem<T>::widen(x[c]) + s1 / n), m2 = (float)fmax(s2 - s1 * s1 / n, 0.0);
   bn_finish<FIN>(c, C, m, m2, (float)n, moments, eps, mean, invstd, running_mean, running_var, momentum);
 }
 
@@ -267,13 +218,13 @@ __global__ __launch_bounds__(256) void bn_partials_final(const float* __restrict
 }
 
 // The incoming gradient of a backward pass: a tensor, or (the stem) what pm_maxpool3x3s2_bwd would have written, gathered per pixel from the gradient of the
-// 3x3 / s2 max pool that followed the activation and its argmax bytes (pm_maxpool_gather4: the same values in the same order), so that the full-resolution
+// 3x3 / s2 max pool that followed the activation and its argmax bytes (pm_maxpool_gather: the same values in the same order), so that the full-resolution
 // gradient is never written.
 template <typename T>
 struct TensorGrad {
   const T* dy;
   long pitch;
-  __device__ __forceinline__ void load(long p, int c, float* d) const { Elem<T>::ld(dy + p * pitch + c, d); }
+  __device__ __forceinline__ void load(long p, int c, float* d) const { pm_elem<T>::ld(dy + p * pitch + c, d); }
 };
 struct PoolGrad {
   const float* dyp;
@@ -282,8 +233,7 @@ struct PoolGrad {
   const uint8_t* arg;
   int H, W, C;
   __device__ __forceinline__ void load(long p, int c, float* d) const {
-    const float4 g = pm_maxpool_gather4(dyp, pitch, Ho, Wo, arg, H, W, C, p, c);
-    d[0] = g.x, d[1] = g.y, d[2] = g.z, d[3] = g.w;
+    pm_maxpool_gather<float, 4>(dyp, pitch, Ho, Wo, arg, H, W, C, p, c, d);
   }
 };
 
@@ -296,7 +246,7 @@ template <typename T, int GPR, int RELU, bool GOUT, typename SRC>
 __global__ __launch_bounds__(256) void bn_bwd_partial(SRC dy, const T* __restrict__ y, long ypitch, const uint8_t* __restrict__ mask, const T* __restrict__ x, long xpitch,
                                                       const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, T* __restrict__ gout, long gpitch, long P, int C, int rows, float* __restrict__ part) {
-  constexpr int V = Elem<T>::V;
+  constexpr int V = pm_elem<T>::V;
   const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
   const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
   const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
@@ -305,14 +255,14 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(SRC dy, const T* __restric
   for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
   if (c < C) {
     float mu[V], is[V], ga[V], be[V];
-    ldp<V>(mean + c, mu), ldp<V>(invstd + c, is);
-    if (RELU == 2) ldp<V>(gamma + c, ga), ldp<V>(beta + c, be);
+    pm_ldp<V>(mean + c, mu), pm_ldp<V>(invstd + c, is);
+    if (RELU == 2) pm_ldp<V>(gamma + c, ga), pm_ldp<V>(beta + c, be);
     for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
       float d[V], v[V], o[V];
       dy.load(p, c, d);
-      Elem<T>::ld(x + p * xpitch + c, v);
+      pm_elem<T>::ld(x + p * xpitch + c, v);
       if (RELU == 1) {
-        Elem<T>::ld(y + p * ypitch + c, o);
+        pm_elem<T>::ld(y + p * ypitch + c, o);
         relu_mask<V>(o, d);
       } else if (RELU == 3) {
         relu_mask_bits<V>(mask[p * (C / V) + c / V], d);
@@ -320,7 +270,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(SRC dy, const T* __restric
         bn_affine<V>(v, mu, is, ga, be, o);
         relu_mask<V>(o, d);
       }
-      if (GOUT) Elem<T>::st(gout + p * gpitch + c, d);
+      if (GOUT) pm_elem<T>::st(gout + p * gpitch + c, d);
 #pragma unroll
       for (int j = 0; j < V; ++j) s1[j] += d[j], s2[j] += d[j] * ((v[j] - mu[j]) * is[j]);
     }
@@ -465,7 +415,7 @@ inline int fixed_grid(long pixels, int c) { const int ppb = 256 / (c / V8); retu
 template <typename T>
 int bn_stats(const char* who, const pm_tensor* x, float* moments, float eps, float* mean, float* invstd, float* running_mean, float* running_var, float momentum,
              void* ws, size_t ws_bytes, hipStream_t st) {
-  if (int e = Elem<T>::check(x, who)) return e;
+  if (int e = pm_elem<T>::check(x, who)) return e;
   PM_REQUIRE(ws && ws_bytes >= bn_workspace<T>(x), PM_EWORKSPACE, "%s: workspace too small", who);
   const long P = pm_pixels(x);
   const int C = x->c;
@@ -492,12 +442,12 @@ int bn_stats(const char* who, const pm_tensor* x, float* moments, float eps, flo
 template <typename T, bool RAFF = false>
 int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const pm_tensor* res, const float* rmean,
              const float* rinvstd, const float* rgamma, const float* rbeta, int relu_on, const pm_tensor* y, uint8_t* mask, hipStream_t st) {
-  constexpr int V = Elem<T>::V;
-  if (int e = Elem<T>::check(x, who)) return e;
-  if (int e = Elem<T>::check(y, who)) return e;
+  constexpr int V = pm_elem<T>::V;
+  if (int e = pm_elem<T>::check(x, who)) return e;
+  if (int e = pm_elem<T>::check(y, who)) return e;
   PM_REQUIRE(pm_same_shape(x, y) && mean && invstd && gamma && beta, PM_EINVAL, "%s: bad args", who);
   if (res) {
-    if (int e = Elem<T>::check(res, who)) return e;
+    if (int e = pm_elem<T>::check(res, who)) return e;
     PM_REQUIRE(pm_same_shape(x, res), PM_EINVAL, "%s: residual shape mismatch", who);
   }
   PM_REQUIRE(!RAFF || (res && rmean && rinvstd && rgamma && rbeta), PM_EINVAL, "%s: bad args", who);
@@ -521,17 +471,17 @@ int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float
       return pm_check_launch(who);
     }
   }
-  return ew_launch<T>(P, x->c, st, who, [=] __device__(long p, int ch) {
+  return pm_ew_launch_as<T>(P, x->c, st, who, [=] __device__(long p, int ch) {
     float v[V], mu[V], is[V], ga[V], be[V], o[V];
-    Elem<T>::ld(px + p * a + ch, v);
-    ldp<V>(mean + ch, mu), ldp<V>(invstd + ch, is), ldp<V>(gamma + ch, ga), ldp<V>(beta + ch, be);
+    pm_elem<T>::ld(px + p * a + ch, v);
+    pm_ldp<V>(mean + ch, mu), pm_ldp<V>(invstd + ch, is), pm_ldp<V>(gamma + ch, ga), pm_ldp<V>(beta + ch, be);
     bn_affine<V>(v, mu, is, ga, be, o);
     if (pr) {
       float q[V];
-      Elem<T>::ld(pr + p * b + ch, q);
+      pm_elem<T>::ld(pr + p * b + ch, q);
       if constexpr (RAFF) {
         float rm[V], ri[V], rg[V], rb[V];
-        ldp<V>(rmean + ch, rm), ldp<V>(rinvstd + ch, ri), ldp<V>(rgamma + ch, rg), ldp<V>(rbeta + ch, rb);
+        pm_ldp<V>(rmean + ch, rm), pm_ldp<V>(rinvstd + ch, ri), pm_ldp<V>(rgamma + ch, rg), pm_ldp<V>(rbeta + ch, rb);
         bn_affine<V>(q, rm, ri, rg, rb, q);
       }
 #pragma unroll
@@ -539,7 +489,7 @@ int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float
     }
     if (mask) mask[p * cg + ch / V] = (unsigned char)positive_bits<V>(o);
     if (relu_on) relu<V>(o);
-    Elem<T>::st(py + p * c + ch, o);
+    pm_elem<T>::st(py + p * c + ch, o);
   });
 }
 
@@ -547,13 +497,13 @@ int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float
 template <typename T, typename SRC>
 int bn_bwd_reduce(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, int relu_mode, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (int e = Elem<T>::check(x, who)) return e;
+  if (int e = pm_elem<T>::check(x, who)) return e;
   PM_REQUIRE(mean && invstd && sums, PM_EINVAL, "%s: bad args", who);
   PM_REQUIRE(relu_mode >= 0 && relu_mode <= 3, PM_EINVAL, "%s: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x, 3 mask bytes)", who, relu_mode);
-  PM_REQUIRE(relu_mode != 1 || (y && Elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
+  PM_REQUIRE(relu_mode != 1 || (y && pm_elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
   PM_REQUIRE(relu_mode != 2 || (gamma && beta), PM_EINVAL, "%s: relu mode 2 needs gamma and beta", who);
   PM_REQUIRE(relu_mode != 3 || mask, PM_EINVAL, "%s: relu mode 3 needs the mask bytes", who);
-  PM_REQUIRE(!gmask || (relu_mode != 0 && Elem<T>::check(gmask, who) == PM_OK && pm_same_shape(gmask, x)), PM_EINVAL, "%s: gmask needs a ReLU mode and the shape of x", who);
+  PM_REQUIRE(!gmask || (relu_mode != 0 && pm_elem<T>::check(gmask, who) == PM_OK && pm_same_shape(gmask, x)), PM_EINVAL, "%s: gmask needs a ReLU mode and the shape of x", who);
   PM_REQUIRE(ws && ws_bytes >= bn_workspace<T>(x), PM_EWORKSPACE, "%s: workspace too small", who);
   const long P = pm_pixels(x);
   const int C = x->c;
@@ -585,17 +535,17 @@ int bn_bwd_reduce(const char* who, SRC dy, const pm_tensor* y, const uint8_t* ma
 template <typename T, int MODE, typename SRC>
 int bn_bwd_apply(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                  const float* beta, const float* sums, float count, int relu_mode, const pm_tensor* dx, const pm_tensor* dres, hipStream_t st) {
-  constexpr int V = Elem<T>::V;
-  if (int e = Elem<T>::check(x, who)) return e;
-  if (int e = Elem<T>::check(dx, who)) return e;
+  constexpr int V = pm_elem<T>::V;
+  if (int e = pm_elem<T>::check(x, who)) return e;
+  if (int e = pm_elem<T>::check(dx, who)) return e;
   PM_REQUIRE(pm_same_shape(dx, x) && mean && invstd && gamma && sums, PM_EINVAL, "%s: bad args", who);
   PM_REQUIRE(pm_aligned16(sums), PM_EINVAL, "%s: sums must be 16-byte aligned (sections of a shared exchange start at multiples of 4 floats)", who);
   if (MODE >= 0) relu_mode = MODE;
   PM_REQUIRE(MODE >= 0 || (relu_mode >= 0 && relu_mode <= 2), PM_EINVAL, "%s: relu mode %d (0 none, 1 mask from y, 2 mask rebuilt from x)", who, relu_mode);
-  PM_REQUIRE(relu_mode != 1 || (y && Elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
+  PM_REQUIRE(relu_mode != 1 || (y && pm_elem<T>::check(y, who) == PM_OK && pm_same_shape(y, x)), PM_EINVAL, "%s: relu mode 1 needs the forward output", who);
   PM_REQUIRE(relu_mode != 2 || beta, PM_EINVAL, "%s: relu mode 2 needs beta", who);
   PM_REQUIRE(relu_mode != 3 || mask, PM_EINVAL, "%s: relu mode 3 needs the mask bytes", who);
-  PM_REQUIRE(!dres || (Elem<T>::check(dres, who) == PM_OK && pm_same_shape(dres, x)), PM_EINVAL, "%s: dres shape mismatch", who);
+  PM_REQUIRE(!dres || (pm_elem<T>::check(dres, who) == PM_OK && pm_same_shape(dres, x)), PM_EINVAL, "%s: dres shape mismatch", who);
   const T *po = relu_mode == 1 ? (const T*)y->ptr : nullptr, *px = (const T*)x->ptr;
   T *pdx = (T*)dx->ptr, *pdr = dres ? (T*)dres->ptr : nullptr;
   const long b = relu_mode == 1 ? y->pitch : 0, c = x->pitch, d = dx->pitch, e2 = dres ? dres->pitch : 0, P = pm_pixels(x);
@@ -615,36 +565,36 @@ int bn_bwd_apply(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mas
       return pm_check_launch(who);
     }
   }
-  return ew_launch<T>(P, C, st, who, [=] __device__(long p, int ch) {
+  return pm_ew_launch_as<T>(P, C, st, who, [=] __device__(long p, int ch) {
     const float inv_n = bn_inv_n(dev_count, sums, C, host_inv_n);
     float g[V], v[V], mu[V], is[V], ga[V], s1[V], s2[V], r[V];
     dy.load(p, ch, g);
     if (MODE < 0 && po) {
       float o[V];
-      Elem<T>::ld(po + p * b + ch, o);
+      pm_elem<T>::ld(po + p * b + ch, o);
       relu_mask<V>(o, g);
     }
     if constexpr (MODE == 3) relu_mask_bits<V>(mask[p * cg + ch / V], g);
-    Elem<T>::ld(px + p * c + ch, v);
-    ldp<V>(mean + ch, mu), ldp<V>(invstd + ch, is), ldp<V>(gamma + ch, ga);
+    pm_elem<T>::ld(px + p * c + ch, v);
+    pm_ldp<V>(mean + ch, mu), pm_ldp<V>(invstd + ch, is), pm_ldp<V>(gamma + ch, ga);
     if (MODE == 2 || (MODE < 0 && from_x)) {
       float be[V], o[V];
-      ldp<V>(beta + ch, be);
+      pm_ldp<V>(beta + ch, be);
       bn_affine<V>(v, mu, is, ga, be, o);
       relu_mask<V>(o, g);
     }
-    if (MODE < 0 && pdr) Elem<T>::st(pdr + p * e2 + ch, g);
-    ldp<V>(sums + ch, s1), ldp<V>(sums + C + ch, s2);
+    if (MODE < 0 && pdr) pm_elem<T>::st(pdr + p * e2 + ch, g);
+    pm_ldp<V>(sums + ch, s1), pm_ldp<V>(sums + C + ch, s2);
 #pragma unroll
     for (int j = 0; j < V; ++j) r[j] = BN_DX(g[j], v[j], mu[j], is[j], s1[j] * inv_n, s2[j] * inv_n, is[j] * ga[j]);
-    Elem<T>::st(pdx + p * d + ch, r);
+    pm_elem<T>::st(pdx + p * d + ch, r);
   });
 }
 
 // the incoming gradient as a tensor of x's type and shape
 template <typename T>
 int tensor_grad(const char* who, const pm_tensor* dy, const pm_tensor* x, TensorGrad<T>* g) {
-  if (int e = Elem<T>::check(dy, who)) return e;
+  if (int e = pm_elem<T>::check(dy, who)) return e;
   PM_REQUIRE(pm_same_shape(dy, x), PM_EINVAL, "%s: dy must have the shape of x", who);
   g->dy = (const T*)dy->ptr, g->pitch = dy->pitch;
   return PM_OK;
@@ -666,8 +616,8 @@ int bn_bwd_apply_tensor(const char* who, const pm_tensor* dy, const pm_tensor* y
 // the stem: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x (fp32)
 int pool_grad(const char* who, const pm_tensor* dyp, const uint8_t* argmax, const pm_tensor* x, PoolGrad* g) {
   PM_REQUIRE(dyp && argmax && x, PM_EINVAL, "%s: null", who);
-  if (int e = Elem<float>::check(dyp, who)) return e;
-  if (int e = Elem<float>::check(x, who)) return e;
+  if (int e = pm_elem<float>::check(dyp, who)) return e;
+  if (int e = pm_elem<float>::check(x, who)) return e;
   PM_REQUIRE(dyp->n == x->n && dyp->c == x->c && dyp->h == (x->h + 2 - 3) / 2 + 1 && dyp->w == (x->w + 2 - 3) / 2 + 1, PM_EINVAL,
              "%s: dy is the gradient of the 3x3 / s2 / p1 max pool of a tensor shaped like x", who);
   *g = PoolGrad{(const float*)dyp->ptr, (long)dyp->pitch, dyp->h, dyp->w, argmax, x->h, x->w, x->c};

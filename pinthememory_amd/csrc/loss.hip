@@ -284,17 +284,6 @@ __global__ __launch_bounds__(CE_FINAL_T) void ce_final_img_kernel(const float* _
   }
 }
 
-__host__ __device__ __forceinline__ void support(float scale, int i, int out, int& lo, int& hi) {   // hi-res indices that can touch low-res index i
-  if (scale <= 0.f) {
-    lo = 0, hi = out - 1;
-    return;
-  }
-  const float inv = 1.f / scale;
-  lo = max(0, (int)floorf(((float)i - 1.f) * inv) - 1);
-  hi = min(out - 1, (int)ceilf(((float)i + 1.f) * inv) + 1);
-}
-__device__ __forceinline__ float tap_weight(const pm_lerp& l, int i) { return (l.i0 == i ? l.w0 : 0.f) + (l.i1 == i ? l.w1 : 0.f); }
-
 // pass 2: thread per (low-res pixel, class): supporting hi-res rows in ascending order, then the loss scale (WT, per_image: the image's own weight sum divides)
 template <bool WT = false>
 __global__ __launch_bounds__(256) void ce_bwd_cols_kernel(const CEGeom g, const float* __restrict__ T, const float* __restrict__ loss_out,
@@ -310,9 +299,9 @@ __global__ __launch_bounds__(256) void ce_bwd_cols_kernel(const CEGeom g, const 
     q /= g.w;
     const int y = (int)(q % g.h), b = (int)(q / g.h);
     int lo, hi;
-    support(g.sy, y, g.H, lo, hi);
+    pm_support(g.sy, y, g.H, lo, hi);
     float acc = 0.f;
-    for (int Y = lo; Y <= hi; ++Y) acc += tap_weight(pm_ac_lerp(g.sy, Y, g.h), y) * T[(((long)b * g.H + Y) * g.w + x) * C + c];
+    for (int Y = lo; Y <= hi; ++Y) acc += pm_tap_weight(pm_ac_lerp(g.sy, Y, g.h), y) * T[(((long)b * g.H + Y) * g.w + x) * C + c];
     if constexpr (WT) {
       const float gsb = g.per_image ? (gscale ? gscale[0] : 1.f) * g.inv_temp / loss_out[2 + b] : gs;
       dl[((long)(b * g.h + y) * g.w + x) * dlp + c] = acc * gsb;

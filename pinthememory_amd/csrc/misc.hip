@@ -1,4 +1,4 @@
-// Error reporting, elementwise helpers, layout edges and the flat-arena SGD step.
+// Error reporting, the elementwise entry points (relu_bwd and scale_shift_act: fp32; add, add_n, copy: both activation tiers), layout edges and the flat-arena SGD step.
 #include <algorithm>
 
 #include "pm_common.h"
@@ -14,98 +14,108 @@ void pm_set_error(const char* fmt, ...) {
 extern "C" const char* pm_last_error(void) { return g_err; }
 extern "C" int pm_version(void) { return PM_ABI_VERSION; }
 
-#define LD4 PM_LD4
-#define ST4 PM_ST4
-#define ew_launch pm_ew_launch
-#define same_shape pm_same_shape
-#define vec4 pm_vec4
-
 extern "C" int pm_relu_bwd(const pm_tensor* dy, const pm_tensor* y, const pm_tensor* dx, void* stream) {
-  PM_REQUIRE(dy && y && dx && same_shape(dy, y) && same_shape(dy, dx), PM_EINVAL, "relu_bwd: shape mismatch");
+  PM_REQUIRE(dy && y && dx && pm_same_shape(dy, y) && pm_same_shape(dy, dx), PM_EINVAL, "relu_bwd: shape mismatch");
   PM_REQUIRE_F32(dy, "relu_bwd"); PM_REQUIRE_F32(y, "relu_bwd"); PM_REQUIRE_F32(dx, "relu_bwd");
   const float *pdy = (const float*)dy->ptr, *py = (const float*)y->ptr;
   float* pdx = (float*)dx->ptr;
   const long a = dy->pitch, b = y->pitch, c = dx->pitch;
-  const bool v = vec4(dy) && vec4(y) && vec4(dx);
+  const bool v = pm_vec4(dy) && pm_vec4(y) && pm_vec4(dx);
   if (v)
-    return ew_launch(true, pm_pixels(dy), dy->c, (hipStream_t)stream, "relu_bwd", [=] __device__(long p, int ch) {
-      float4 g = LD4(pdy + p * a + ch), o = LD4(py + p * b + ch);
+    return pm_ew_launch(true, pm_pixels(dy), dy->c, (hipStream_t)stream, "relu_bwd", [=] __device__(long p, int ch) {
+      float4 g = PM_LD4(pdy + p * a + ch), o = PM_LD4(py + p * b + ch);
       g.x = o.x > 0.f ? g.x : 0.f, g.y = o.y > 0.f ? g.y : 0.f, g.z = o.z > 0.f ? g.z : 0.f, g.w = o.w > 0.f ? g.w : 0.f;
-      ST4(pdx + p * c + ch, g);
+      PM_ST4(pdx + p * c + ch, g);
     });
-  return ew_launch(false, pm_pixels(dy), dy->c, (hipStream_t)stream, "relu_bwd",
-                   [=] __device__(long p, int ch) { pdx[p * c + ch] = py[p * b + ch] > 0.f ? pdy[p * a + ch] : 0.f; });
+  return pm_ew_launch(false, pm_pixels(dy), dy->c, (hipStream_t)stream, "relu_bwd",
+                      [=] __device__(long p, int ch) { pdx[p * c + ch] = py[p * b + ch] > 0.f ? pdy[p * a + ch] : 0.f; });
+}
+
+// ---- add / add_n / copy on both tiers: one body over 16-byte vector views (pm_elem<T>), the element type selected once by the extern "C" function; fp32 views
+// that are no vectors keep their element-by-element forms, a bf16 view has to be a vector view ---------------------------------------------------------------
+namespace {
+// o = x[0] + x[1] + ... + x[n-1] (2 <= n <= 8, same shapes, vector views of any pitches), summed left to right in one pass: the gradient of a
+// tensor with several consumers (the ASPP input feeds five branches) without a chain of two-operand adds
+template <typename T>
+struct AddN {
+  const T* p[8];
+  long pitch[8];
+};
+template <typename T>
+int add_n(const char* who, const pm_tensor* const* xs, int n, const pm_tensor* o, hipStream_t st) {
+  constexpr int V = pm_elem<T>::V;
+  AddN<T> a;
+  for (int i = 0; i < n; ++i) {
+    if constexpr (V == 4) PM_REQUIRE_F32(xs[i], who);      // a bf16 operand of an fp32 sum; an fp32 operand of a bf16 sum is no bf16 vector view (PM_EINVAL)
+    PM_REQUIRE(xs[i] && pm_same_shape(xs[i], o) && pm_elem<T>::vec(xs[i]), PM_EINVAL, "%s: operand %d: shape / 16-byte vector view mismatch", who, i);
+    a.p[i] = (const T*)xs[i]->ptr, a.pitch[i] = xs[i]->pitch;
+  }
+  PM_REQUIRE(pm_elem<T>::vec(o), PM_EINVAL, "%s: output must be a 16-byte vector view", who);
+  T* po = (T*)o->ptr;
+  const long c = o->pitch;
+  return pm_ew_launch_as<T>(pm_pixels(o), o->c, st, who, [=] __device__(long p, int ch) {
+    float s[V];
+    pm_elem<T>::ld(a.p[0] + p * a.pitch[0] + ch, s);
+    for (int i = 1; i < n; ++i) {
+      float v[V];
+      pm_elem<T>::ld(a.p[i] + p * a.pitch[i] + ch, v);
+#pragma unroll
+      for (int e = 0; e < V; ++e) s[e] += v[e];
+    }
+    pm_elem<T>::st(po + p * c + ch, s);
+  });
+}
+// 16 bytes per lane, moved as they are
+template <typename T>
+int copy_vec(const pm_tensor* x, const pm_tensor* o, hipStream_t st) {
+  const T* px = (const T*)x->ptr;
+  T* po = (T*)o->ptr;
+  const long a = x->pitch, c = o->pitch;
+  return pm_ew_launch_as<T>(pm_pixels(x), x->c, st, "copy",
+                            [=] __device__(long p, int ch) { *reinterpret_cast<uint4*>(po + p * c + ch) = *reinterpret_cast<const uint4*>(px + p * a + ch); });
+}
+}  // namespace
+
+extern "C" int pm_add_n(const pm_tensor* const* xs, int n, const pm_tensor* o, void* stream) {
+  PM_REQUIRE(xs && o && n >= 2 && n <= 8, PM_EINVAL, "add_n: 2..8 operands");
+  return pm_is_bf16(o) ? add_n<pm_bf16>("add_n", xs, n, o, (hipStream_t)stream) : add_n<float>("add_n", xs, n, o, (hipStream_t)stream);
 }
 
 extern "C" int pm_add(const pm_tensor* x, const pm_tensor* y, const pm_tensor* o, void* stream) {
-  PM_REQUIRE(x && y && o && same_shape(x, y) && same_shape(x, o), PM_EINVAL, "add: shape mismatch");
-  if (pm_is_bf16(o)) {
-    const pm_tensor* two[2] = {x, y};
-    return pm16_add_n(two, 2, o, (hipStream_t)stream);
-  }
+  PM_REQUIRE(x && y && o && pm_same_shape(x, y) && pm_same_shape(x, o), PM_EINVAL, "add: shape mismatch");
+  const pm_tensor* two[2] = {x, y};
+  if (pm_is_bf16(o)) return add_n<pm_bf16>("add", two, 2, o, (hipStream_t)stream);
   PM_REQUIRE_F32(x, "add"); PM_REQUIRE_F32(y, "add");
+  if (pm_vec4(x) && pm_vec4(y) && pm_vec4(o)) return add_n<float>("add", two, 2, o, (hipStream_t)stream);
   const float *px = (const float*)x->ptr, *py = (const float*)y->ptr;
   float* po = (float*)o->ptr;
   const long a = x->pitch, b = y->pitch, c = o->pitch;
-  if (vec4(x) && vec4(y) && vec4(o))
-    return ew_launch(true, pm_pixels(x), x->c, (hipStream_t)stream, "add", [=] __device__(long p, int ch) {
-      float4 u = LD4(px + p * a + ch), w = LD4(py + p * b + ch);
-      ST4(po + p * c + ch, make_float4(u.x + w.x, u.y + w.y, u.z + w.z, u.w + w.w));
-    });
-  return ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "add",
-                   [=] __device__(long p, int ch) { po[p * c + ch] = px[p * a + ch] + py[p * b + ch]; });
-}
-
-// o = x[0] + x[1] + ... + x[n-1] (2 <= n <= 8, same shapes, float4 views), summed left to right in one pass: the gradient of a
-// tensor with several consumers (the ASPP input feeds five branches) without a chain of two-operand adds
-struct AddN {
-  const float* p[8];
-  long pitch[8];
-};
-extern "C" int pm_add_n(const pm_tensor* const* xs, int n, const pm_tensor* o, void* stream) {
-  PM_REQUIRE(xs && o && n >= 2 && n <= 8, PM_EINVAL, "add_n: 2..8 operands");
-  if (pm_is_bf16(o)) return pm16_add_n(xs, n, o, (hipStream_t)stream);
-  AddN a;
-  for (int i = 0; i < n; ++i) {
-    PM_REQUIRE_F32(xs[i], "add_n");
-    PM_REQUIRE(xs[i] && same_shape(xs[i], o) && vec4(xs[i]), PM_EINVAL, "add_n: operand %d: shape / float4 view mismatch", i);
-    a.p[i] = (const float*)xs[i]->ptr, a.pitch[i] = xs[i]->pitch;
-  }
-  PM_REQUIRE(vec4(o), PM_EINVAL, "add_n: output must be a float4 view");
-  float* po = (float*)o->ptr;
-  const long c = o->pitch;
-  return ew_launch(true, pm_pixels(o), o->c, (hipStream_t)stream, "add_n", [=] __device__(long p, int ch) {
-    float4 s = LD4(a.p[0] + p * a.pitch[0] + ch);
-    for (int i = 1; i < n; ++i) {
-      const float4 v = LD4(a.p[i] + p * a.pitch[i] + ch);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-    ST4(po + p * c + ch, s);
-  });
+  return pm_ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "add", [=] __device__(long p, int ch) { po[p * c + ch] = px[p * a + ch] + py[p * b + ch]; });
 }
 
 extern "C" int pm_copy(const pm_tensor* x, const pm_tensor* o, void* stream) {
-  PM_REQUIRE(x && o && same_shape(x, o), PM_EINVAL, "copy: shape mismatch");
-  if (pm_is_bf16(x) && pm_is_bf16(o)) return pm16_copy(x, o, (hipStream_t)stream);
+  PM_REQUIRE(x && o && pm_same_shape(x, o), PM_EINVAL, "copy: shape mismatch");
+  if (pm_is_bf16(x) && pm_is_bf16(o)) {
+    PM_REQUIRE(pm_vec8(x) && pm_vec8(o), PM_EINVAL, "copy: bf16 tensors need 16-byte views");
+    return copy_vec<pm_bf16>(x, o, (hipStream_t)stream);
+  }
   PM_REQUIRE_F32(x, "copy"); PM_REQUIRE_F32(o, "copy");
+  if (pm_vec4(x) && pm_vec4(o)) return copy_vec<float>(x, o, (hipStream_t)stream);
   const float* px = (const float*)x->ptr;
   float* po = (float*)o->ptr;
   const long a = x->pitch, c = o->pitch;
-  if (vec4(x) && vec4(o))
-    return ew_launch(true, pm_pixels(x), x->c, (hipStream_t)stream, "copy",
-                     [=] __device__(long p, int ch) { ST4(po + p * c + ch, LD4(px + p * a + ch)); });
-  return ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "copy", [=] __device__(long p, int ch) { po[p * c + ch] = px[p * a + ch]; });
+  return pm_ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "copy", [=] __device__(long p, int ch) { po[p * c + ch] = px[p * a + ch]; });
 }
 
 // y = relu?(x*scale[c] + shift[c] + residual?)  -- eval-mode BN fold applied to an existing tensor
 extern "C" int pm_scale_shift_act(const pm_tensor* x, const float* scale, const float* shift, const pm_tensor* res, int relu,
                                   const pm_tensor* o, void* stream) {
-  PM_REQUIRE(x && o && scale && shift && same_shape(x, o) && (!res || same_shape(x, res)), PM_EINVAL, "scale_shift_act: bad args");
+  PM_REQUIRE(x && o && scale && shift && pm_same_shape(x, o) && (!res || pm_same_shape(x, res)), PM_EINVAL, "scale_shift_act: bad args");
   PM_REQUIRE_F32(x, "scale_shift_act"); PM_REQUIRE_F32(o, "scale_shift_act"); PM_REQUIRE_F32(res, "scale_shift_act");
   const float *px = (const float*)x->ptr, *pr = res ? (const float*)res->ptr : nullptr;
   float* po = (float*)o->ptr;
   const long a = x->pitch, b = res ? res->pitch : 0, c = o->pitch;
-  return ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "scale_shift_act", [=] __device__(long p, int ch) {
+  return pm_ew_launch(false, pm_pixels(x), x->c, (hipStream_t)stream, "scale_shift_act", [=] __device__(long p, int ch) {
     float v = px[p * a + ch] * scale[ch] + shift[ch];
     if (pr) v += pr[p * b + ch];
     po[p * c + ch] = relu ? fmaxf(v, 0.f) : v;
@@ -256,12 +266,12 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdBatch tab, floa
 #pragma unroll
       for (int u = 0; u < SGD_CHUNK / 1024; ++u) {
         const long i = i0 + u * 1024 + threadIdx.x * 4;
-        const float4 w = LD4(P + i), g = LD4(G + i), b0 = LD4(Mb + i);
+        const float4 w = PM_LD4(P + i), g = PM_LD4(G + i), b0 = PM_LD4(Mb + i);
         float4 b, o;
         b.x = sgd_buf(mom, b0.x, g.x, wd, w.x), b.y = sgd_buf(mom, b0.y, g.y, wd, w.y), b.z = sgd_buf(mom, b0.z, g.z, wd, w.z), b.w = sgd_buf(mom, b0.w, g.w, wd, w.w);
         o.x = __fmaf_rn(-lr, b.x, w.x), o.y = __fmaf_rn(-lr, b.y, w.y), o.z = __fmaf_rn(-lr, b.z, w.z), o.w = __fmaf_rn(-lr, b.w, w.w);
-        ST4(Mb + i, b);
-        ST4(P + i, o);
+        PM_ST4(Mb + i, b);
+        PM_ST4(P + i, o);
       }
     } else {
       for (long i = i0 + threadIdx.x; i < i1; i += 256) {
@@ -313,7 +323,7 @@ __global__ __launch_bounds__(256) void image_u8_kernel(const uint8_t* __restrict
     const uint8_t* q = img + p * 3;
     // ToTensor: /255 ; Normalize: (x - mean) / std  -- same operation order as torchvision
     const float4 o = make_float4(((float)q[0] / 255.f - m0) / s0, ((float)q[1] / 255.f - m1) / s1, ((float)q[2] / 255.f - m2) / s2, 0.f);
-    ST4(out + p * 4, o);
+    PM_ST4(out + p * 4, o);
   }
 }
 __global__ __launch_bounds__(256) void labels_u8_kernel(const uint8_t* __restrict__ lab, long n, int64_t* __restrict__ out) {

@@ -69,19 +69,9 @@ int pm_bf16_cast_weights_s2(const float* w, int Cout, int kh, int kw, int Cin, i
 int pm_bf16_transpose_taps(const float* x, long pitch, int C, int N, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad, int dil, void* out,
                            hipStream_t st);
 
-// ---- bf16 activation tier (act16.hip): the bf16 forms of the elementwise / pooling / resize entry points; the extern "C" functions dispatch on dtype (BatchNorm: bn.hip) ------
+// ---- bf16 activations (NHWC, pm_tensor.dtype == PM_BF16) ---------------------------------------------------------------------------------------------------------
 typedef unsigned short pm_bf16;
-int pm16_add_n(const pm_tensor* const* xs, int n, const pm_tensor* y, hipStream_t st);
-int pm16_copy(const pm_tensor* x, const pm_tensor* y, hipStream_t st);
-int pm16_maxpool_fwd(const pm_tensor* x, const pm_tensor* y, uint8_t* argmax, hipStream_t st);
-int pm16_maxpool_bwd(const pm_tensor* dy, const uint8_t* argmax, const pm_tensor* dx, hipStream_t st);
-int pm16_gap_fwd(const pm_tensor* x, const pm_tensor* y, hipStream_t st);
-int pm16_gap_bwd(const pm_tensor* dy, const pm_tensor* dx, int accumulate, hipStream_t st);
-int pm16_resize_fwd(const pm_tensor* x, const pm_tensor* y, hipStream_t st);
-int pm16_resize_bwd(const pm_tensor* dy, const pm_tensor* dx, int accumulate, hipStream_t st);
-size_t pm16_resize_bwd_workspace(const pm_tensor* dy, const pm_tensor* dx);
-int pm16_resize_bwd_separable(const pm_tensor* dy, const pm_tensor* dx, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
-// dense conversions used by the convolution entry points for the few mixed-type call sites of the tier (fp32 logits / image next to bf16 activations)
+// dense conversions (bf16.hip) used by the convolution entry points for the few mixed-type call sites of the tier (fp32 logits / image next to bf16 activations)
 int pm16_to_f32(const pm_bf16* x, long pitch, int C, long P, float* out, long out_pitch, hipStream_t st);
 int pm16_pad_rows(const pm_bf16* x, long pitch, int C, int Cp, long P, pm_bf16* out, hipStream_t st);
 
@@ -257,32 +247,6 @@ __device__ __forceinline__ float pm_bn_affine(float v, float mu, float is, float
   return fmaf(v, s, fmaf(-mu, s, be));
 }
 
-// Gradient of input pixel ip (channels ch ... ch + 3) of a 3x3 / stride 2 / pad 1 max pool: the sum, in window order, of dy over the (at most four) windows that
-// cover the pixel and whose argmax byte names this tap. A gather: no atomics, deterministic. Shared by the pool's own backward and by the BatchNorm backward passes
-// that read a pooled gradient (the stem), so both produce the same bits.
-__device__ __forceinline__ float4 pm_maxpool_gather4(const float* __restrict__ dy, long dp, int Ho, int Wo, const uint8_t* __restrict__ arg, int H, int W, int C, long ip,
-                                                     int ch) {
-  const int ix = (int)(ip % W), iy = (int)((ip / W) % H), n = (int)(ip / ((long)W * H));
-  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int oy_hi = min((iy + 1) >> 1, Ho - 1), ox_hi = min((ix + 1) >> 1, Wo - 1);
-  for (int oy = iy >> 1; oy <= oy_hi; ++oy) {
-    const int ky = iy + 1 - 2 * oy;
-    if (ky < 0 || ky > 2) continue;
-    for (int ox = ix >> 1; ox <= ox_hi; ++ox) {
-      const int kx = ix + 1 - 2 * ox;
-      if (kx < 0 || kx > 2) continue;
-      const long op = (long)(n * Ho + oy) * Wo + ox;
-      const unsigned a = *reinterpret_cast<const unsigned*>(arg + op * C + ch), want = (unsigned)(ky * 3 + kx);
-      const float4 d = *reinterpret_cast<const float4*>(dy + op * dp + ch);
-      g.x += (a & 255u) == want ? d.x : 0.f;
-      g.y += ((a >> 8) & 255u) == want ? d.y : 0.f;
-      g.z += ((a >> 16) & 255u) == want ? d.z : 0.f;
-      g.w += (a >> 24) == want ? d.w : 0.f;
-    }
-  }
-  return g;
-}
-
 __device__ __forceinline__ float pm_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -318,6 +282,19 @@ __device__ __forceinline__ pm_lerp pm_ac_lerp(float scale, int dst, int in) {
   r.w0 = 1.f - l1;
   return r;
 }
+
+// The transposed operator (every resize backward pass, and the fused up-sample + loss backward): output indices whose taps may touch input index `i`, a
+// conservative [lo, hi] from the inverse map -- each is verified exactly by pm_tap_weight, the weight output index (lerp l) puts on input index i.
+__device__ __forceinline__ void pm_support(float scale, int i, int out, int& lo, int& hi) {
+  if (scale <= 0.f) {
+    lo = 0, hi = out - 1;
+    return;
+  }
+  const float inv = 1.f / scale;
+  lo = max(0, (int)floorf(((float)i - 1.f) * inv) - 1);
+  hi = min(out - 1, (int)ceilf(((float)i + 1.f) * inv) + 1);
+}
+__device__ __forceinline__ float pm_tap_weight(const pm_lerp& l, int i) { return (l.i0 == i ? l.w0 : 0.f) + (l.i1 == i ? l.w1 : 0.f); }
 
 // ---- generic NHWC elementwise driver: thread -> (pixel, 4 channels) ----------------------------------------------
 // VEC=true needs 16B-aligned views with c % 4 == 0 (pm_vec4). f(pixel, channel) is a __device__ lambda.
@@ -364,4 +341,111 @@ static inline int pm_ew16_launch(long pixels, int c, hipStream_t st, const char*
   const long work = pixels * (c / 8);
   hipLaunchKernelGGL((pm_ew16_kernel<F>), dim3((int)std::min<long>((work + 255) / 256, 256 * 16)), dim3(256), 0, st, pixels, c / 8, f);
   return pm_check_launch(name);
+}
+
+// ---- the element trait: what differs between the fp32 and the bf16 activation tier ---------------------------------------------------------------------------------
+// A lane moves 16 bytes = V channels; values are widened to fp32 in registers and travel as float[V] (every loop over V fully unrolled); bf16 results are rounded
+// (nearest even) once, on the way out. One kernel template over T serves both tiers (bn.hip, pool_resize.hip, misc.hip).
+template <typename T>
+struct pm_elem;
+template <>
+struct pm_elem<float> {
+  static constexpr int V = 4;      // channels per 16-byte lane access
+  static __device__ __forceinline__ void ld(const float* p, float* v) {
+    const float4 a = PM_LD4(p);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+  }
+  static __device__ __forceinline__ void st(float* p, const float* v) { PM_ST4(p, make_float4(v[0], v[1], v[2], v[3])); }
+  static __device__ __forceinline__ float widen(float v) { return v; }
+  static __device__ __forceinline__ float narrow(float v) { return v; }
+  static int gpr(int) { return 16; }      // BatchNorm reductions, lane groups per pixel row: 16 float4 groups x 16 row lanes
+  static bool vec(const pm_tensor* t) { return pm_vec4(t); }
+  static int check(const pm_tensor* t, const char* who) {
+    PM_REQUIRE_F32(t, who);      // a mixed-type call ends here
+    PM_REQUIRE(t && t->ptr && pm_vec4(t), PM_EINVAL, "%s: tensor must be 16B aligned, pitch %% 4 == 0 and C %% 4 == 0", who);
+    return PM_OK;
+  }
+};
+template <>
+struct pm_elem<pm_bf16> {
+  static constexpr int V = 8;
+  static __device__ __forceinline__ void ld(const pm_bf16* p, float* v) { pm_ld8(p, v); }
+  static __device__ __forceinline__ void st(pm_bf16* p, const float* v) { pm_st8(p, v); }
+  static __device__ __forceinline__ float widen(pm_bf16 v) { return pm_bf16_to_f32(v); }
+  static __device__ __forceinline__ pm_bf16 narrow(float v) { return pm_f32_to_bf16(v); }
+  static int gpr(int C) { return C <= 64 ? 8 : 16; }      // 8 for tensors of <= 64 channels: no idle half-waves on the 64-channel maps of layer1
+  static bool vec(const pm_tensor* t) { return pm_vec8(t); }
+  static int check(const pm_tensor* t, const char* who) {
+    PM_REQUIRE(t && t->ptr && pm_vec8(t), PM_EINVAL, "%s: bf16 tensors must be 16B aligned with pitch %% 8 == 0 and C %% 8 == 0", who);
+    return PM_OK;
+  }
+};
+// V channels of a T tensor <-> float[V]: V = pm_elem<T>::V (one 16-byte access) or 1 (the scalar fallbacks of odd fp32 views)
+template <typename T, int V>
+__device__ __forceinline__ void pm_ldv(const T* p, float* v) {
+  if constexpr (V == 1) v[0] = pm_elem<T>::widen(*p);
+  else pm_elem<T>::ld(p, v);
+}
+template <typename T, int V>
+__device__ __forceinline__ void pm_stv(T* p, const float* v) {
+  if constexpr (V == 1) *p = pm_elem<T>::narrow(v[0]);
+  else pm_elem<T>::st(p, v);
+}
+// V per-channel fp32 values (mean, invstd, gamma, beta, sums; the fp32 workspace of the separable resize backward)
+template <int V>
+__device__ __forceinline__ void pm_ldp(const float* p, float* v) {
+  if constexpr (V == 4) pm_elem<float>::ld(p, v);
+  else pm_ld8f(p, v);
+}
+template <int V>
+__device__ __forceinline__ void pm_stp(float* p, const float* v) {
+  pm_elem<float>::st(p, v);
+  if constexpr (V == 8) pm_elem<float>::st(p + 4, v + 4);
+}
+// thread -> (pixel, V channels), f(pixel, channel) a __device__ lambda
+template <typename T, typename F>
+int pm_ew_launch_as(long pixels, int c, hipStream_t st, const char* name, F f) {
+  if constexpr (pm_elem<T>::V == 8) {
+    return pm_ew16_launch(pixels, c, st, name, f);
+  } else {      // pm_ew_launch(true, ...) without its scalar twin
+    if (pixels * c == 0) return PM_OK;
+    hipLaunchKernelGGL((pm_ew_kernel<true, F>), dim3(pm_ew_grid(pixels * c / 4)), dim3(256), 0, st, pixels, c, f);
+    return pm_check_launch(name);
+  }
+}
+// grid of the grid-stride pooling / resize / conversion kernels (256 threads, one work item each per trip)
+static inline int pm_grid_for(long work) { return (int)std::min<long>((work + 255) / 256, 256 * 32); }
+
+// Gradient of input pixel ip (channels ch ... ch + V - 1) of a 3x3 / stride 2 / pad 1 max pool: the sum, in window order, of dy over the (at most four) windows that
+// cover the pixel and whose argmax byte names this tap; the V argmax bytes come as one load. A gather: no atomics, deterministic. The only copy of the window walk:
+// the pool's own backward on both tiers (V = 1: the scalar fallback) and the BatchNorm backward passes that read a pooled gradient (the stem) produce the same bits.
+template <typename T, int V>
+__device__ __forceinline__ void pm_maxpool_gather(const T* __restrict__ dy, long dp, int Ho, int Wo, const uint8_t* __restrict__ arg, int H, int W, int C, long ip, int ch,
+                                                  float* g) {
+  const int ix = (int)(ip % W), iy = (int)((ip / W) % H), n = (int)(ip / ((long)W * H));
+#pragma unroll
+  for (int e = 0; e < V; ++e) g[e] = 0.f;
+  const int oy_hi = min((iy + 1) >> 1, Ho - 1), ox_hi = min((ix + 1) >> 1, Wo - 1);
+  for (int oy = iy >> 1; oy <= oy_hi; ++oy) {
+    const int ky = iy + 1 - 2 * oy;
+    if (ky < 0 || ky > 2) continue;
+    for (int ox = ix >> 1; ox <= ox_hi; ++ox) {
+      const int kx = ix + 1 - 2 * ox;
+      if (kx < 0 || kx > 2) continue;
+      const long op = (long)(n * Ho + oy) * Wo + ox;
+      const uint8_t* ap = arg + op * C + ch;
+      uint2 a = make_uint2(0u, 0u);
+      if constexpr (V == 1) a.x = *ap;
+      else if constexpr (V == 4) a.x = *reinterpret_cast<const unsigned*>(ap);
+      else a = *reinterpret_cast<const uint2*>(ap);
+      const unsigned want = (unsigned)(ky * 3 + kx);
+      float d[V];
+      pm_ldv<T, V>(dy + op * dp + ch, d);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const unsigned b = ((e < 4 ? a.x : a.y) >> (8 * (e & 3))) & 255u;
+        g[e] += b == want ? d[e] : 0.f;
+      }
+    }
+  }
 }

@@ -22,7 +22,7 @@ def _lib():
 # prec 2 falls back to for the call sites it does not cover (3-channel stem, 19-class heads, stride-2 data gradients).
 CONV_PREC = 0
 # Element type of the activations BETWEEN layers. 'bf16' (round 4) = the whole tier: convolutions write bf16, every elementwise / reduction kernel between them
-# (BatchNorm, pooling, resize, adds: csrc/act16.hip) reads and writes bf16 with fp32 arithmetic; the image, the class logits, the losses, the memory module,
+# (BatchNorm: csrc/bn.hip; pooling, resize: csrc/pool_resize.hip; adds, copies: csrc/misc.hip -- one kernel template per pass for both element types) reads and writes bf16 with fp32 arithmetic; the image, the class logits, the losses, the memory module,
 # every statistic and every parameter / parameter gradient stay fp32. 'bf16_operands' = round 2-3's form (fp32 activations, operands cast per convolution).
 ACT_DTYPE = torch.float32
 
@@ -667,11 +667,8 @@ def resize_fwd(x, size, out=None):
     return y
 
 
-RESIZE_SEPARABLE = os.environ.get('PM_RESIZE_SEP', '1') == '1'      # A/B knob: 0 = gather formulation everywhere
-
-
-def resize_bwd(dy, x_shape, separable=None):
-    separable = RESIZE_SEPARABLE if separable is None else separable
+def resize_bwd(dy, x_shape, separable=True):
+    """separable=False: the gather formulation everywhere."""
     dx = new(x_shape, dy, pitch_pad=True)
     lib, dyd, dxd = _lib(), tdesc(dy), tdesc(dx)
     nb = lib.pm_resize_bilinear_bwd_workspace(byref(dyd), byref(dxd)) if separable else 0
