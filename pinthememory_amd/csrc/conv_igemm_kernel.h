@@ -70,13 +70,6 @@ __device__ __forceinline__ float4 bload(__amdgpu_buffer_rsrc_t r, int off) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// XCD-aware bijective remap: consecutive logical ids (which share the A row-panel) land on one XCD's L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
-}
-
 // KM selects how the running K-state of the gather advances by one K-step:
 //   K_FAST  the channel extent is a multiple of BK (and stride 1 for dgrad): a K-slab never straddles a tap, so
 //           (tap, channel) are wave-uniform -> they live in SGPRs and the per-row work is add / compare / select;
@@ -161,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
     }
     by = u % (int)gridDim.y, z = u / (int)gridDim.y;
   } else {
-    lid = xcd_remap(blockIdx.x, ntile), by = blockIdx.y, z = blockIdx.z;
+    lid = pm_xcd_remap(blockIdx.x, ntile), by = blockIdx.y, z = blockIdx.z;
   }
   int tile_m, tile_n;
   if (a.n_group > 0 && a.tiles_n > a.n_group) {

@@ -58,12 +58,7 @@ __device__ __forceinline__ void interp_logits(const CEGeom& g, int b, const pm_l
 
 // Workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MB L2. With block id = hi-res row, every XCD would walk ALL low-res logit rows (the four
 // hi-res rows between two low-res rows sit on four different XCDs): the 22 MB of main-loss logits were fetched 8 x per sweep (counters, round 4: 226 MB read for
-// 60 MB of inputs). Bijective remap: consecutive hi-res rows -> one XCD, so a low-res row pair is fetched into one L2 and re-used there.
-__device__ __forceinline__ int ce_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
-}
+// 60 MB of inputs). Bijective remap (pm_xcd_remap): consecutive hi-res rows -> one XCD, so a low-res row pair is fetched into one L2 and re-used there.
 
 // Block partial: wave sums, then thread 0 adds the waves' sums in wave order: true for that thread alone, with the block's (loss sum, count or weight sum) in lsum and
 // lcnt -- the caller stores them. NW = 4: a block of four waves, one expression; NW = 0: blockDim.x / 64 waves, a loop.
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
   extern __shared__ float L[];
   const int C = C_ > 0 ? C_ : g.C;
   const int CP = C | 1;
-  const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
   float* wsm = nullptr;
   if constexpr (WT) {
@@ -292,7 +287,7 @@ __global__ __launch_bounds__(256) void ce_bwd_cols_kernel(const CEGeom g, const 
   const long total = (long)g.n * g.h * g.w * C;
   const float gs = (gscale ? gscale[0] : 1.f) * g.inv_temp / loss_out[1];
   // consecutive logical blocks (neighbouring low-res rows, which share most of their supporting field rows) on one XCD's L2
-  for (long i = (long)ce_xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+  for (long i = (long)pm_xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int c = (int)(i % C);
     long q = i / C;
     const int x = (int)(q % g.w);
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
   const int C = C_ > 0 ? C_ : g.C;
   const int CP = C | 1;
   const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
-  const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
   float* wsm = nullptr;
   if constexpr (WT) {
@@ -465,7 +460,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   // the column LEFT of the segment -- it evaluates its hi-res pixels only for the right-tap sums B they owe to column c0 (4 % of redundant work at 96 columns per
   // segment; its loss terms and its own row entries belong to the neighbouring segment and are dropped here). Half the columns per block = half the LDS: four
   // resident blocks per CU instead of two.
-  const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int seg = bid % nseg, y = (bid / nseg) % g.h, b = bid / (nseg * g.h);
   const int y1 = min(y + 1, g.h - 1);
   float* wsm = nullptr;
@@ -903,7 +898,7 @@ __global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int r
   __shared__ float sm[EVAL_MAX_ROWS][2][4];
   const int C = C_ > 0 ? C_ : g.C;
   const int CP = C | 1;
-  const int bid = ce_xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int b = bid / chunks, Y0 = (bid - b * chunks) * rows, Y1 = min(g.H, Y0 + rows);
   float* L0 = L;
   float* L1 = L + (size_t)g.w * CP;

@@ -94,10 +94,10 @@ struct pm_conv16 {
   float* stats;              // train-mode BatchNorm statistics of the bf16 output: (mean, M2) per 32-row slab and channel (pm_conv_epilogue.bn_partials), or null
   int bm, bn, tiles_m, tiles_n, ksplit, ksteps_per;      // pm_conv16_plan
   long c_split;
-  int wide;                  // pm_conv16_plan: 1 = a kernel of conv16w.hip takes the call (one block per CU): 256 x 256 two-stage, or the 256 x 128 / 128 x 256 ring (persistent)
+  int wide;                  // pm_conv16_plan: 1 = a wide form takes the call (one block per CU): 256 x 256 two-stage, or the 256 x 128 / 128 x 256 ring (persistent: conv16w.hip)
 };
 void pm_conv16_plan(pm_conv16* k);
-int pm_conv16w_launch(const pm_conv16* k, hipStream_t st);
+int pm_conv16w_launch(const pm_conv16* k, hipStream_t st);      // the persistent plans only; pm_conv16_launch takes every plan and hands these on
 int pm_conv16w_persistent(const pm_conv16* k);      // 1: the plan runs in the persistent producer / consumer form of conv16w.hip
 size_t pm_conv16_slab_bytes(const pm_conv16* k);
 double pm_conv16_executed_fraction(const pm_conv16* k);
@@ -167,6 +167,13 @@ extern pm_routing pm_route;
 
 
 // ---- device helpers -------------------------------------------------------------------------------------------
+// XCD-aware bijective remap of a block id: workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MB L2; consecutive LOGICAL ids (which share an operand
+// panel: the A rows of a GEMM tile row, the low-res logit rows of the fused upsample + CE, the V rows of the fused Winograd) land on one XCD and re-use its L2.
+__device__ __forceinline__ int pm_xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  return base + idx;
+}
 // eight bf16 channels (16 bytes) <-> eight floats. Round to nearest even on the way out (v_cvt_pk_bf16_f32).
 __device__ __forceinline__ void pm_ld8(const pm_bf16* p, float* v) {
   const uint4 q = *reinterpret_cast<const uint4*>(p);

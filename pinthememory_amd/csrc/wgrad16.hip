@@ -12,14 +12,10 @@
 #include <stdlib.h>
 #include <algorithm>
 
-#include "pm_common.h"
+#include "conv16_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 
 namespace {
 
@@ -27,26 +23,10 @@ constexpr int BKP = 64;       // pixels per K-step
 constexpr int NP = 4;         // producer waves
 constexpr int FT = NP * 64;   // fetching threads
 
-__device__ __forceinline__ int xcd_remap_g(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-__device__ __forceinline__ void dma16g(__amdgpu_buffer_rsrc_t r, char* dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm_g() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void ring_barrier_g() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-// stores the compiler's wait bookkeeping does not see (conv16w.hip): the first fragment read of the next unit must not wait for this unit's partial tile
-__device__ __forceinline__ void st16_untracked_g(void* p, u32x4 q) { asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(p), "v"(q) : "memory"); }
-__device__ __forceinline__ void st4_untracked_g(float* p, float v) { asm volatile("global_store_dword %0, %1, off" ::"v"(p), "v"(v) : "memory"); }
+// one unit of work: rows m0 ... of dw (output channels), columns = input channels c0 ... of one tap, pixels p0 ... in `steps` K-steps of 64
+struct wg_unit {
+  int m0, tap, c0, z, p0, steps;
+};
 
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(const pm_wgrad16 a) {
@@ -64,14 +44,16 @@ __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(co
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int ntiles = a.tiles_m * a.tiles_n, total = ntiles * a.ksplit, G = gridDim.x;
   const int cpt = (a.Cin + BN - 1) / BN;      // channel blocks per tap; the last one may be partial (304 / 320 channels): its missing channels are fetched as zeros and not stored
-  auto decode = [&](int v, int& m0, int& tap, int& c0, int& z, int& p0, int& nk) {
-    z = v / ntiles;
-    const int lid = xcd_remap_g(v - z * ntiles, ntiles);
+  auto open = [&](int v) {      // unit v: the ONE place producers and consumers learn how many barriers the unit takes
+    wg_unit u;
+    u.z = v / ntiles;
+    const int lid = pm_xcd_remap(v - u.z * ntiles, ntiles);
     const int tn = lid % a.tiles_n;
-    m0 = (lid / a.tiles_n) * BM;
-    tap = tn / cpt, c0 = (tn - tap * cpt) * BN;
-    p0 = z * a.kper;
-    nk = (min(a.P, p0 + a.kper) - p0 + BKP - 1) / BKP;
+    u.m0 = (lid / a.tiles_n) * BM;
+    u.tap = tn / cpt, u.c0 = (tn - u.tap * cpt) * BN;
+    u.p0 = u.z * a.kper;
+    u.steps = (min(a.P, u.p0 + a.kper) - u.p0 + BKP - 1) / BKP;
+    return u;
   };
 
   if (wave >= 8) {
@@ -79,7 +61,6 @@ __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(co
     const int wave_u = wave - 8, t = wave_u * 64 + lane;
     const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<pm_bf16*>(a.DY), 0, (int)((long)a.P * a.dy_pitch * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<pm_bf16*>(a.X), 0, (int)((long)a.N * a.H * a.W * a.x_pitch * 2), 0x00020000);
-    constexpr int OOB = 0x7fffffff;
     const int dyb = (int)a.dy_pitch * 2, xb = (int)a.x_pitch * 2;
     // fixed per lane: pixel row inside the stage and (swizzled) channel slot of every piece
     int a_row[A_IT], a_col[A_IT], b_row[B_IT], b_src[B_IT], b_col[B_IT];
@@ -97,58 +78,43 @@ __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(co
     int a_off[A_IT];                          // byte offset of (pixel row, cout slot) relative to the step's first pixel, or OOB for couts beyond Cout
     int b_img[B_IT], b_oy[B_IT], b_ox[B_IT];  // output pixel of the piece's row at the current step
     int b_ch = 0, dy0 = 0, dx0 = 0;           // channel byte offset of the tile, tap displacement
-    int pix = 0, pend = 0, left = 0;          // first pixel of the next step, end of the unit's pixel range, steps left
-    int vf = blockIdx.x;
-    auto open_unit = [&]() {
-      for (; vf < total; vf += G) {
-        int m0, tap, c0, z, p0, nk;
-        decode(vf, m0, tap, c0, z, p0, nk);
-        if (nk <= 0) continue;
-        left = nk, pix = p0, pend = min(a.P, p0 + a.kper);
+    int pix = 0, pend = 0;                    // first pixel of the next step, end of the unit's pixel range
+    auto load = [&](const wg_unit& u) {
+      const int m0 = u.m0, tap = u.tap, c0 = u.c0, p0 = u.p0;
+      pix = p0, pend = min(a.P, p0 + a.kper);
 #pragma unroll
-        for (int it = 0; it < A_IT; ++it) a_off[it] = (m0 * 2 + a_col[it] < a.Cout * 2) ? a_row[it] * dyb + m0 * 2 + a_col[it] : OOB;
-        const int ky = tap / a.kw, kx = tap - ky * a.kw;
-        dy0 = ky * a.dil - a.pad, dx0 = kx * a.dil - a.pad;
-        b_ch = c0 * 2;
+      for (int it = 0; it < A_IT; ++it) a_off[it] = (m0 * 2 + a_col[it] < a.Cout * 2) ? a_row[it] * dyb + m0 * 2 + a_col[it] : C16_OOB;
+      const int ky = tap / a.kw, kx = tap - ky * a.kw;
+      dy0 = ky * a.dil - a.pad, dx0 = kx * a.dil - a.pad;
+      b_ch = c0 * 2;
 #pragma unroll
-        for (int it = 0; it < B_IT; ++it) b_col[it] = (c0 * 2 + b_src[it] < a.Cin * 2) ? b_src[it] : -1;      // -1: a channel group beyond Cin (partial last block) reads zeros
-        // one index decomposition per unit (row 0 of the lane), the other pieces step on from it
-        constexpr int RSTEP = FT / B_SL;
-        int p = p0 + b_row[0];
-        int img = p / (a.Ho * a.Wo);
-        const int rem = p - img * (a.Ho * a.Wo);
-        int oy = rem / a.Wo, ox = rem - oy * a.Wo;
+      for (int it = 0; it < B_IT; ++it) b_col[it] = (c0 * 2 + b_src[it] < a.Cin * 2) ? b_src[it] : -1;      // -1: a channel group beyond Cin (partial last block) reads zeros
+      // one index decomposition per unit (row 0 of the lane), the other pieces step on from it
+      constexpr int RSTEP = FT / B_SL;
+      int p = p0 + b_row[0];
+      int img = p / (a.Ho * a.Wo);
+      const int rem = p - img * (a.Ho * a.Wo);
+      int oy = rem / a.Wo, ox = rem - oy * a.Wo;
 #pragma unroll
-        for (int it = 0; it < B_IT; ++it) {
-          b_img[it] = img, b_oy[it] = oy, b_ox[it] = ox;
-          ox += RSTEP;
-          while (ox >= a.Wo) {
-            ox -= a.Wo;
-            if (++oy == a.Ho) oy = 0, ++img;
-          }
+      for (int it = 0; it < B_IT; ++it) {
+        b_img[it] = img, b_oy[it] = oy, b_ox[it] = ox;
+        ox += RSTEP;
+        while (ox >= a.Wo) {
+          ox -= a.Wo;
+          if (++oy == a.Ho) oy = 0, ++img;
         }
-        return;
       }
-      left = 0;
     };
-    int slot = 0;
-    auto issue = [&]() -> int {
-      if (left == 0) {
-        if (vf >= total) return 0;
-        vf += G;
-        open_unit();
-        if (left == 0) return 0;
-      }
-      char* la = lds + slot * STAGE;
+    auto fetch = [&](char* la) {
       char* lb = la + A_BYTES;
       const int s_a = pix * dyb;      // scalar offset of the step's first pixel row (the range check of the descriptor covers the vector offset alone)
 #pragma unroll
-      for (int it = 0; it < A_IT; ++it) dma16g(rA, la + (it * FT + wave_u * 64) * 16, (pix + a_row[it] < pend) ? a_off[it] : OOB, s_a);
+      for (int it = 0; it < A_IT; ++it) dma16(rA, la + (it * FT + wave_u * 64) * 16, (pix + a_row[it] < pend) ? a_off[it] : C16_OOB, s_a);
 #pragma unroll
       for (int it = 0; it < B_IT; ++it) {
         const int iy = b_oy[it] * a.stride + dy0, ix = b_ox[it] * a.stride + dx0;
         const bool ok = ((unsigned)iy < (unsigned)a.H) & ((unsigned)ix < (unsigned)a.W) & (pix + b_row[it] < pend) & (b_col[it] >= 0);
-        dma16g(rB, lb + (it * FT + wave_u * 64) * 16, ok ? ((b_img[it] * a.H + iy) * a.W + ix) * xb + b_ch + b_col[it] : OOB, 0);
+        dma16(rB, lb + (it * FT + wave_u * 64) * 16, ok ? ((b_img[it] * a.H + iy) * a.W + ix) * xb + b_ch + b_col[it] : C16_OOB, 0);
         // this piece's pixel, 64 further on
         b_ox[it] += BKP;
         while (b_ox[it] >= a.Wo) {
@@ -157,29 +123,13 @@ __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(co
         }
       }
       pix += BKP;
-      --left;
-      slot = slot == 2 ? 0 : slot + 1;
-      return 1;
     };
-    open_unit();
-    int ahead = issue();
-    ahead += issue();
-    for (int vc = blockIdx.x; vc < total; vc += G) {      // mirror of the multiplying waves' barrier sequence
-      int m0, tap, c0, z, p0, nk;
-      decode(vc, m0, tap, c0, z, p0, nk);
-      for (int kt = 0; kt < nk; ++kt) {
-        if (ahead >= 2) wait_vm_g<FETCH>();
-        else wait_vm_g<0>();
-        ring_barrier_g();
-        ahead += issue() - 1;
-      }
-      ring_barrier_g();
-    }
+    c16_ring_produce<FETCH, STAGE>(lds, blockIdx.x, total, G, open, load, fetch);
     return;
   }
 
   // ================================================== multiplying waves ==================================================
-  const int wm = wave / WN, wn = wave % WN, l31 = lane & 31, half = lane >> 5;
+  const int wm = wave / WN, wn = wave % WN, half = lane >> 5;
   // transpose reads: within a 16-lane group lane i hands in the address of pixel row (i >> 2), 8-byte column block (i & 3) and receives column i of those four rows
   const int frow = half * 8 + ((lane & 15) >> 2);                      // pixel row inside a 16-pixel block (the second read: + 4)
   const int fcol = (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;      // byte offset inside the 64-byte chunk of the lane's 32-channel group
@@ -195,65 +145,29 @@ __global__ __launch_bounds__((8 + NP) * 64, (8 + NP) / 4) void wgrad16_kernel(co
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
   };
-  int rd = 0;
-  for (int vc = blockIdx.x; vc < total; vc += G) {
-    int m0, tap, c0, z, p0, nk;
-    decode(vc, m0, tap, c0, z, p0, nk);
-    f32x16 acc[TM][TN];
+  f32x16 acc[TM][TN];
+  c16_ring_consume<STAGE>(
+      lds, blockIdx.x, total, G, open, [&](const wg_unit&) { c16_zero(acc); },
+      [&](const char* ls) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int kb = 0; kb < BKP / 16; ++kb) {
+          bf16x8 fa[TM], fb[TN];
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
+          for (int i = 0; i < TM; ++i) fa[i] = frag(ls + kb * 16 * A_ROWB + fa_off[i], A_ROWB);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-    for (int kt = 0; kt < nk; ++kt) {
-      ring_barrier_g();
-      const char* ls = lds + rd * STAGE;
+          for (int j = 0; j < TN; ++j) fb[j] = frag(ls + kb * 16 * B_ROWB + fb_off[j], B_ROWB);
 #pragma unroll
-      for (int kb = 0; kb < BKP / 16; ++kb) {
-        bf16x8 fa[TM], fb[TN];
+          for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = frag(ls + kb * 16 * A_ROWB + fa_off[i], A_ROWB);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fb[j] = frag(ls + kb * 16 * B_ROWB + fb_off[j], B_ROWB);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-      rd = rd == 2 ? 0 : rd + 1;
-    }
-    // ---- epilogue: the fp32 partial tile, 32 x 32 slabs through the ring slot read last (conv16w.hip conv16p_kernel) ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    ring_barrier_g();
-    float* Ws = reinterpret_cast<float*>(lds + (rd == 0 ? 2 : rd - 1) * STAGE) + wave * 32 * LDS_SUB;
-    float* Cf = a.C + (long)z * a.c_split;
-    const long cp = a.Nn;
-    const int rr0 = lane >> 3, cc = (lane & 7) * 4;
-#pragma unroll
-    for (int n = 0; n < TN; ++n) {
-      const int cl = c0 + wn * (BN / WN) + n * 32 + cc;      // channel inside the tap: groups of four, Cin % 8 == 0 -- a group is whole or beyond Cin
-      const int col = tap * a.Cin + cl;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) Ws[((q & 3) + 8 * (q >> 2) + 4 * half) * LDS_SUB + l31] = acc[i][n][q];
-#pragma unroll
-        for (int r0 = 0; r0 < 32; r0 += 8) {
-          const int rr = r0 + rr0;
-          const long row = m0 + wm * (BM / WM) + i * 32 + rr;
-          const float4 v = *reinterpret_cast<const float4*>(Ws + rr * LDS_SUB + cc);
-          if (row >= a.M || cl >= a.Cin) continue;
-          if ((cp & 3) == 0) st16_untracked_g(Cf + row * cp + col, u32x4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)});
-          else {
-            const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) st4_untracked_g(Cf + row * cp + col + k, e[k]);
-          }
+            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
         }
-      }
-    }
-  }
+      },
+      [&](const wg_unit& u, char* slot) {
+        // ---- epilogue: the fp32 partial tile, 32 x 32 slabs through the ring slot read last. Columns = channels inside the tap: groups of four, Cin % 8 == 0 -- a
+        // group is whole or beyond Cin (the partial last channel block), i.e. beyond the tap's last column.
+        c16_store_f32<TM, TN, 32, true>(reinterpret_cast<float*>(slot) + wave * 32 * LDS_SUB, acc, lane, u.m0 + wm * (BM / WM), u.tap * a.Cin + u.c0 + wn * (BN / WN),
+                                        a.C + (long)u.z * a.c_split, a.Nn, a.M, (u.tap + 1) * a.Cin, nullptr, true);
+      });
 }
 
 template <int BM, int BN, int WM, int WN>

@@ -409,16 +409,10 @@ struct WinoFusedArgs {
 constexpr int WF_THREADS = 768, WF_TB = 32, WF_CB = 32, WF_BK = 16, WF_P = 36;
 constexpr size_t WF_LDS = (size_t)WF_P * WF_TB * (WF_CB + 1) * sizeof(float);   // the parked accumulators (152 064 B) >= the operand stage (147 456 B)
 
-__device__ __forceinline__ int wf_xcd_remap(int bid, int nwg) {   // consecutive logical ids (they share the V rows) on one XCD's L2
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
-}
-
 __global__ __launch_bounds__(WF_THREADS) void wino_fused_f4_kernel(const WinoFusedArgs a) {
   extern __shared__ __align__(16) float4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lid = wf_xcd_remap(blockIdx.x, gridDim.x);
+  const int lid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int tb = lid / a.ncb, cb = lid - tb * a.ncb;
   const long tile0 = (long)tb * WF_TB;
   const int co0 = cb * WF_CB;

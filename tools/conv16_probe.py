@@ -1,5 +1,6 @@
 """GPU probe: the bf16 tier's forward convolution on the shapes the LDS-DMA kernel carries (bs=8 768^2: the 48 x 48 maps and two 192 x 192 controls), TFLOP/s per shape.
-Run once per library configuration (PM_C16_NST / PM_C16_BM / PM_C16_HYBRID / PM_CONV16 are read at load time)."""
+Run once per library configuration (PM_LIB: another build of the library; PROBE_CONV16: a pm_set_conv16 route). PROBE_GRADS=1 adds the data gradient and the weight
+gradient of the same shapes (two more lines per shape)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,17 +35,21 @@ tot = 0.0
 for name, n, cin, h, w, cout, k, p, d in SHAPES:
     x = torch.randn(n, h, w, cin, device='cuda').bfloat16()
     wt = torch.randn(cout, k, k, cin, device='cuda') * 0.05
-    fn = lambda: K.conv_fwd(x, wt, 1, p, d)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(10):
-        fn()
-    e.record(); torch.cuda.synchronize()
-    ms = s.elapsed_time(e) / 10
     fl = 2.0 * n * h * w * cout * cin * k * k
-    tot += ms
-    print('%-36s %7.1f GF %7.3f ms %7.1f TF' % (name, fl / 1e9, ms, fl / ms / 1e9), flush=True)
+    calls = [(name, lambda: K.conv_fwd(x, wt, 1, p, d))]
+    if os.environ.get('PROBE_GRADS'):
+        dy = torch.randn(n, h, w, cout, device='cuda').bfloat16()
+        calls += [('  dgrad', lambda: K.conv_bwd_data(dy, wt, (n, h, w, cin), 1, p, d)), ('  wgrad', lambda: K.conv_bwd_weight(x, dy, (cout, k, k, cin), 1, p, d))]
+    for label, fn in calls:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(10):
+            fn()
+        e.record(); torch.cuda.synchronize()
+        ms = s.elapsed_time(e) / 10
+        tot += ms
+        print('%-36s %7.1f GF %7.3f ms %7.1f TF' % (label, fl / 1e9, ms, fl / ms / 1e9), flush=True)
 print('sum %.3f ms' % tot)
