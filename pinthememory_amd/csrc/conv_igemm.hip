@@ -102,46 +102,44 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-int splitk_reduce(const float* ws, int ksplit, long M, long Nn, float* C, long c_pitch, const float* bias, const float* scale, const float* shift,
-                  const float* residual, long res_pitch, int relu, hipStream_t st, bool out16 = false, const unsigned char* res_mask = nullptr) {
+// e: the fused epilogue the reduce applies (bn_partials is not its business). out16: C and e.residual are bf16 tensors (pitches in elements).
+int splitk_reduce(const float* ws, int ksplit, long M, long Nn, float* C, long c_pitch, const pm_conv_epilogue& e, hipStream_t st, bool out16 = false,
+                  const unsigned char* res_mask = nullptr) {
   const long total = M * Nn;
-  PM_REQUIRE(!res_mask || (residual && !out16), PM_EUNSUPPORTED, "splitk_reduce: a masked residual is an fp32 operand");
-  if (out16) {      // bf16 tier: bf16 output / residual, four outputs = 8 bytes per thread
-    PM_REQUIRE((Nn % 4 == 0) && (c_pitch % 4 == 0) && (res_pitch % 4 == 0) && pm_aligned16(ws) && (reinterpret_cast<uintptr_t>(C) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(residual) & 7) == 0 && (!bias || pm_aligned16(bias)) && (!scale || (pm_aligned16(scale) && pm_aligned16(shift))),
-               PM_EUNSUPPORTED, "splitk_reduce(bf16): unaligned output");
-    const long groups = total / 4;
-    const int zl = (ksplit >= 32 && groups < (1 << 18)) ? 16 : (ksplit >= 8 && groups < (1 << 20) ? 4 : 1);
-    const int nb = (int)std::min<long>((groups + 256 / zl - 1) / (256 / zl), 8192);
-    if (zl == 16)
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<16, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
-    else if (zl == 4)
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<4, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
-    else
-      hipLaunchKernelGGL((splitk_reduce_vec_kernel<1, true>), dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
-    return pm_check_launch("splitk_reduce(bf16)");
-  }
-  const bool vec = (Nn % 4 == 0) && (c_pitch % 4 == 0) && (res_pitch % 4 == 0) && pm_aligned16(ws) && pm_aligned16(C) &&
-                   (!bias || pm_aligned16(bias)) && (!scale || (pm_aligned16(scale) && pm_aligned16(shift))) && (!residual || pm_aligned16(residual));
+  PM_REQUIRE(!res_mask || (e.residual && !out16), PM_EUNSUPPORTED, "splitk_reduce: a masked residual is an fp32 operand");
+  // four outputs per thread: rows of C and of the residual in whole groups of 16 bytes (bf16: 8), 16-byte aligned slabs and per-column operands
+  const uintptr_t row_mask = out16 ? 7 : 15;
+  const bool vec = (Nn % 4 == 0) && (c_pitch % 4 == 0) && (e.residual_pitch % 4 == 0) && pm_aligned16(ws) && (reinterpret_cast<uintptr_t>(C) & row_mask) == 0 &&
+                   (reinterpret_cast<uintptr_t>(e.residual) & row_mask) == 0 && (!e.bias || pm_aligned16(e.bias)) && (!e.scale || (pm_aligned16(e.scale) && pm_aligned16(e.shift)));
   if (!vec) {
+    PM_REQUIRE(!out16, PM_EUNSUPPORTED, "splitk_reduce(bf16): unaligned output");
     PM_REQUIRE(!res_mask, PM_EUNSUPPORTED, "splitk_reduce: a masked residual needs 16-byte aligned rows");
     const int nb = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual,
-                       res_pitch, relu);
-  } else {
-    const long groups = total / 4;
-    // enough lanes per output group that the whole GPU has work: small outputs with many slabs take 16 lanes
-    const int zl = (ksplit >= 32 && groups < (1 << 18)) ? 16 : (ksplit >= 8 && groups < (1 << 20) ? 4 : 1);
-    const int gp = 256 / zl;
-    const int nb = (int)std::min<long>((groups + gp - 1) / gp, 8192);
-    if (zl == 16)
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<16>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
-    else if (zl == 4)
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<4>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
-    else
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel<1>, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, bias, scale, shift, residual, res_pitch, relu, res_mask);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, e.bias, e.scale, e.shift, e.residual,
+                       (long)e.residual_pitch, e.relu);
+    return pm_check_launch("splitk_reduce");
   }
-  return pm_check_launch("splitk_reduce");
+  const long groups = total / 4;
+  // enough lanes per output group that the whole GPU has work: small outputs with many slabs take 16 lanes
+  const int zl = (ksplit >= 32 && groups < (1 << 18)) ? 16 : (ksplit >= 8 && groups < (1 << 20) ? 4 : 1);
+  const int gp = 256 / zl;
+  const int nb = (int)std::min<long>((groups + gp - 1) / gp, 8192);
+  auto kernel = out16 ? (zl == 16 ? splitk_reduce_vec_kernel<16, true> : (zl == 4 ? splitk_reduce_vec_kernel<4, true> : splitk_reduce_vec_kernel<1, true>))
+                      : (zl == 16 ? splitk_reduce_vec_kernel<16> : (zl == 4 ? splitk_reduce_vec_kernel<4> : splitk_reduce_vec_kernel<1>));
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, st, ws, ksplit, total, (int)M, (int)Nn, C, c_pitch, e.bias, e.scale, e.shift, e.residual, (long)e.residual_pitch, e.relu,
+                     res_mask);
+  return pm_check_launch(out16 ? "splitk_reduce(bf16)" : "splitk_reduce");
+}
+const pm_conv_epilogue NO_EPILOGUE = {(int64_t)sizeof(pm_conv_epilogue), nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0};
+
+// A planned GEMM, the two ways every caller runs one. A K-split: launch(slab, true) fills the fp32 slabs [ksplit][M][Nn], then the fixed-order reduce writes `out` and
+// applies the epilogue. One split: launch(out, false) writes the output with the fused epilogue itself.
+template <class Launch>
+int run_planned(int ksplit, long M, long Nn, float* slab, float* out, long out_pitch, const pm_conv_epilogue& e, bool out16, const unsigned char* res_mask, hipStream_t st,
+                Launch&& launch) {
+  if (ksplit == 1) return launch(out, false);
+  if (int err = launch(slab, true)) return err;
+  return splitk_reduce(slab, ksplit, M, Nn, out, out_pitch, e, st, out16, res_mask);
 }
 
 // pixel rows per block of the bias-gradient column sum: ~1024 blocks in flight, 64 ... 2048 rows each
@@ -334,17 +332,11 @@ Plan make_plan(int mode, long M, long Nn, long K, bool bf16 = false) {
 template <int MODE, int BM, int BN, int WM, int WN, int KM, int PREC, int NST>
 void launch_nst(const ConvK& k, dim3 grid, size_t smem, hipStream_t st) {
   const size_t ep_bytes = (size_t)4 * 32 * (BN / WN + 4) * sizeof(float);      // staged epilogue: four wave slabs
+  const size_t bytes = std::max(smem / (NST == 1 ? 2 : 1), ep_bytes);
   if constexpr (MODE == MODE_FWD && PREC != 1 && BN >= 64) {
-    if (k.stats) {
-      static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs an explicit opt-in
-      (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>), 160 * 1024);
-      hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>), grid, dim3(256), std::max(smem / (NST == 1 ? 2 : 1), ep_bytes), st, k);
-      return;
-    }
+    if (k.stats) return igemm_launch<conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST, true>>(k, grid, bytes, st);
   }
-  static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>), 160 * 1024);
-  hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>), grid, dim3(256), std::max(smem / (NST == 1 ? 2 : 1), ep_bytes), st, k);
+  igemm_launch<conv_igemm_kernel<MODE, BM, BN, WM, WN, KM, PREC, NST>>(k, grid, bytes, st);
 }
 // LDS stages of the tile kernel: the single-stage variant only where it is used -- fast-path fwd / dgrad with a short reduction per block
 constexpr int NST1_MAX_STEPS = 64;      // longest reduction (in K-steps per block) that takes the single-stage variant
@@ -405,6 +397,15 @@ struct ProfScope {
   }
 };
 
+// the fused epilogue operands of a launch that writes its output itself (ConvK, pm_conv16, pm_gemm_pw)
+template <class K>
+void set_epilogue(K& k, const pm_conv_epilogue& e) {
+  k.bias = e.bias, k.scale = e.scale, k.shift = e.shift, k.residual = e.residual, k.res_pitch = e.residual_pitch, k.relu = e.relu;
+}
+inline void set_epilogue(ConvK& k, const pm_conv_epilogue& e, const unsigned char* res_mask) {
+  set_epilogue(k, e);
+  k.res_mask = res_mask, k.stats = e.bn_partials;
+}
 inline bool split_takes(int mode, const Plan& p, const ConvK& k, int batch) {      // batched launches (the Winograd point products: their output stays in L2) at every K
   return pm_route.split != 0 && p.bn >= 64 && !k.io16 && (batch > 1 || split_k_ok(mode, k.K));
 }
@@ -432,10 +433,11 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   if constexpr (MODE != MODE_WGRAD) {      // short pointwise reductions of the fp32 tier stream wave by wave (pwstream.hip): the split path's arithmetic, no tiles
     if (pm_route.split && (k.prec == 0 || k.prec == 5) && !k.io16 && batch == 1 && p.ksplit == 1 && !k.stats && k.kh * k.kw == 1 && k.stride == 1 && k.pad == 0 && !k.sub) {      // fp32 operands only (prec 1 / 2: bf16-operand forms of the older tier)
       pm_gemm_pw g;
-      g.A = k.A, g.B = k.B, g.C = k.C, g.bias = k.bias, g.scale = k.scale, g.shift = k.shift, g.residual = k.residual, g.res_mask = k.res_mask;
-      g.a_pitch = MODE == MODE_FWD ? k.x_pitch : k.y_pitch, g.c_pitch = k.c_pitch, g.res_pitch = k.res_pitch;
+      g.A = k.A, g.B = k.B, g.C = k.C, g.res_mask = k.res_mask;
+      set_epilogue(g, pm_conv_epilogue{(int64_t)sizeof(pm_conv_epilogue), k.bias, k.scale, k.shift, k.residual, k.res_pitch, k.relu, nullptr, 0});
+      g.a_pitch = MODE == MODE_FWD ? k.x_pitch : k.y_pitch, g.c_pitch = k.c_pitch;
       g.b_sn = MODE == MODE_FWD ? k.K : 1, g.b_sk = MODE == MODE_FWD ? 1 : k.Nn;
-      g.M = k.M, g.Nn = k.Nn, g.K = k.K, g.relu = k.relu;
+      g.M = k.M, g.Nn = k.Nn, g.K = k.K;
       if (pm_pwstream_ok(&g)) {
         prof.rec.bm = 32, prof.rec.bn = 64, prof.rec.km = 4, prof.rec.prec = 5, prof.rec.nst = 0;
         const int e = pm_pwstream_launch(&g, st);
@@ -468,6 +470,17 @@ int launch(const ConvK& k0, const Plan& p, hipStream_t st, int batch = 1, double
   }
   prof.done();
   return pm_check_launch("conv_igemm");
+}
+
+// run_planned on the implicit-GEMM kernel: `k` holds the operands and the geometry; slabs are dense [ksplit][M][Nn], `out` has rows of out_pitch elements (bf16 where k.io16)
+template <int MODE>
+int run_gemm(ConvK& k, const Plan& pl, float* slab, float* out, long out_pitch, const pm_conv_epilogue& e, hipStream_t st, double flops = -1.0,
+             const unsigned char* res_mask = nullptr) {
+  return run_planned(pl.ksplit, k.M, k.Nn, slab, out, out_pitch, e, k.io16 != 0, res_mask, st, [&](float* C, bool slabs) {
+    k.C = C, k.c_pitch = slabs ? k.Nn : out_pitch, k.c_split = slabs ? (long)k.M * k.Nn : 0;
+    if (!slabs) set_epilogue(k, e, res_mask);
+    return launch<MODE>(k, pl, st, 1, flops);
+  });
 }
 
 int check_common(const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p) {
@@ -725,22 +738,13 @@ int conv_bf16(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
       // EXECUTED FLOPs: the K-steps of filter rows that no row of a tile can see are skipped by the kernel (dilated ASPP branches) and are not counted
       const double fl = 2.0 * (double)b.M * (double)b.Nn * (double)T * (double)xin->c * (g_prof_on ? pm_conv16_executed_fraction(&k) : 1.0);
       ProfScope prof(st, k.wide ? 5 : 4, k.bm, k.bn, pm_conv16w_persistent(&k), 5, k.wide ? 3 : (k.ksteps_per == 1 ? 1 : 2), k.M, k.Nn, k.K / 2, 1, k.ksplit, fl);
-      int e;
-      if (k.ksplit > 1) {
-        k.C = slab;
-        e = pm_conv16_launch(&k, st);
-      } else {
-        k.C = yout->ptr;
-        k.bias = e0.bias, k.scale = e0.scale, k.shift = e0.shift, k.residual = e0.residual, k.res_pitch = e0.residual_pitch, k.relu = e0.relu;
-        k.stats = o16 ? e0.bn_partials : nullptr;
-        e = pm_conv16_launch(&k, st);
-      }
-      prof.done();
-      if (e) return e;
-      if (k.ksplit > 1)
-        return splitk_reduce(slab, k.ksplit, b.M, b.Nn, (float*)yout->ptr, (long)yout->pitch, e0.bias, e0.scale, e0.shift, e0.residual, (long)e0.residual_pitch, e0.relu,
-                             st, o16);
-      return PM_OK;
+      return run_planned(k.ksplit, b.M, b.Nn, slab, (float*)yout->ptr, (long)yout->pitch, e0, o16, nullptr, st, [&](float* C, bool slabs) {
+        k.C = C;
+        if (!slabs) set_epilogue(k, e0), k.stats = o16 ? e0.bn_partials : nullptr;
+        const int e = pm_conv16_launch(&k, st);
+        prof.done();
+        return e;
+      });
     }
   }
   const pm_tensor xv = {xb, xin->n, xin->h, xin->w, b.Cp / 2, xpitch16 / 2};   // fp32-typed view: one float = two bf16 channels
@@ -752,16 +756,7 @@ int conv_bf16(const pm_tensor* xin, const float* w, int w_cout, int w_cin, bool 
   k.a_bytes = (unsigned)((size_t)pm_pixels(xin) * xpitch16 * 2), k.b_bytes = (unsigned)((size_t)yout->c * T * b.Cp * 2), k.kmode = K_FAST;
   const double flops = 2.0 * (double)b.M * (double)b.Nn * (double)T * (double)xin->c;
   k.io16 = pm_is_bf16(yout) ? 1 : 0;      // bf16 output (and bf16 residual / skip gradient: the caller checked the types)
-  if (b.pl.ksplit > 1) {
-    k.C = slab, k.c_pitch = b.Nn, k.c_split = b.M * b.Nn;
-    if (int e = launch<MODE_FWD>(k, b.pl, st, 1, flops)) return e;
-    return splitk_reduce(slab, b.pl.ksplit, b.M, b.Nn, (float*)yout->ptr, (long)yout->pitch, e0.bias, e0.scale, e0.shift, e0.residual, (long)e0.residual_pitch,
-                         e0.relu, st, k.io16 != 0);
-  }
-  k.C = (float*)yout->ptr, k.c_pitch = yout->pitch, k.c_split = 0;
-  k.bias = e0.bias, k.scale = e0.scale, k.shift = e0.shift, k.residual = e0.residual, k.res_pitch = e0.residual_pitch, k.relu = e0.relu;
-  k.stats = e0.bn_partials;
-  return launch<MODE_FWD>(k, b.pl, st, 1, flops);
+  return run_gemm<MODE_FWD>(k, b.pl, slab, (float*)yout->ptr, (long)yout->pitch, e0, st, flops);
 }
 inline pm_conv_params dgrad_as_fwd(const pm_conv_params* p) {
   pm_conv_params q = *p;
@@ -845,12 +840,13 @@ int dgrad_s2_bf16(const pm_tensor* dy, const float* w, const pm_tensor* dx, cons
     k.A = (const pm_bf16*)dy->ptr, k.B = (const pm_bf16*)((char*)ws + s.wb_off[cls]);
     void* out = (char*)ws + s.out_off[cls];
     ProfScope prof(st, 4, k.bm, k.bn, 0, 5, k.ksteps_per == 1 ? 1 : 2, k.M, k.Nn, k.K / 2, 1, k.ksplit, 2.0 * (double)k.M * (double)k.Nn * (double)k.K);
-    k.C = k.ksplit > 1 ? (void*)slab : out;
-    const int e = pm_conv16_launch(&k, st);
-    prof.done();
+    const int e = run_planned(k.ksplit, k.M, k.Nn, slab, (float*)out, (long)dx->c, NO_EPILOGUE, false, nullptr, st, [&](float* C, bool) {
+      k.C = C;
+      const int el = pm_conv16_launch(&k, st);
+      prof.done();
+      return el;
+    });
     if (e) return e;
-    if (k.ksplit > 1)
-      if (int e2 = splitk_reduce(slab, k.ksplit, k.M, k.Nn, (float*)out, (long)dx->c, nullptr, nullptr, nullptr, nullptr, 0l, 0, st, false)) return e2;
   }
   return s2_interleave((const float*)((char*)ws + s.out_off[0]), s.class_stride, s.valid, dx, add, st, "dgrad_s2_interleave(native bf16 classes)");
 }
@@ -896,13 +892,7 @@ int conv_wgrad_bf16(const pm_tensor* x, const pm_tensor* dy, float* dw, const pm
   k.M = (int)b.M, k.Nn = (int)b.Nn, k.K = (int)b.Kf;
   k.a_bytes = (unsigned)((size_t)b.M * b.P * 2), k.b_bytes = (unsigned)((size_t)b.Nn * b.P * 2), k.kmode = K_FAST;
   const double flops = 2.0 * (double)b.M * (double)b.Nn * (double)b.P;
-  if (b.pl.ksplit > 1) {
-    k.C = slab, k.c_pitch = b.Nn, k.c_split = b.M * b.Nn;
-    if (int e = launch<MODE_FWD>(k, b.pl, st, 1, flops)) return e;
-    return splitk_reduce(slab, b.pl.ksplit, b.M, b.Nn, dw, b.Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st);
-  }
-  k.C = dw, k.c_pitch = b.Nn, k.c_split = 0;
-  return launch<MODE_FWD>(k, b.pl, st, 1, flops);
+  return run_gemm<MODE_FWD>(k, b.pl, slab, dw, b.Nn, NO_EPILOGUE, st, flops);
 }
 
 void gemm_dims(int which, const pm_tensor* x, const pm_tensor* y, const pm_conv_params* p, long& M, long& Nn, long& K) {
@@ -1091,14 +1081,7 @@ int dgrad_s2_parity(const pm_tensor* dy0, const float* w, const pm_tensor* dx, c
     k.T_eff = c.nky * c.nkx, k.tk_w = c.nkx, k.ky0 = c.ky0, k.kx0 = c.kx0, k.ksy = c.ksy, k.ksx = c.ksx;
     k.sub = 1, k.sub_cy = c.cy, k.sub_cx = c.cx, k.Hc = c.Hc, k.Wc = c.Wc;
     float* out = (float*)((char*)tmp + cls * r.s2p.tmp_bytes);
-    if (pl.ksplit > 1) {
-      k.C = slab, k.c_pitch = dx->c, k.c_split = c.M * dx->c;
-      if (int e = launch<MODE_DGRAD>(k, pl, st)) return e;
-      if (int e = splitk_reduce(slab, pl.ksplit, c.M, dx->c, out, (long)dx->c, nullptr, nullptr, nullptr, nullptr, 0l, 0, st)) return e;
-    } else {
-      k.C = out, k.c_pitch = dx->c, k.c_split = 0;
-      if (int e = launch<MODE_DGRAD>(k, pl, st)) return e;
-    }
+    if (int e = run_gemm<MODE_DGRAD>(k, pl, slab, out, (long)dx->c, NO_EPILOGUE, st)) return e;
   }
   return s2_interleave(tmp, (long)(r.s2p.tmp_bytes / sizeof(float)), r.s2p.valid, dx, add, st, "dgrad_s2_interleave");
 }
@@ -1118,16 +1101,7 @@ int conv_direct(const pm_tensor* x, const pm_tensor* y, const float* w, const pm
   k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
   k.a_bytes = (unsigned)(pm_pixels(xin) * xin->pitch * 4), k.b_bytes = (unsigned)((long)y->c * p->kh * p->kw * x->c * 4);
   k.kmode = (xin->c % BK == 0 && (MODE == MODE_FWD || p->stride == 1)) ? 0 : (xin->c >= BK ? 1 : 2);
-  if (pl.ksplit > 1) {
-    k.C = (float*)ws, k.c_pitch = Nn, k.c_split = M * Nn;
-    if (int err = launch<MODE>(k, pl, st)) return err;
-    return splitk_reduce((const float*)ws, pl.ksplit, M, Nn, (float*)out->ptr, (long)out->pitch, e.bias, e.scale, e.shift, e.residual, (long)e.residual_pitch, e.relu, st, k.io16 != 0,
-                         res_mask);
-  }
-  k.C = (float*)out->ptr, k.c_pitch = out->pitch, k.c_split = 0;
-  k.bias = e.bias, k.scale = e.scale, k.shift = e.shift, k.residual = e.residual, k.res_pitch = e.residual_pitch, k.res_mask = res_mask, k.relu = e.relu;
-  k.stats = e.bn_partials;
-  return launch<MODE>(k, pl, st);
+  return run_gemm<MODE>(k, pl, (float*)ws, (float*)out->ptr, (long)out->pitch, e, st, -1.0, res_mask);
 }
 
 // R_DIRECT_WGRAD. x / dy: the operands as gathered (bf16 where r.native16, else fp32 -- the caller's tensor or its widened copy)
@@ -1136,12 +1110,13 @@ int conv_wgrad_direct(const pm_tensor* x, const pm_tensor* dy, float* dw, const 
   gemm_dims(MODE_WGRAD, x, dy, p, M, Nn, K);
   if (r.w16.use) {
     pm_wgrad16 w16 = r.w16.k;
-    w16.C = w16.ksplit > 1 ? (float*)ws : dw;
     ProfScope prof(st, MODE_WGRAD, w16.bm, w16.bn, 2, 4, 3, M, Nn, K, 1, w16.ksplit, 2.0 * (double)M * (double)Nn * (double)K);
-    const int e = pm_wgrad16_launch(&w16, st);
-    prof.done();
-    if (e || w16.ksplit == 1) return e;
-    return splitk_reduce((const float*)ws, w16.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st);
+    return run_planned(w16.ksplit, M, Nn, (float*)ws, dw, Nn, NO_EPILOGUE, false, nullptr, st, [&](float* C, bool) {
+      w16.C = C;
+      const int e = pm_wgrad16_launch(&w16, st);
+      prof.done();
+      return e;
+    });
   }
   ConvK k;
   fill_geom(k, x, dy, p);
@@ -1156,10 +1131,7 @@ int conv_wgrad_direct(const pm_tensor* x, const pm_tensor* dy, float* dw, const 
   k.A = (const float*)dy->ptr, k.B = (const float*)x->ptr;
   k.M = (int)M, k.Nn = (int)Nn, k.K = (int)K;
   k.a_bytes = (unsigned)(pm_pixels(dy) * dy->pitch * esz), k.b_bytes = (unsigned)(pm_pixels(x) * x->pitch * esz), k.kmode = dy->w >= (r.native16 ? 2 * BK : BK) ? 1 : 2;
-  k.C = r.pl.ksplit > 1 ? (float*)ws : dw, k.c_pitch = Nn, k.c_split = r.pl.ksplit > 1 ? M * Nn : 0;
-  if (int e = launch<MODE_WGRAD>(k, r.pl, st)) return e;
-  if (r.pl.ksplit == 1) return PM_OK;
-  return splitk_reduce((const float*)ws, r.pl.ksplit, M, Nn, dw, (long)Nn, nullptr, nullptr, nullptr, nullptr, 0l, 0, st);
+  return run_gemm<MODE_WGRAD>(k, r.pl, (float*)ws, dw, Nn, NO_EPILOGUE, st);
 }
 
 }  // namespace

@@ -1,53 +1,8 @@
 // The implicit-GEMM convolution kernel template of conv_igemm.hip, in a header so that the split-operand instantiations (PREC 5, conv_split.hip) compile as
-// their own translation unit beside the fp32 / bf16 ones. See conv_igemm.hip for the description of the modes; the kernel parameter block is ConvK.
+// their own translation unit beside the fp32 / bf16 ones. See conv_igemm.hip for the description of the modes. The kernel parameter block ConvK and the pieces the
+// kernel is put together from (tile map, LDS layouts, epilogues) are in conv_igemm_parts.h; here are the gather, the K-group multiply and the three main-loop schedules.
 #pragma once
-#include <stdint.h>
-#include <type_traits>
-
-#include "pm_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// kernel parameter block (global namespace: conv_igemm.hip hands it to the PREC 5 launcher of conv_split.hip)
-struct ConvK {
-  const float* A;
-  const float* B;
-  float* C;
-  int N, H, W, Cin;       // conv input tensor (x / dx)
-  int Ho, Wo, Cout;       // conv output tensor (y / dy)
-  long x_pitch, y_pitch;  // floats between pixels
-  int kh, kw, stride, pad, dil, sshift;
-  int M, Nn, K;           // GEMM extents
-  int ksplit;             // gridDim.z
-  int kper;               // K range per split (multiple of BK)
-  long c_pitch;           // row pitch of C
-  long c_split;           // floats between split-K slabs (ksplit > 1 -> C is the workspace)
-  long a_bs, b_bs, c_bs;  // batched launch (gridDim.y > 1, the 16 Winograd points): floats between consecutive A / B / C operands
-  int tiles_m, tiles_n;
-  unsigned a_bytes, b_bytes;  // extents of the A / B buffers (buffer-descriptor range)
-  int kmode;                  // K_FAST / K_MID / K_SMALL: how the gather's K-state advances (see the kernel)
-  int prec;                   // 0 fp32 MFMA, 1 bf16 MFMA operands (fp32 storage and accumulation)
-  // tap list actually iterated: rows ky0 + ksy*i (i < nky), cols kx0 + ksx*j (j < tk_w); T_eff = nky * tk_w. The full kernel
-  // window for fwd / wgrad / stride-1 dgrad; the parity-matching subset for one input-pixel class of a stride-2 dgrad.
-  int T_eff, tk_w, ky0, kx0, ksy, ksx;
-  int sub, sub_cy, sub_cx, Hc, Wc;  // stride-2 dgrad: this launch covers input pixels (2*py + sub_cy, 2*px + sub_cx) only
-  const float* bias;
-  const float* scale;
-  const float* shift;
-  const float* residual;
-  long res_pitch;
-  const unsigned char* res_mask;   // data gradient, fp32 staged epilogue only, or null: `residual` enters masked -- one byte per float4 group of C, dense [M][Nn / 4] (pm_bn_apply_mask's
-                                   // layout), bit e set = element e of the group is added, clear = it counts as 0 (the skip gradient behind a ReLU, never stored masked)
-  int relu;
-  float* stats;               // train-mode BN statistics of the output: (mean, M2) per 32-row slab and channel, or null
-  int io16;                   // the bf16 tier: C and `residual` are bf16 tensors (pitches in elements); accumulation and the epilogue arithmetic stay fp32
-  int stage_ep;               // 1: epilogue staged through LDS (16-byte row stores); 0: per-element stores (batched launches)
-  int n_group;                // > 0: N tiles are walked in groups of n_group columns (tile order inside a group: M outer, N inner), so that one XCD's co-resident
-                              // blocks cover a squarer patch of the output and the weight columns of the group stay in that XCD's L2 over the whole sweep of M
-  int batch_xcd;              // 1: gridDim.y >= 8 batches are dealt to the XCDs whole (see the kernel); set by the launcher when the counts divide
-  int spl_prio;               // PREC 5: 1 = waves in odd hardware wave slots run at s_setprio 2 (see the kernel), 0 = all equal
-};
+#include "conv_igemm_parts.h"
 
 // conv_split.hip: launches the PREC 5 instantiation of the tile (bm x bn) / K-state mode of `k`, on one LDS stage of smem bytes
 int pm_conv_split_launch(int mode, int bm, int bn, const ConvK& k, unsigned gx, unsigned gy, unsigned gz, size_t smem, hipStream_t st);
@@ -55,19 +10,18 @@ size_t pm_conv_split_stage_bytes(int mode, int bm, int bn);
 
 namespace {
 
-enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
-constexpr int BK = 32;
-constexpr int LDK = 36;  // k-contiguous LDS row stride (floats): 144 B rows -> conflict-free ds_read_b128
-
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-constexpr int OOB = 0x7fffffff;  // any byte offset beyond num_records makes a raw buffer load return zeros
-
-// 16-byte load through a buffer descriptor: out-of-range lanes read 0 without a branch (padding taps, tile edges),
-// and the address is a 32-bit byte offset (half the VALU work of 64-bit pointer arithmetic).
-__device__ __forceinline__ float4 bload(__amdgpu_buffer_rsrc_t r, int off) {
-  const v4f v = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-  return make_float4(v.x, v.y, v.z, v.w);
+// One pixel-window gather, for the A rows of the forward pass (SG = +1: input pixel = window origin + tap displacement) and of the stride-1 data gradient (SG = -1: dy
+// pixel = dx pixel + pad - tap displacement): row i reads base[i] + SG * toff where its pixel (y0[i] + SG * dy, x0[i] + SG * dx) lies inside the hh x ww grid and the
+// tap exists, zeros elsewhere. Branch-free: every lane always issues its loads, invalid ones at offset OOB.
+template <int SG, int N>
+__device__ __forceinline__ void igemm_gather_window(__amdgpu_buffer_rsrc_t rs, const int* base, const int* y0, const int* x0, int dy, int dx, int toff, bool tok, int hh, int ww,
+                                                    v4f* out) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const bool ok = ((unsigned)(y0[i] + SG * dy) < (unsigned)hh) & ((unsigned)(x0[i] + SG * dx) < (unsigned)ww) & tok;
+    const int off = base[i] + SG * toff;
+    out[i] = bload(rs, ok ? off : OOB);
+  }
 }
 
 // KM selects how the running K-state of the gather advances by one K-step:
@@ -79,9 +33,275 @@ __device__ __forceinline__ float4 bload(__amdgpu_buffer_rsrc_t r, int off) {
 //           not depend on the K-step, so it is folded into the row's base offset once and a gather costs ONE add per row (K_FAST: two compares, two adds, a select).
 enum { K_FAST = 0, K_MID = 1, K_SMALL = 2, K_PW = 3 };
 
-// Thread -> tile element mapping (256 threads, g = t & 7, r = t >> 3):
-//   k-contiguous (KC) tiles [rows][LDK]: thread owns k-group g (4 floats) of rows r + 32*i   -> 1 K-state, static rows
-//   m-contiguous (MC) tiles [BK][cols] : thread owns k-row r, column groups (g + 8*j) * 4      -> 1 K-state, static cols
+// ---- gather state, one struct per operand role: init() once per block, load() per K-step (branch-free: every lane always issues its loads, invalid ones at offset
+// OOB), advance() per K-step. g = t & 7, r = t >> 3 come from the kernel. xp4 / yp4: bytes between pixels of the convolution's input / output tensor.
+
+// The (tap, channel) decomposition of the running k of a forward pass / data gradient: wave-uniform (K_FAST / K_PW: SGPRs) or per lane (K_MID / K_SMALL: the k-group
+// g of this thread). Both operands' gathers read it.
+template <int MODE, int KM>
+struct IgemmKState {
+  static constexpr bool FAST = KM == K_FAST || KM == K_PW;
+  int ch = 0, tap = 0, ky = 0, kx = 0;
+  __device__ __forceinline__ void init(const ConvK& a, int k_begin, int g) {
+    const int cdim = (MODE == MODE_FWD) ? a.Cin : a.Cout;
+    if constexpr (FAST) {
+      tap = __builtin_amdgcn_readfirstlane(k_begin / cdim);
+      ch = k_begin - tap * cdim;
+      ky = tap / a.kw;
+      kx = tap - ky * a.kw;
+    } else {
+      const int k = k_begin + g * 4;
+      tap = k / cdim;
+      ch = k - tap * cdim;
+      ky = tap / a.tk_w;
+      kx = tap - ky * a.tk_w;
+    }
+  }
+  __device__ __forceinline__ void advance(const ConvK& a) {
+    const int cdim = (MODE == MODE_FWD) ? a.Cin : a.Cout;
+    ch += BK;
+    if constexpr (FAST) {
+      if (ch >= cdim) {            // uniform branch on SGPRs (scalar unit), never diverges
+        ch = 0;
+        ++tap;
+        if (++kx == a.kw) kx = 0, ++ky;
+      }
+    } else if constexpr (KM == K_SMALL) {
+      while (ch >= cdim) {
+        ch -= cdim;
+        ++tap;
+        if (++kx == a.tk_w) kx = 0, ++ky;
+      }
+    } else {
+      const bool wrap = ch >= cdim;
+      ch -= wrap ? cdim : 0;
+      tap += wrap ? 1 : 0;
+      const bool roww = wrap & (kx + 1 == a.tk_w);
+      kx = roww ? 0 : kx + (wrap ? 1 : 0);
+      ky += roww ? 1 : 0;
+    }
+  }
+};
+
+// A rows of the forward pass (pixels of x) and of the data gradient (pixels of dy): row i of the thread is GEMM row m0 + r + 32 * i. The window entry serves the forward
+// pass and the stride-1 data gradient (igemm_gather_window); K_PW folds a row's validity into its base offset once; the per-lane data gradient (K_MID / K_SMALL,
+// stride 2, parity classes) is the second entry.
+template <int MODE, int BM, int KM>
+struct IgemmPixelGather {
+  static constexpr bool FAST = KM == K_FAST || KM == K_PW, PW = KM == K_PW;
+  static constexpr int N = BM / 32;
+  int base[N], y0[N], x0[N];      // byte offset of the window origin (per-lane data gradient: pixel offset of the image), window origin
+  __device__ __forceinline__ void init(const ConvK& a, int m0, int g, int r, int xp4, int yp4) {
+    const int rh = (MODE == MODE_FWD) ? a.Ho : (a.sub ? a.Hc : a.H), rw = (MODE == MODE_FWD) ? a.Wo : (a.sub ? a.Wc : a.W);
+    const bool pointwise = FAST && a.kh * a.kw == 1 && a.stride == 1 && a.pad == 0 && !a.sub;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int m = m0 + r + 32 * i;
+      int b = 0, y = -(1 << 28), x = -(1 << 28);      // (one store per member and row, behind the branches: stores sunk out of them address the struct dynamically -> scratch)
+      if (PW) {          // the launcher vouches for a pointwise problem: rows beyond M carry an out-of-range base, nothing else is checked per K-step
+        y = x = 0;
+        b = m < a.M ? m * (MODE == MODE_FWD ? xp4 : yp4) + g * 16 : OOB;
+      } else if (pointwise) {   // 1x1 / stride 1 / no padding (and every Winograd GEMM): pixel m of the operand, no index decomposition
+        y = x = m < a.M ? 0 : -(1 << 28);
+        b = m < a.M ? m * (MODE == MODE_FWD ? xp4 : yp4) + (FAST ? g * 16 : 0) : 0;
+      } else if (m < a.M) {
+        const int img = m / (rh * rw), rem = m - img * (rh * rw);
+        const int py = rem / rw, px = rem - py * rw;
+        if constexpr (MODE == MODE_FWD) {
+          y = py * a.stride - a.pad;
+          x = px * a.stride - a.pad;
+          b = (img * a.H * a.W + y * a.W + x) * xp4 + (FAST ? g * 16 : 0);
+        } else {
+          y = (a.sub ? 2 * py + a.sub_cy : py) + a.pad;
+          x = (a.sub ? 2 * px + a.sub_cx : px) + a.pad;
+          b = FAST ? ((img * a.Ho + y) * a.Wo + x) * yp4 + g * 16 : img * a.Ho * a.Wo;
+        }
+      }
+      base[i] = b, y0[i] = y, x0[i] = x;
+    }
+  }
+  __device__ __forceinline__ void load(const ConvK& a, __amdgpu_buffer_rsrc_t rA, const IgemmKState<MODE, KM>& ks, int xp4, int yp4, v4f* ra) const {
+    [[maybe_unused]] const bool tok = ks.tap < a.T_eff;
+    if constexpr (PW) {
+      // wave-uniform offset; a K-step beyond the reduction (the software pipeline's run-ahead) moves every offset out of the descriptor's range: no traffic
+      const unsigned toff = (unsigned)(ks.ch * 4) + (tok ? 0u : 0x80000000u);
+#pragma unroll
+      for (int i = 0; i < N; ++i) ra[i] = bload(rA, (unsigned)base[i] + toff);
+    } else if constexpr (MODE == MODE_FWD) {
+      const int dy = ks.ky * a.dil, dx = ks.kx * a.dil;
+      igemm_gather_window<1, N>(rA, base, y0, x0, dy, dx, (dy * a.W + dx) * xp4 + ks.ch * 4, tok, a.H, a.W, ra);
+    } else if constexpr (FAST) {   // stride 1, Cout % BK == 0: uniform (tap, co0)
+      const int dy = ks.ky * a.dil, dx = ks.kx * a.dil;
+      igemm_gather_window<-1, N>(rA, base, y0, x0, dy, dx, (dy * a.Wo + dx) * yp4 - ks.ch * 4, tok, a.Ho, a.Wo, ra);
+    } else {
+      const int dy = (a.ky0 + a.ksy * ks.ky) * a.dil, dx = (a.kx0 + a.ksx * ks.kx) * a.dil, smask = a.stride - 1;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int ty = y0[i] - dy, tx = x0[i] - dx;
+        const int oy = ty >> a.sshift, ox = tx >> a.sshift;
+        const bool ok = tok & ((ty | tx) >= 0) & (((ty | tx) & smask) == 0) & (oy < a.Ho) & (ox < a.Wo);   // '&': no short-circuit branches
+        const int off = (base[i] + oy * a.Wo + ox) * yp4 + ks.ch * 4;   // computed unconditionally: keeps the loop body branch-free
+        ra[i] = bload(rA, ok ? off : OOB);
+      }
+    }
+  }
+};
+
+// B of the forward pass (weight rows [Cout][K], k contiguous: row n0 + r + 32 * i, k-group g) and of the data gradient (the weights viewed [k][Cin]: k-row r, ci
+// group g + 8 * j). The per-lane data gradient keeps the (tap, co) of its own k-row.
+template <int MODE, int BN, int KM>
+struct IgemmWeightGather {
+  static constexpr bool FAST = KM == K_FAST || KM == K_PW, PW = KM == K_PW;
+  static constexpr int N = BN / 32;
+  int base[N];
+  int co = 0, tap = 0;      // per-lane data gradient: (tap, co) of k-row r
+  __device__ __forceinline__ void init(const ConvK& a, int n0, int k_begin, int g, int r) {
+    if constexpr (MODE == MODE_FWD) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int row = n0 + r + 32 * i;
+        base[i] = row < a.Cout ? row * a.K * 4 + g * 16 : OOB;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const int col = n0 + (g + 8 * j) * 4;
+        base[j] = col < a.Cin ? col * 4 + (FAST ? r * (a.kh * a.kw) * a.Cin * 4 : 0) : OOB;
+      }
+      if constexpr (!FAST) {
+        const int k = k_begin + r;
+        tap = k / a.Cout;
+        co = k - tap * a.Cout;
+      }
+    }
+  }
+  __device__ __forceinline__ void load(const ConvK& a, __amdgpu_buffer_rsrc_t rB, const IgemmKState<MODE, KM>& ks, int kbase, int k_end, int g, int r, v4f* rb) const {
+    const int Treal = a.kh * a.kw;         // tap stride of the KRSC weight layout
+    [[maybe_unused]] const bool tok = ks.tap < a.T_eff;
+    if constexpr (PW) {
+      const unsigned beyond = 0x80000000u;
+      const unsigned off = MODE == MODE_FWD ? (kbase < k_end ? (unsigned)(kbase * 4) : beyond) : (tok ? (unsigned)((ks.ch * Treal + ks.tap) * a.Cin * 4) : beyond);
+#pragma unroll
+      for (int i = 0; i < N; ++i) rb[i] = bload(rB, (unsigned)base[i] + off);
+    } else if constexpr (MODE == MODE_FWD) {
+      const bool kok = FAST ? (kbase < k_end) : (kbase + g * 4 < k_end);
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int off = base[i] + kbase * 4;   // base already carries this thread's k-group (g * 16 bytes)
+        rb[i] = bload(rB, (kok & (base[i] != OOB)) ? off : OOB);
+      }
+    } else {
+      bool rok;
+      int roff;
+      if constexpr (FAST) {
+        rok = tok, roff = (ks.ch * Treal + ks.tap) * a.Cin * 4;
+      } else {
+        rok = (tap < a.T_eff) & (kbase + r < k_end);
+        const int tky = tap / a.tk_w, tkx = tap - tky * a.tk_w;
+        roff = (co * Treal + (a.ky0 + a.ksy * tky) * a.kw + a.kx0 + a.ksx * tkx) * a.Cin * 4;
+      }
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const int off = roff + base[j];
+        rb[j] = bload(rB, (rok & (base[j] != OOB)) ? off : OOB);
+      }
+    }
+  }
+  __device__ __forceinline__ void advance(const ConvK& a) {
+    if constexpr (MODE == MODE_DGRAD && !FAST) {
+      co += BK;
+      if constexpr (KM == K_SMALL) {
+        while (co >= a.Cout) co -= a.Cout, ++tap;
+      } else {
+        const bool wrap = co >= a.Cout;
+        co -= wrap ? a.Cout : 0;
+        tap += wrap ? 1 : 0;
+      }
+    }
+  }
+};
+
+// The weight gradient's pair: A = dy columns (m contiguous: k-row r is output pixel k, channel groups g + 8 * j), B = the x window of that pixel under the tap of
+// column group j. KX pixel rows per thread (PREC 4: r and r + 32, eight bf16 channels per 16-byte gather).
+template <int BM, int BN, int KM, int PREC>
+struct IgemmWgradGather {
+  static constexpr bool NAT16 = PREC == 4;
+  static constexpr int KX = NAT16 ? 2 : 1, BKW = BK * KX, EPL = NAT16 ? 8 : 4, ESZ = NAT16 ? 2 : 4;      // pixel rows, pixels per K-step, elements per gather, bytes per element
+  static constexpr int A_NL = NAT16 ? (BM / 32 + 1) / 2 : BM / 32, B_NL = NAT16 ? (BN / 32 + 1) / 2 : BN / 32;      // 16-byte gathers per thread, tile and pixel row
+  int a_col[A_NL];                           // byte offset of dy channel group j (OOB beyond Cout)
+  int b_base[B_NL], b_dy[B_NL], b_dx[B_NL];  // tap + channel byte offset of column group j, its tap displacement
+  int ox[KX], oy[KX], img[KX];               // output pixel of this thread's k-row(s)
+  __device__ __forceinline__ void init(const ConvK& a, int m0, int n0, int k_begin, int g, int r, int xp4) {
+#pragma unroll
+    for (int j = 0; j < A_NL; ++j) {
+      const int col = m0 + (g + 8 * j) * EPL;
+      a_col[j] = col < a.Cout ? col * ESZ : OOB;
+    }
+#pragma unroll
+    for (int j = 0; j < B_NL; ++j) {
+      const int n = n0 + (g + 8 * j) * EPL;
+      const int tap = n < a.Nn ? n / a.Cin : 0;
+      const int ky = tap / a.kw, kx = tap - ky * a.kw;
+      b_dy[j] = ky * a.dil - a.pad;
+      b_dx[j] = kx * a.dil - a.pad;
+      b_base[j] = n < a.Nn ? (b_dy[j] * a.W + b_dx[j]) * xp4 + (n - tap * a.Cin) * ESZ : OOB;
+    }
+#pragma unroll
+    for (int kk = 0; kk < KX; ++kk) {
+      const int p = k_begin + r + 32 * kk;
+      img[kk] = p / (a.Ho * a.Wo);
+      const int rem = p - img[kk] * (a.Ho * a.Wo);
+      oy[kk] = rem / a.Wo;
+      ox[kk] = rem - oy[kk] * a.Wo;
+    }
+  }
+  __device__ __forceinline__ void load(const ConvK& a, __amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int kbase, int k_end, int r, bool doA, bool doB, int xp4, int yp4,
+                                       v4f* ra, v4f* rb) const {
+#pragma unroll
+    for (int kk = 0; kk < KX; ++kk) {
+      const int p = kbase + r + 32 * kk;
+      const bool pok = p < k_end;
+      const int poff = p * yp4;
+      if (doA)
+#pragma unroll
+      for (int j = 0; j < A_NL; ++j) {
+        const int off = poff + a_col[j];
+        ra[kk * A_NL + j] = bload(rA, (pok & (a_col[j] != OOB)) ? off : OOB);
+      }
+      const int by = oy[kk] * a.stride, bx = ox[kk] * a.stride;
+      const int rowbase = ((img[kk] * a.H + by) * a.W + bx) * xp4;
+      if (doB)
+#pragma unroll
+      for (int j = 0; j < B_NL; ++j) {
+        const bool ok = pok & (b_base[j] != OOB) & ((unsigned)(by + b_dy[j]) < (unsigned)a.H) & ((unsigned)(bx + b_dx[j]) < (unsigned)a.W);
+        const int off = rowbase + b_base[j];
+        rb[kk * B_NL + j] = bload(rB, ok ? off : OOB);
+      }
+    }
+  }
+  __device__ __forceinline__ void advance(const ConvK& a) {
+#pragma unroll
+    for (int kk = 0; kk < KX; ++kk) {
+      ox[kk] += BKW;
+      if constexpr (KM == K_SMALL) {
+        while (ox[kk] >= a.Wo) {
+          ox[kk] -= a.Wo;
+          if (++oy[kk] == a.Ho) oy[kk] = 0, ++img[kk];
+        }
+      } else {      // Wo >= BKW: at most one wrap per step
+        const bool wrap = ox[kk] >= a.Wo;
+        ox[kk] -= wrap ? a.Wo : 0;
+        const bool imgw = wrap & (oy[kk] + 1 == a.Ho);
+        oy[kk] = imgw ? 0 : oy[kk] + (wrap ? 1 : 0);
+        img[kk] += imgw ? 1 : 0;
+      }
+    }
+  }
+};
+
+// Thread -> tile element mapping (256 threads, g = t & 7, r = t >> 3; the LDS layouts of conv_igemm_parts.h):
+//   k-contiguous (KC) tiles: thread owns k-group g (4 floats) of rows r + 32*i   -> 1 K-state, static rows
+//   m-contiguous (MC) tiles: thread owns k-row r, column groups (g + 8*j) * 4      -> 1 K-state, static cols
 // PREC 0: operands stay fp32 -> v_mfma_f32_32x32x2_f32 (exact fp32 FMA chain, 157 TF). PREC 1: the fp32 tiles staged in LDS are
 // rounded to bf16 (RNE, v_cvt_pk_bf16_f32) as the fragments are read -> v_mfma_f32_32x32x16_bf16 with fp32 accumulation (2.5 PF):
 // BASELINE configs[2]. Gathers, LDS layout and epilogue are shared; storage stays fp32.
@@ -93,8 +313,6 @@ template <int MODE, int BM, int BN, int WM, int WN, int KM, int PREC, int NST, b
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
   constexpr bool A_KC = (MODE != MODE_WGRAD);  // A tile stored [BM][LDK] (k contiguous) else [BK][BM]
   constexpr bool B_KC = (MODE == MODE_FWD);    // B tile stored [BN][LDK] else [BK][BN]
-  constexpr bool FAST = (KM == K_FAST || KM == K_PW) && (MODE != MODE_WGRAD);
-  constexpr bool PW = (KM == K_PW) && (MODE != MODE_WGRAD);
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   // PREC 3 (weight gradient of the bf16 tier): the pixel-major (m-contiguous) tiles are kept in LDS as bf16 [BK][BM + 32] -- rounded once, as the
   // gathered fp32 rows are stored -- and the MFMA fragments (8 consecutive k per lane) come out of them through the hardware transpose read
@@ -109,16 +327,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
   // lo hi; the dropped mid lo + lo mid + lo lo are <= 3 * 2^-24 of |a b|) on v_mfma_f32_32x32x16_bf16 into the same fp32 accumulators: 6 / 16 of the fp32 MFMA's
   // matrix-pipe cycles per K-step. Measured against fp64 (tools/micro/split_gemm.hip): the same error class as the fp32 fma chain of PREC 0.
   constexpr bool SPL = (PREC == 5);
-  constexpr int LD5 = 52;      // floats per k-contiguous row: [hi | mid | lo] x 32 k x 2 B + 16 B -> 13 sixteen-byte granules per row: conflict-free ds_read_b128
   // K-step of this instantiation. PREC 4 takes 64 pixels per step (a thread gathers two pixel rows, r and r + 32): the bf16 MFMA phase of a 32-pixel step is 256
   // cycles per wave -- too short for one barrier pair and one round of address arithmetic; the forward kernels' steps are 64 deep as well (round 4: 465 -> see DESIGN)
   constexpr int KX = NAT16 ? 2 : 1, BKW = BK * KX;
   static_assert(!TR || MODE == MODE_WGRAD, "PREC 3 / 4 are the weight-gradient forms");
-  constexpr int LDA_T = BM + 32, LDB_T = BN + 32;   // bf16 elements per k-row
-  constexpr int PLANE_A = BK * LDA_T / 2, PLANE_B = BK * LDB_T / 2;   // PREC 5, m-contiguous operands: floats per bf16 plane [BK][m + 32]
-  constexpr int A_FLOATS = SPL ? (A_KC ? BM * LD5 : 3 * PLANE_A) : (A_KC ? BM * LDK : (TR ? BKW * LDA_T / 2 : BK * BM));
-  constexpr int B_FLOATS = SPL ? (B_KC ? BN * LD5 : 3 * PLANE_B) : (B_KC ? BN * LDK : (TR ? BKW * LDB_T / 2 : BK * BN));
-  constexpr int STAGE = A_FLOATS + B_FLOATS;
+  using LA = LdsTile<PREC, A_KC, BM>;      // the LDS layout of each operand's tile
+  using LB = LdsTile<PREC, B_KC, BN>;
+  constexpr int A_FLOATS = LA::FLOATS, STAGE = A_FLOATS + LB::FLOATS;
   constexpr int A_N = BM / 32, B_N = BN / 32;  // float4 per thread and tile
   static_assert(WM * WN == 4 && TM >= 1 && TN >= 1 && BK == 32, "bad tile config");
 
@@ -136,341 +351,48 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
   const int half = lane >> 5, l31 = lane & 31;
   const int g = t & 7, r = t >> 3;
 
-  const int ntile = a.tiles_m * a.tiles_n;
-  // Batched / split-K launches (the 36 / 16 point GEMMs of a Winograd layer; the K slices of a weight gradient): whole (batch, K-slice) units go to one XCD (unit u -> XCD
-  // u mod 8; a remainder of 1 / 2 / 4 units is cut into 8 / 4 / 2 runs of tiles), so that both operands of a unit pass through ONE L2 instead of the weight tile of a
-  // point (the activation rows of a K slice) being fetched by every XCD that holds a few of its tiles. The linear workgroup id is dealt round-robin to the XCDs
-  // (MI355X_MICROARCH.md "Workgroup dispatch"); a wrong guess costs locality only.
-  int lid, by, z;
-  if (a.batch_xcd) {
-    const int L = blockIdx.x + ntile * (blockIdx.y + gridDim.y * blockIdx.z), xcd = L & 7, idx = L >> 3;
-    const int units = (int)(gridDim.y * gridDim.z), whole = units >> 3, rem = units & 7;
-    int u;
-    if (idx < whole * ntile) {
-      u = xcd + 8 * (idx / ntile), lid = idx % ntile;
-    } else {
-      const int share = 8 / rem, per = ntile / share;
-      u = whole * 8 + xcd / share, lid = (xcd % share) * per + (idx - whole * ntile);
-    }
-    by = u % (int)gridDim.y, z = u / (int)gridDim.y;
-  } else {
-    lid = pm_xcd_remap(blockIdx.x, ntile), by = blockIdx.y, z = blockIdx.z;
-  }
-  int tile_m, tile_n;
-  if (a.n_group > 0 && a.tiles_n > a.n_group) {
-    const int gsz = a.tiles_m * a.n_group, grp = lid / gsz, rem = lid - grp * gsz;
-    const int gw = min(a.n_group, a.tiles_n - grp * a.n_group);      // the last group may be narrower
-    tile_m = rem / gw, tile_n = grp * a.n_group + rem % gw;
-  } else {
-    tile_m = lid / a.tiles_n, tile_n = lid % a.tiles_n;
-  }
+  int tile_m, tile_n, by, z;
+  igemm_tile_map(a, a.tiles_m * a.tiles_n, tile_m, tile_n, by, z);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int k_begin = z * a.kper;
   const int k_end = min(a.K, k_begin + a.kper);
   const int nk = (k_end - k_begin + BKW - 1) / BKW;
-  const int T = a.T_eff;                 // taps iterated by this launch
-  const int Treal = a.kh * a.kw;         // tap stride of the KRSC weight layout
 
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A + by * a.a_bs), 0, (int)a.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.B + by * a.b_bs), 0, (int)a.b_bytes, 0x00020000);
   const int xp4 = (int)a.x_pitch * (NAT16 ? 2 : 4), yp4 = (int)a.y_pitch * (NAT16 ? 2 : 4);      // bytes between pixels
   constexpr int A_NL = NAT16 ? (A_N + 1) / 2 : A_N, B_NL = NAT16 ? (B_N + 1) / 2 : B_N;            // 16-byte gathers per thread and tile
-  constexpr int EPL = NAT16 ? 8 : 4;                                                               // elements per 16-byte gather
 
-  // ---- gather state ---------------------------------------------------------------------------------------------
-  // uniform K-state (FAST) / per-lane K-state (MID, SMALL) of the (tap, channel) decomposition of k
-  int u_ch = 0, u_tap = 0, u_ky = 0, u_kx = 0;     // FAST: wave-uniform (SGPR)
-  int a_ch = 0, a_tap = 0, a_ky = 0, a_kx = 0;     // MID/SMALL FWD+DGRAD A
-  int b_co = 0, b_tap = 0;                         // MID/SMALL DGRAD B row (tap, co)
-  int p_ox = 0, p_oy = 0, p_img = 0;               // WGRAD B: output pixel of this thread's k-row
-  int q_ox = 0, q_oy = 0, q_img = 0;               // ... and of its second k-row (r + 32) when the K-step is 64 pixels (KX == 2)
-  // static per-item constants
-  int a_base[A_N], a_y0[A_N], a_x0[A_N];           // FWD/DGRAD A rows: byte offset of the window origin, window origin
-  int a_col4[A_N];                                 // WGRAD A: byte offset of dy channel group j (OOB beyond Cout)
-  int b_base[B_N];                                 // FWD: weight-row byte offset; DGRAD: ci group byte offset; WGRAD: tap+channel offset
-  int b_dy[B_N], b_dx[B_N];                        // WGRAD B: tap displacement of column group j
-
-  if constexpr (MODE == MODE_FWD || MODE == MODE_DGRAD) {
-    const int rh = (MODE == MODE_FWD) ? a.Ho : (a.sub ? a.Hc : a.H), rw = (MODE == MODE_FWD) ? a.Wo : (a.sub ? a.Wc : a.W);
-    const int cdim = (MODE == MODE_FWD) ? a.Cin : a.Cout;
-    const bool pointwise = FAST && a.kh * a.kw == 1 && a.stride == 1 && a.pad == 0 && !a.sub;
-#pragma unroll
-    for (int i = 0; i < A_N; ++i) {
-      const int m = m0 + r + 32 * i;
-      if (PW) {          // the launcher vouches for a pointwise problem: rows beyond M carry an out-of-range base, nothing else is checked per K-step
-        a_y0[i] = a_x0[i] = 0;
-        a_base[i] = m < a.M ? m * (MODE == MODE_FWD ? xp4 : yp4) + g * 16 : OOB;
-      } else if (pointwise) {   // 1x1 / stride 1 / no padding (and every Winograd GEMM): pixel m of the operand, no index decomposition
-        a_y0[i] = a_x0[i] = m < a.M ? 0 : -(1 << 28);
-        a_base[i] = m < a.M ? m * (MODE == MODE_FWD ? xp4 : yp4) + (FAST ? g * 16 : 0) : 0;
-      } else if (m < a.M) {
-        const int img = m / (rh * rw), rem = m - img * (rh * rw);
-        const int py = rem / rw, px = rem - py * rw;
-        if constexpr (MODE == MODE_FWD) {
-          a_y0[i] = py * a.stride - a.pad;
-          a_x0[i] = px * a.stride - a.pad;
-          a_base[i] = (img * a.H * a.W + a_y0[i] * a.W + a_x0[i]) * xp4 + (FAST ? g * 16 : 0);
-        } else {
-          a_y0[i] = (a.sub ? 2 * py + a.sub_cy : py) + a.pad;
-          a_x0[i] = (a.sub ? 2 * px + a.sub_cx : px) + a.pad;
-          a_base[i] = FAST ? ((img * a.Ho + a_y0[i]) * a.Wo + a_x0[i]) * yp4 + g * 16 : img * a.Ho * a.Wo;
-        }
-      } else {
-        a_base[i] = 0;
-        a_y0[i] = -(1 << 28);
-        a_x0[i] = -(1 << 28);
-      }
-    }
-    if constexpr (FAST) {
-      u_tap = __builtin_amdgcn_readfirstlane(k_begin / cdim);
-      u_ch = k_begin - u_tap * cdim;
-      u_ky = u_tap / a.kw;
-      u_kx = u_tap - u_ky * a.kw;
-    } else {
-      const int k = k_begin + g * 4;
-      a_tap = k / cdim;
-      a_ch = k - a_tap * cdim;
-      a_ky = a_tap / a.tk_w;
-      a_kx = a_tap - a_ky * a.tk_w;
-    }
+  // the gathers of this instantiation (the unused role's state is never touched and folds away)
+  IgemmKState<MODE, KM> ks;
+  IgemmPixelGather<MODE, BM, KM> ga;
+  IgemmWeightGather<MODE, BN, KM> gb;
+  IgemmWgradGather<BM, BN, KM, PREC> gw;
+  if constexpr (MODE != MODE_WGRAD) {
+    ga.init(a, m0, g, r, xp4, yp4);
+    ks.init(a, k_begin, g);
+    gb.init(a, n0, k_begin, g, r);
   } else {
-#pragma unroll
-    for (int j = 0; j < A_NL; ++j) {
-      const int col = m0 + (g + 8 * j) * EPL;
-      a_col4[j] = col < a.Cout ? col * (NAT16 ? 2 : 4) : OOB;
-    }
+    gw.init(a, m0, n0, k_begin, g, r, xp4);
   }
-  if constexpr (MODE == MODE_FWD) {
-#pragma unroll
-    for (int i = 0; i < B_N; ++i) {
-      const int row = n0 + r + 32 * i;
-      b_base[i] = row < a.Cout ? row * a.K * 4 + g * 16 : OOB;
-    }
-  } else if constexpr (MODE == MODE_DGRAD) {
-#pragma unroll
-    for (int j = 0; j < B_N; ++j) {
-      const int col = n0 + (g + 8 * j) * 4;
-      b_base[j] = col < a.Cin ? col * 4 + (FAST ? r * Treal * a.Cin * 4 : 0) : OOB;
-    }
-    if constexpr (!FAST) {
-      const int k = k_begin + r;
-      b_tap = k / a.Cout;
-      b_co = k - b_tap * a.Cout;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < B_NL; ++j) {
-      const int n = n0 + (g + 8 * j) * EPL;
-      const int tap = n < a.Nn ? n / a.Cin : 0;
-      const int ky = tap / a.kw, kx = tap - ky * a.kw;
-      b_dy[j] = ky * a.dil - a.pad;
-      b_dx[j] = kx * a.dil - a.pad;
-      b_base[j] = n < a.Nn ? (b_dy[j] * a.W + b_dx[j]) * xp4 + (n - tap * a.Cin) * (NAT16 ? 2 : 4) : OOB;
-    }
-    const int p = k_begin + r;
-    p_img = p / (a.Ho * a.Wo);
-    const int rem = p - p_img * (a.Ho * a.Wo);
-    p_oy = rem / a.Wo;
-    p_ox = rem - p_oy * a.Wo;
-    if constexpr (KX == 2) {
-      const int q = p + 32;
-      q_img = q / (a.Ho * a.Wo);
-      const int rq = q - q_img * (a.Ho * a.Wo);
-      q_oy = rq / a.Wo;
-      q_ox = rq - q_oy * a.Wo;
-    }
-  }
-
-  float4 ra[A_N], rb[B_N];
-
-  auto load_tiles = [&](int kt, int which = 0) {   // branch-free: every lane always issues its loads, invalid ones at offset OOB. which: 0 both operands, 1 A only, 2 B only
+  v4f ra[A_N], rb[B_N];
+  auto load_tiles = [&](int kt, int which = 0) {   // which: 0 both operands, 1 A only, 2 B only
     const int kbase = k_begin + kt * BKW;
-    const bool doA = which != 2, doB = which != 1;
-    if constexpr (PW) {
-      // wave-uniform offsets; a K-step beyond the reduction (the software pipeline's run-ahead) moves every offset out of the descriptor's range: no traffic
-      const unsigned beyond = 0x80000000u;
-      const bool tok = u_tap < T;
-      if constexpr (MODE == MODE_FWD) {
-        const unsigned toff = (unsigned)(u_ch * 4) + (tok ? 0u : beyond), kb4 = kbase < k_end ? (unsigned)(kbase * 4) : beyond;
-        if (doA)
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) ra[i] = bload(rA, (int)((unsigned)a_base[i] + toff));
-        if (doB)
-#pragma unroll
-        for (int i = 0; i < B_N; ++i) rb[i] = bload(rB, (int)((unsigned)b_base[i] + kb4));
-      } else {
-        const unsigned toff = (unsigned)(u_ch * 4) + (tok ? 0u : beyond), uoff = tok ? (unsigned)((u_ch * Treal + u_tap) * a.Cin * 4) : beyond;
-        if (doA)
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) ra[i] = bload(rA, (int)((unsigned)a_base[i] + toff));
-        if (doB)
-#pragma unroll
-        for (int j = 0; j < B_N; ++j) rb[j] = bload(rB, (int)((unsigned)b_base[j] + uoff));
-      }
-    } else if constexpr (MODE == MODE_FWD) {
-      const int ky = FAST ? u_ky : a_ky, kx = FAST ? u_kx : a_kx, tap = FAST ? u_tap : a_tap, ch = FAST ? u_ch : a_ch;
-      const int dy = ky * a.dil, dx = kx * a.dil;
-      const int toff = (dy * a.W + dx) * xp4 + ch * 4;
-      const bool tok = tap < T;
-      if (doA)
-#pragma unroll
-      for (int i = 0; i < A_N; ++i) {
-        const bool ok = ((unsigned)(a_y0[i] + dy) < (unsigned)a.H) & ((unsigned)(a_x0[i] + dx) < (unsigned)a.W) & tok;
-        const int off = a_base[i] + toff;
-        ra[i] = bload(rA, ok ? off : OOB);
-      }
-      const bool kok = FAST ? (kbase < k_end) : (kbase + g * 4 < k_end);
-      if (doB)
-#pragma unroll
-      for (int i = 0; i < B_N; ++i) {
-        const int off = b_base[i] + kbase * 4;   // b_base already carries this thread's k-group (g * 16 bytes)
-        rb[i] = bload(rB, (kok & (b_base[i] != OOB)) ? off : OOB);
-      }
-    } else if constexpr (MODE == MODE_DGRAD) {
-      if constexpr (FAST) {   // stride 1, Cout % BK == 0: uniform (tap, co0)
-        const int dy = u_ky * a.dil, dx = u_kx * a.dil;
-        const int toff = (dy * a.Wo + dx) * yp4 - u_ch * 4;
-        const bool tok = u_tap < T;
-        if (doA)
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) {
-          const bool ok = ((unsigned)(a_y0[i] - dy) < (unsigned)a.Ho) & ((unsigned)(a_x0[i] - dx) < (unsigned)a.Wo) & tok;
-          const int off = a_base[i] - toff;
-          ra[i] = bload(rA, ok ? off : OOB);
-        }
-        const int uoff = (u_ch * Treal + u_tap) * a.Cin * 4;
-        if (doB)
-#pragma unroll
-        for (int j = 0; j < B_N; ++j) {
-          const int off = b_base[j] + uoff;
-          rb[j] = bload(rB, (tok & (b_base[j] != OOB)) ? off : OOB);
-        }
-      } else {
-        const int dy = (a.ky0 + a.ksy * a_ky) * a.dil, dx = (a.kx0 + a.ksx * a_kx) * a.dil, smask = a.stride - 1;
-        const bool kok = a_tap < T;
-        if (doA)
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) {
-          const int ty = a_y0[i] - dy, tx = a_x0[i] - dx;
-          const int oy = ty >> a.sshift, ox = tx >> a.sshift;
-          const bool ok = kok & ((ty | tx) >= 0) & (((ty | tx) & smask) == 0) & (oy < a.Ho) & (ox < a.Wo);   // '&': no short-circuit branches
-          const int off = (a_base[i] + oy * a.Wo + ox) * yp4 + a_ch * 4;   // computed unconditionally: keeps the loop body branch-free
-          ra[i] = bload(rA, ok ? off : OOB);
-        }
-        const bool rok = (b_tap < T) & (kbase + r < k_end);
-        const int b_tky = b_tap / a.tk_w, b_tkx = b_tap - b_tky * a.tk_w;
-        const int roff = (b_co * Treal + (a.ky0 + a.ksy * b_tky) * a.kw + a.kx0 + a.ksx * b_tkx) * a.Cin * 4;
-        if (doB)
-#pragma unroll
-        for (int j = 0; j < B_N; ++j) {
-          const int off = roff + b_base[j];
-          rb[j] = bload(rB, (rok & (b_base[j] != OOB)) ? off : OOB);
-        }
-      }
+    if constexpr (MODE != MODE_WGRAD) {
+      if (which != 2) ga.load(a, rA, ks, xp4, yp4, ra);
+      if (which != 1) gb.load(a, rB, ks, kbase, k_end, g, r, rb);
     } else {
-#pragma unroll
-      for (int kk = 0; kk < KX; ++kk) {      // KX == 2: the thread's second pixel row, 32 further on
-        const int p = kbase + r + 32 * kk;
-        const bool pok = p < k_end;
-        const int poff = p * yp4;
-        if (doA)
-#pragma unroll
-        for (int j = 0; j < A_NL; ++j) {
-          const int off = poff + a_col4[j];
-          ra[kk * A_NL + j] = bload(rA, (pok & (a_col4[j] != OOB)) ? off : OOB);
-        }
-        const int by = (kk ? q_oy : p_oy) * a.stride, bx = (kk ? q_ox : p_ox) * a.stride;
-        const int rowbase = (((kk ? q_img : p_img) * a.H + by) * a.W + bx) * xp4;
-        if (doB)
-#pragma unroll
-        for (int j = 0; j < B_NL; ++j) {
-          const bool ok = pok & (b_base[j] != OOB) & ((unsigned)(by + b_dy[j]) < (unsigned)a.H) & ((unsigned)(bx + b_dx[j]) < (unsigned)a.W);
-          const int off = rowbase + b_base[j];
-          rb[kk * B_NL + j] = bload(rB, ok ? off : OOB);
-        }
-      }
+      gw.load(a, rA, rB, kbase, k_end, r, which != 2, which != 1, xp4, yp4, ra, rb);
     }
   };
-
-  auto advance = [&]() {  // move the K-state one K-step (BK) forward
-    if constexpr (MODE == MODE_FWD || MODE == MODE_DGRAD) {
-      const int cdim = (MODE == MODE_FWD) ? a.Cin : a.Cout;
-      if constexpr (FAST) {
-        u_ch += BK;
-        if (u_ch >= cdim) {            // uniform branch on SGPRs (scalar unit), never diverges
-          u_ch = 0;
-          ++u_tap;
-          if (++u_kx == a.kw) u_kx = 0, ++u_ky;
-        }
-      } else {
-        a_ch += BK;
-        if constexpr (KM == K_SMALL) {
-          while (a_ch >= cdim) {
-            a_ch -= cdim;
-            ++a_tap;
-            if (++a_kx == a.tk_w) a_kx = 0, ++a_ky;
-          }
-        } else {
-          const bool wrap = a_ch >= cdim;
-          a_ch -= wrap ? cdim : 0;
-          a_tap += wrap ? 1 : 0;
-          const bool roww = wrap & (a_kx + 1 == a.tk_w);
-          a_kx = roww ? 0 : a_kx + (wrap ? 1 : 0);
-          a_ky += roww ? 1 : 0;
-        }
-        if constexpr (MODE == MODE_DGRAD) {
-          b_co += BK;
-          if constexpr (KM == K_SMALL) {
-            while (b_co >= a.Cout) b_co -= a.Cout, ++b_tap;
-          } else {
-            const bool wrap = b_co >= a.Cout;
-            b_co -= wrap ? a.Cout : 0;
-            b_tap += wrap ? 1 : 0;
-          }
-        }
-      }
-    } else {
-      auto step = [&](int& ox, int& oy, int& img) {
-        ox += BKW;
-        if constexpr (KM == K_SMALL) {
-          while (ox >= a.Wo) {
-            ox -= a.Wo;
-            if (++oy == a.Ho) oy = 0, ++img;
-          }
-        } else {      // Wo >= BKW: at most one wrap per step
-          const bool wrap = ox >= a.Wo;
-          ox -= wrap ? a.Wo : 0;
-          const bool imgw = wrap & (oy + 1 == a.Ho);
-          oy = imgw ? 0 : oy + (wrap ? 1 : 0);
-          img += imgw ? 1 : 0;
-        }
-      };
-      step(p_ox, p_oy, p_img);
-      if constexpr (KX == 2) step(q_ox, q_oy, q_img);
-    }
+  auto advance = [&]() {  // move the K-state one K-step forward
+    if constexpr (MODE != MODE_WGRAD) ks.advance(a), gb.advance(a);
+    else gw.advance(a);
   };
 
-  auto pack4 = [](const float4& v) {   // four fp32 -> four bf16 (RNE), 8 bytes
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 o;
-    o[0] = (__bf16)v.x, o[1] = (__bf16)v.y, o[2] = (__bf16)v.z, o[3] = (__bf16)v.w;
-    return __builtin_bit_cast(float2, o);
-  };
-  auto split4 = [](const float4& v, float2& h, float2& m, float2& l) {   // four fp32 -> 3 x four bf16 (truncation split, exact): 16 VALU + 6 v_perm_b32
-    const unsigned u0 = __float_as_uint(v.x), u1 = __float_as_uint(v.y), u2 = __float_as_uint(v.z), u3 = __float_as_uint(v.w);
-    h.x = __uint_as_float(__builtin_amdgcn_perm(u1, u0, 0x07060302)), h.y = __uint_as_float(__builtin_amdgcn_perm(u3, u2, 0x07060302));
-    const float r0 = v.x - __uint_as_float(u0 & 0xffff0000u), r1 = v.y - __uint_as_float(u1 & 0xffff0000u);
-    const float r2 = v.z - __uint_as_float(u2 & 0xffff0000u), r3 = v.w - __uint_as_float(u3 & 0xffff0000u);
-    const unsigned q0 = __float_as_uint(r0), q1 = __float_as_uint(r1), q2 = __float_as_uint(r2), q3 = __float_as_uint(r3);
-    m.x = __uint_as_float(__builtin_amdgcn_perm(q1, q0, 0x07060302)), m.y = __uint_as_float(__builtin_amdgcn_perm(q3, q2, 0x07060302));
-    const float s0 = r0 - __uint_as_float(q0 & 0xffff0000u), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-    const float s2 = r2 - __uint_as_float(q2 & 0xffff0000u), s3 = r3 - __uint_as_float(q3 & 0xffff0000u);
-    l.x = __uint_as_float(__builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302));
-    l.y = __uint_as_float(__builtin_amdgcn_perm(__float_as_uint(s3), __float_as_uint(s2), 0x07060302));
-  };
   // PREC 5: the split pieces of the gathered rows wait in registers (sa / sb) between the split -- interleaved with the MFMAs of the running K-step -- and the
   // LDS write behind the barrier
-  float2 sa[SPL ? A_N : 1][3], sb[SPL ? B_N : 1][3];
+  uint2 sa[SPL ? A_N : 1][3], sb[SPL ? B_N : 1][3];
   auto split_a = [&]() {
     if constexpr (SPL) {
 #pragma unroll
@@ -486,63 +408,21 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
   auto write_planes = [&](int buf) {
     if constexpr (SPL) {
       float* As = smem + buf * STAGE;
-      float* Bs = As + A_FLOATS;
 #pragma unroll
-      for (int i = 0; i < A_N; ++i) {
-        if constexpr (A_KC) {
-          float* d = As + (r + 32 * i) * LD5 + g * 2;
-          *reinterpret_cast<float2*>(d) = sa[i][0], *reinterpret_cast<float2*>(d + 16) = sa[i][1], *reinterpret_cast<float2*>(d + 32) = sa[i][2];
-        } else {
-          float* d = As + (r * LDA_T + (g + 8 * i) * 4) / 2;
-          *reinterpret_cast<float2*>(d) = sa[i][0], *reinterpret_cast<float2*>(d + PLANE_A) = sa[i][1], *reinterpret_cast<float2*>(d + 2 * PLANE_A) = sa[i][2];
-        }
-      }
+      for (int i = 0; i < A_N; ++i) LA::store(As, r, g, i, sa[i]);
 #pragma unroll
-      for (int i = 0; i < B_N; ++i) {
-        if constexpr (B_KC) {
-          float* d = Bs + (r + 32 * i) * LD5 + g * 2;
-          *reinterpret_cast<float2*>(d) = sb[i][0], *reinterpret_cast<float2*>(d + 16) = sb[i][1], *reinterpret_cast<float2*>(d + 32) = sb[i][2];
-        } else {
-          float* d = Bs + (r * LDB_T + (g + 8 * i) * 4) / 2;
-          *reinterpret_cast<float2*>(d) = sb[i][0], *reinterpret_cast<float2*>(d + PLANE_B) = sb[i][1], *reinterpret_cast<float2*>(d + 2 * PLANE_B) = sb[i][2];
-        }
-      }
+      for (int i = 0; i < B_N; ++i) LB::store(As + A_FLOATS, r, g, i, sb[i]);
     }
   };
   auto store_tiles = [&](int buf) {
     float* As = smem + buf * STAGE;
-    float* Bs = As + A_FLOATS;
     if constexpr (SPL) {
       split_a();
       split_b();
       write_planes(buf);
-      return;
-    }
-    if constexpr (NAT16) {      // two pixel rows per thread (r, r + 32), 16 bytes = eight channels per gather, stored as they are
-#pragma unroll
-      for (int kk = 0; kk < KX; ++kk) {
-#pragma unroll
-        for (int i = 0; i < A_NL; ++i)
-          *reinterpret_cast<float4*>(reinterpret_cast<char*>(As) + ((r + 32 * kk) * LDA_T + (g + 8 * i) * 8) * 2) = ra[kk * A_NL + i];
-#pragma unroll
-        for (int i = 0; i < B_NL; ++i)
-          *reinterpret_cast<float4*>(reinterpret_cast<char*>(Bs) + ((r + 32 * kk) * LDB_T + (g + 8 * i) * 8) * 2) = rb[kk * B_NL + i];
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < A_NL; ++i) {
-      if constexpr (A_KC) *reinterpret_cast<float4*>(As + (r + 32 * i) * LDK + g * 4) = ra[i];
-      else if constexpr (NAT16) *reinterpret_cast<float4*>(reinterpret_cast<char*>(As) + (r * LDA_T + (g + 8 * i) * 8) * 2) = ra[i];
-      else if constexpr (TR) *reinterpret_cast<float2*>(reinterpret_cast<char*>(As) + (r * LDA_T + (g + 8 * i) * 4) * 2) = pack4(ra[i]);
-      else *reinterpret_cast<float4*>(As + r * BM + (g + 8 * i) * 4) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B_NL; ++i) {
-      if constexpr (B_KC) *reinterpret_cast<float4*>(Bs + (r + 32 * i) * LDK + g * 4) = rb[i];
-      else if constexpr (NAT16) *reinterpret_cast<float4*>(reinterpret_cast<char*>(Bs) + (r * LDB_T + (g + 8 * i) * 8) * 2) = rb[i];
-      else if constexpr (TR) *reinterpret_cast<float2*>(reinterpret_cast<char*>(Bs) + (r * LDB_T + (g + 8 * i) * 4) * 2) = pack4(rb[i]);
-      else *reinterpret_cast<float4*>(Bs + r * BN + (g + 8 * i) * 4) = rb[i];
+    } else {
+      lds_store_operand<PREC, A_KC, BM, A_NL>(As, r, g, ra);
+      lds_store_operand<PREC, B_KC, BN, B_NL>(As + A_FLOATS, r, g, rb);
     }
   };
 
@@ -562,22 +442,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
       // (i & 3) * 4 and receives column i of those four rows (tools/micro/tr_probe.hip) -- four consecutive k of its own m. Two reads = the lane's
       // eight k of v_mfma_f32_32x32x16_bf16 (lanes 32..63: the upper eight k of the 16-k block).
       if (kg & 1) return;                                   // two 16-k blocks per slab, issued on the even groups
-      typedef short s16x4 __attribute__((ext_vector_type(4)));
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
       const int krow = (kg >> 1) * 16 + half * 8 + ((lane & 15) >> 2);
       const int cofs = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-      auto frag = [&](const float* T, int ld, int col0) {
-        const short* base = reinterpret_cast<const short*>(T) + krow * ld + col0 + cofs;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * ld));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, v);
-      };
       bf16x8 fa[TM], fb[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = frag(As, LDA_T, wm * (BM / WM) + i * 32);
+      for (int i = 0; i < TM; ++i) fa[i] = LA::frag(As, krow, wm * (BM / WM) + i * 32 + cofs);
 #pragma unroll
-      for (int i = 0; i < TN; ++i) fb[i] = frag(Bs, LDB_T, wn * (BN / WN) + i * 32);
+      for (int i = 0; i < TN; ++i) fb[i] = LB::frag(Bs, krow, wn * (BN / WN) + i * 32 + cofs);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -585,30 +456,19 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
           acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[n], acc[i][n], 0, 0, 0);
     } else if constexpr (SPL) {
       if (kg & 1) return;                                   // two 16-k blocks per slab, issued on the even groups
-      typedef short s16x4 __attribute__((ext_vector_type(4)));
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
       const int krow = (kg >> 1) * 16 + half * 8 + ((lane & 15) >> 2);
       const int cofs = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-      auto frag_t = [&](const float* T, int ld, int col0) {      // m-contiguous plane [BK][ld] of bf16: the hardware transpose read, as PREC 3
-        const short* base = reinterpret_cast<const short*>(T) + krow * ld + col0 + cofs;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * ld));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, v);
-      };
       const int kk = (kg >> 1) * 8 + half * 4;              // float offset of this lane-half's eight bf16 k inside a 64-byte plane row
       bf16x8 fa[3][TM], fb[3][TN];
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-          if constexpr (A_KC) fa[p][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const float4*>(As + (wm * (BM / WM) + i * 32 + l31) * LD5 + p * 16 + kk));
-          else fa[p][i] = frag_t(As + p * PLANE_A, LDA_T, wm * (BM / WM) + i * 32);
+          fa[p][i] = LA::frag(As, p, wm * (BM / WM) + i * 32 + l31, kk, krow, wm * (BM / WM) + i * 32 + cofs);      // k-contiguous rows take (row, kk), planes (krow, column)
         }
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
-          if constexpr (B_KC) fb[p][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const float4*>(Bs + (wn * (BN / WN) + i * 32 + l31) * LD5 + p * 16 + kk));
-          else fb[p][i] = frag_t(Bs + p * PLANE_B, LDB_T, wn * (BN / WN) + i * 32);
+          fb[p][i] = LB::frag(Bs, p, wn * (BN / WN) + i * 32 + l31, kk, krow, wn * (BN / WN) + i * 32 + cofs);
         }
       }
 #define PM_SPL_PROD(PA, PB)                                                                                  \
@@ -802,80 +662,41 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
   }
 
   // ---- epilogue -------------------------------------------------------------------------------------------------
-  // row form: a lane holds one output column and 16 rows of it (the MFMA's native C layout)
+  // Split-K slabs are plain fp32 whatever the tier. Otherwise: the staged form for every output of 16-byte row segments (bf16: eight columns per lane, fp32: four),
+  // the per-element form for the rest -- batched launches (stage_ep == 0), the 19 class logits, a bf16 residual that is a channel slice off a 16-byte boundary
+  // (pm_conv_fwd does not constrain the residual's pitch or alignment, so the C ABI admits that call).
   float* Cb = a.C + by * a.c_bs + (a.ksplit > 1 ? (long)z * a.c_split : 0);
   const bool plain = a.ksplit > 1 || !(a.bias || a.scale || a.residual || a.relu);
-  const bool full = m0 + BM <= a.M && n0 + BN <= a.Nn;
+  const bool aff = !plain && (a.bias || a.scale), res = !plain && a.residual, relu = !plain && a.relu;
   const int rbase = m0 + wm * (BM / WM) + 4 * half, cbase = n0 + wn * (BN / WN) + l31;
-  // Staged form (every 16-byte-aligned output): each wave parks 32 rows of its tile in LDS (the A / B stages are dead by now) and
-  // stores WHOLE row segments -- (BN / WN) / 4 lanes per row, 16 bytes per lane, full 128-byte lines -- instead of 16 four-byte stores
-  // per MFMA tile and lane. A finished tile is bound by the ISSUE of its stores, not by bandwidth: 64 -> 16 store instructions per
-  // lane and 128 x 128 tile (tools/micro/gemm_lab.hip: +4 ... +18 % on the store-heavy shapes, never slower). The fused epilogue
-  // operands are read as 16-byte vectors of the same row segments; values and their evaluation order are unchanged.
-  // The bf16 tier (a.io16, split-K slabs excepted: they stay fp32): the same staging, a lane owns EIGHT columns of a row -- two 16-byte LDS reads, the fused
-  // epilogue in fp32, one 16-byte store of eight bf16 (round to nearest even); the residual / skip-gradient operand is bf16 as well.
-  const bool out16 = a.io16 && a.ksplit == 1;
-  if (out16 && ((a.c_pitch | a.Nn | (a.residual ? a.res_pitch : 0)) & 7) == 0 &&
-      ((reinterpret_cast<uintptr_t>(a.C) | reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0) {
-    constexpr int WC = BN / WN, LDC = WC + 4, LPR = WC / 8, RPI = 64 / LPR;
-    static_assert(32 % RPI == 0, "row segments must tile the 32-row slab");
-    __syncthreads();
-    float* Ws = smem + wave * 32 * LDC;
-    const int rr0 = lane / LPR, cc = (lane % LPR) * 8;
-    const int col = n0 + wn * WC + cc;
-    const bool cok = col < a.Nn;                      // Nn % 8 == 0: the group is all in or all out
-    const bool aff = a.bias || a.scale, res = a.residual != nullptr, relu = a.relu != 0;
-    float bi[8], sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bi[e] = 0.f, sc[e] = 1.f, sh[e] = 0.f;
-    if (aff && cok) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (a.bias) bi[e] = a.bias[col + e];
-        if (a.scale) sc[e] = a.scale[col + e], sh[e] = a.shift[col + e];
-      }
-    }
+  if (a.io16 && a.ksplit == 1) {
     pm_bf16* C16 = reinterpret_cast<pm_bf16*>(a.C) + by * a.c_bs;
     const pm_bf16* R16 = reinterpret_cast<const pm_bf16*>(a.residual);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int n = 0; n < TN; ++n)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) Ws[((q & 3) + 8 * (q >> 2) + 4 * half) * LDC + n * 32 + l31] = acc[i][n][q];
-#pragma unroll
-      for (int r0 = 0; r0 < 32; r0 += RPI) {
-        const int rr = r0 + rr0;
-        const long row = m0 + wm * (BM / WM) + i * 32 + rr;
-        const float4 v0 = *reinterpret_cast<const float4*>(Ws + rr * LDC + cc), v1 = *reinterpret_cast<const float4*>(Ws + rr * LDC + cc + 4);
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        if (row < a.M && cok) {
-          if (aff) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (v[e] + bi[e]) * sc[e] + sh[e];
-          }
-          if (res) {
-            float q[8];
-            pm_ld8(R16 + row * a.res_pitch + col, q);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += q[e];
-          }
-          if (relu) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-          }
-          pm_st8(C16 + row * a.c_pitch + col, v);
-        }
-      }
-      if constexpr (STATS) {      // bf16 tier: statistics of the ROUNDED values of this 32-row slab (pm_common.h)
-        if (a.stats) pm_slab_stats16<LDC, LPR, RPI>(Ws, rr0, cc, (long)m0 + wm * (BM / WM) + i * 32, a.M, a.Nn, col, cok, bi, sc, sh, a.stats);
-      }
-    }
+    if (((a.c_pitch | a.Nn | (a.residual ? a.res_pitch : 0)) & 7) == 0 && ((reinterpret_cast<uintptr_t>(a.C) | reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0)
+      igemm_epilogue_staged<pm_bf16, false, STATS, BM, BN, WM, WN>(a, C16, R16, smem, acc, m0, n0, wm, wn, wave, lane, l31, half, aff, res, relu);
+    else
+      igemm_epilogue_elems<pm_bf16, true>(a, C16, R16, acc, rbase, cbase, true, R16 != nullptr, a.relu != 0);
     return;
   }
-  if (out16) {      // unaligned / narrow bf16 outputs: per-element form
-    pm_bf16* C16 = reinterpret_cast<pm_bf16*>(a.C) + by * a.c_bs;
-    const pm_bf16* R16 = reinterpret_cast<const pm_bf16*>(a.residual);
+  const bool vec = a.stage_ep && ((a.c_pitch | a.Nn | (a.residual ? a.res_pitch : 0)) & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(Cb) | reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0;
+  if (vec) {
+    igemm_epilogue_staged<float, MODE == MODE_DGRAD, STATS, BM, BN, WM, WN>(a, Cb, a.residual, smem, acc, m0, n0, wm, wn, wave, lane, l31, half, aff, res, relu);
+  } else if (m0 + BM <= a.M && n0 + BN <= a.Nn) {
+    // interior tile: straight-line code specialised on the (wave-uniform) fused operations, no per-element predicate
+#define PM_EP(AFF, RES, RELU) igemm_epilogue_elems<float, false>(a, Cb, a.residual, acc, rbase, cbase, AFF, RES, RELU)
+    if (!aff && !res && !relu) PM_EP(false, false, false);
+    else if (!aff && res && !relu) PM_EP(false, true, false);       // dgrad + fused skip gradient
+    else if (aff && !res && !relu) PM_EP(true, false, false);       // conv + bias
+    else if (aff && !res && relu) PM_EP(true, false, true);         // eval: conv + folded BN + ReLU
+    else if (aff && res && relu) PM_EP(true, true, true);           // eval: bottleneck tail
+    else if (aff && res && !relu) PM_EP(true, true, false);
+    else if (!aff && res && relu) PM_EP(false, true, true);
+    else PM_EP(false, false, true);
+#undef PM_EP
+  } else {
+    // fp32 edge tile (the 19 class logits): written out. Through igemm_epilogue_elems<float, true> the per-element branches became selects and the forward pass of the
+    // class head (1x1 256 -> 19 at 192 x 192) measured 0.076 -> 0.082 ms (profiles/igemm_refactor_ab.txt).
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -883,7 +704,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
         const int col = cbase + n * 32;
         const bool cok = col < a.Nn;
         float bi = 0.f, sc = 1.f, sh = 0.f;
-        if (cok) {
+        if (!plain && cok) {
           if (a.bias) bi = a.bias[col];
           if (a.scale) sc = a.scale[col], sh = a.shift[col];
         }
@@ -891,167 +712,25 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK a) {
         for (int q = 0; q < 16; ++q) {
           const int row = rbase + i * 32 + (q & 3) + 8 * (q >> 2);
           if (row < a.M && cok) {
-            float v = (acc[i][n][q] + bi) * sc + sh;
-            if (R16) v += pm_bf16_to_f32(R16[(long)row * a.res_pitch + col]);
-            if (a.relu) v = fmaxf(v, 0.f);
-            C16[(long)row * a.c_pitch + col] = pm_f32_to_bf16(v);
-          }
-        }
-      }
-    return;
-  }
-  const bool vec = a.stage_ep && ((a.c_pitch | a.Nn | (a.residual ? a.res_pitch : 0)) & 3) == 0 &&
-                   ((reinterpret_cast<uintptr_t>(Cb) | reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0;
-  if (vec) {
-    constexpr int WC = BN / WN, LDC = WC + 4, LPR = WC / 4, RPI = 64 / LPR;   // columns per wave, padded pitch, lanes per row, rows per instruction
-    static_assert(32 % RPI == 0, "row segments must tile the 32-row slab");
-    __syncthreads();                                  // every wave is done reading the last K-slab
-    float* Ws = smem + wave * 32 * LDC;
-    const int rr0 = lane / LPR, cc = (lane % LPR) * 4;
-    const int col = n0 + wn * WC + cc;
-    const bool cok = col < a.Nn;                      // Nn % 4 == 0: the quad is all in or all out
-    const bool aff = !plain && (a.bias || a.scale), res = !plain && a.residual, relu = !plain && a.relu;
-    float bi[4] = {0.f, 0.f, 0.f, 0.f}, sc[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
-    if (aff && cok) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (a.bias) bi[e] = a.bias[col + e];
-        if (a.scale) sc[e] = a.scale[col + e], sh[e] = a.shift[col + e];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int n = 0; n < TN; ++n)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) Ws[((q & 3) + 8 * (q >> 2) + 4 * half) * LDC + n * 32 + l31] = acc[i][n][q];
-#pragma unroll
-      for (int r0 = 0; r0 < 32; r0 += RPI) {
-        const int rr = r0 + rr0;
-        const long row = m0 + wm * (BM / WM) + i * 32 + rr;
-        float4 v = *reinterpret_cast<const float4*>(Ws + rr * LDC + cc);
-        if (row < a.M && cok) {
-          if (aff) v.x = (v.x + bi[0]) * sc[0] + sh[0], v.y = (v.y + bi[1]) * sc[1] + sh[1], v.z = (v.z + bi[2]) * sc[2] + sh[2], v.w = (v.w + bi[3]) * sc[3] + sh[3];
-          if (res) {
-            float4 qv = PM_LD4(a.residual + row * a.res_pitch + col);
-            if constexpr (MODE == MODE_DGRAD) if (a.res_mask) {      // (data gradients only: the forward instantiations keep their register allocation)
-              const unsigned mb = a.res_mask[row * (a.Nn >> 2) + (col >> 2)];
-              qv.x = (mb & 1u) ? qv.x : 0.f, qv.y = (mb & 2u) ? qv.y : 0.f, qv.z = (mb & 4u) ? qv.z : 0.f, qv.w = (mb & 8u) ? qv.w : 0.f;
-            }
-            v.x += qv.x, v.y += qv.y, v.z += qv.z, v.w += qv.w;
-          }
-          if (relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-          PM_ST4(Cb + row * a.c_pitch + col, v);
-        }
-      }
-      if constexpr (STATS) {   // BatchNorm statistics of this 32-row slab (train mode: the epilogue is the convolution plus at most a
-                       // bias), two passes over the slab still parked in LDS: per column the mean over the valid rows, then M2 around it;
-                       // the RPI lanes sharing a column quad are combined by lane exchanges (fixed order). The slab is re-read rather than
-                       // kept in registers so that the kernel's register budget (and occupancy) is the one without statistics.
-        const long slab_row0 = m0 + wm * (BM / WM) + i * 32;
-        const float cnt = (float)max(0l, min(32l, (long)a.M - slab_row0));
-        auto slab_row = [&](int r0, bool& rok) {
-          float4 v = *reinterpret_cast<const float4*>(Ws + (r0 + rr0) * LDC + cc);
-          v.x = (v.x + bi[0]) * sc[0] + sh[0], v.y = (v.y + bi[1]) * sc[1] + sh[1], v.z = (v.z + bi[2]) * sc[2] + sh[2], v.w = (v.w + bi[3]) * sc[3] + sh[3];
-          rok = slab_row0 + r0 + rr0 < a.M;
-          return v;
-        };
-        float s1[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r0 = 0; r0 < 32; r0 += RPI) {
-          bool rok;
-          const float4 v = slab_row(r0, rok);
-          s1[0] += rok ? v.x : 0.f, s1[1] += rok ? v.y : 0.f, s1[2] += rok ? v.z : 0.f, s1[3] += rok ? v.w : 0.f;
-        }
-#pragma unroll
-        for (int o = LPR; o < 64; o <<= 1)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s1[e] += __shfl_xor(s1[e], o, 64);
-        float mu[4], m2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mu[e] = cnt > 0.f ? s1[e] / cnt : 0.f;
-#pragma unroll
-        for (int r0 = 0; r0 < 32; r0 += RPI) {
-          bool rok;
-          const float4 v = slab_row(r0, rok);
-          const float d0 = v.x - mu[0], d1 = v.y - mu[1], d2 = v.z - mu[2], d3 = v.w - mu[3];
-          m2[0] += rok ? d0 * d0 : 0.f, m2[1] += rok ? d1 * d1 : 0.f, m2[2] += rok ? d2 * d2 : 0.f, m2[3] += rok ? d3 * d3 : 0.f;
-        }
-#pragma unroll
-        for (int o = LPR; o < 64; o <<= 1)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) m2[e] += __shfl_xor(m2[e], o, 64);
-        if (rr0 == 0 && cok && cnt > 0.f) {
-          float* dst = a.stats + ((slab_row0 >> 5) * (long)a.Nn + col) * 2;
-          PM_ST4(dst, make_float4(mu[0], m2[0], mu[1], m2[1]));
-          PM_ST4(dst + 4, make_float4(mu[2], m2[2], mu[3], m2[3]));
-        }
-      }
-    }
-    return;
-  }
-  if (full) {  // interior tile: straight-line epilogue specialised on the (wave-uniform) fused operations, no per-element predicate
-    auto run = [&](auto AFF, auto RES, auto RELU) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int n = 0; n < TN; ++n) {
-          const int col = cbase + n * 32;
-          float bi = 0.f, sc = 1.f, sh = 0.f;
-          if constexpr (decltype(AFF)::value) {
-            if (a.bias) bi = a.bias[col];
-            if (a.scale) sc = a.scale[col], sh = a.shift[col];
-          }
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const long row = rbase + i * 32 + (q & 3) + 8 * (q >> 2);
             float v = acc[i][n][q];
-            if constexpr (decltype(AFF)::value) v = (v + bi) * sc + sh;
-            if constexpr (decltype(RES)::value) v += a.residual[row * a.res_pitch + col];
-            if constexpr (decltype(RELU)::value) v = fmaxf(v, 0.f);
-            Cb[row * a.c_pitch + col] = v;
+            if (!plain) {
+              v = (v + bi) * sc + sh;
+              if (a.residual) v += a.residual[(long)row * a.res_pitch + col];
+              if (a.relu) v = fmaxf(v, 0.f);
+            }
+            Cb[(long)row * a.c_pitch + col] = v;
           }
         }
-    };
-    using T1 = std::true_type;
-    using T0 = std::false_type;
-    const bool aff = !plain && (a.bias || a.scale), res = !plain && a.residual, relu = !plain && a.relu;
-    if (!aff && !res && !relu) run(T0{}, T0{}, T0{});
-    else if (!aff && res && !relu) run(T0{}, T1{}, T0{});       // dgrad + fused skip gradient
-    else if (aff && !res && !relu) run(T1{}, T0{}, T0{});       // conv + bias
-    else if (aff && !res && relu) run(T1{}, T0{}, T1{});        // eval: conv + folded BN + ReLU
-    else if (aff && res && relu) run(T1{}, T1{}, T1{});         // eval: bottleneck tail
-    else if (aff && res && !relu) run(T1{}, T1{}, T0{});
-    else if (!aff && res && relu) run(T0{}, T1{}, T1{});
-    else run(T0{}, T0{}, T1{});
-    return;
+      }
   }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int n = 0; n < TN; ++n) {
-      const int col = cbase + n * 32;
-      const bool cok = col < a.Nn;
-      float bi = 0.f, sc = 1.f, sh = 0.f;
-      if (!plain && cok) {
-        if (a.bias) bi = a.bias[col];
-        if (a.scale) sc = a.scale[col], sh = a.shift[col];
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = rbase + i * 32 + (q & 3) + 8 * (q >> 2);
-        if (row < a.M && cok) {
-          float v = acc[i][n][q];
-          if (!plain) {
-            v = (v + bi) * sc + sh;
-            if (a.residual) v += a.residual[(long)row * a.res_pitch + col];
-            if (a.relu) v = fmaxf(v, 0.f);
-          }
-          Cb[(long)row * a.c_pitch + col] = v;
-        }
-      }
-    }
-  return;
+}
+
+// One instantiation's launch: the > 64 KB dynamic-LDS opt-in, made once per device and kernel (pm_lds_optin), then the launch on `smem` bytes of LDS.
+template <auto KERNEL>
+void igemm_launch(const ConvK& k, dim3 grid, size_t smem, hipStream_t st) {
+  static pm_lds_optin optin;
+  (void)optin(reinterpret_cast<const void*>(KERNEL), 160 * 1024);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), smem, st, k);
 }
 
 }  // namespace

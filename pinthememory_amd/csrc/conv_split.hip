@@ -16,16 +16,9 @@ void launch_split(const ConvK& k, dim3 grid, size_t smem, hipStream_t st) {
   const size_t ep_bytes = (size_t)4 * 32 * (BN / 2 + 4) * sizeof(float);      // staged epilogue: four wave slabs
   const size_t bytes = std::max(smem, ep_bytes);
   if constexpr (MODE == MODE_FWD) {
-    if (k.stats) {
-      static pm_lds_optin optin;
-      (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1, true>), 160 * 1024);
-      hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1, true>), grid, dim3(256), bytes, st, k);
-      return;
-    }
+    if (k.stats) return igemm_launch<conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1, true>>(k, grid, bytes, st);
   }
-  static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1>), 160 * 1024);
-  hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1>), grid, dim3(256), bytes, st, k);
+  igemm_launch<conv_igemm_kernel<MODE, BM, BN, 2, 2, KM, 5, 1>>(k, grid, bytes, st);
 }
 
 template <int MODE, int BM, int BN>

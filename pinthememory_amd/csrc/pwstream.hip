@@ -17,13 +17,9 @@
 
 #include <algorithm>
 
-#include "pm_common.h"
+#include "conv_igemm_parts.h"      // bload, split4: the tile kernel's buffer load and three-way split
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct PwsK {
   const float* A;            // rows of K floats, a_pitch floats apart
@@ -36,24 +32,6 @@ struct PwsK {
   int b_sn, b_sk;
   int M, Nn, row_tiles, relu;
 };
-
-__device__ __forceinline__ v4f pws_load(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-
-// four fp32 -> 3 x four bf16 by truncation (exact: hi + mid + lo == x), as in the split tile kernel
-__device__ __forceinline__ void pws_split4(const v4f& v, unsigned* hi, unsigned* mid, unsigned* lo) {
-  const unsigned u0 = __float_as_uint(v.x), u1 = __float_as_uint(v.y), u2 = __float_as_uint(v.z), u3 = __float_as_uint(v.w);
-  hi[0] = __builtin_amdgcn_perm(u1, u0, 0x07060302), hi[1] = __builtin_amdgcn_perm(u3, u2, 0x07060302);
-  const float r0 = v.x - __uint_as_float(u0 & 0xffff0000u), r1 = v.y - __uint_as_float(u1 & 0xffff0000u);
-  const float r2 = v.z - __uint_as_float(u2 & 0xffff0000u), r3 = v.w - __uint_as_float(u3 & 0xffff0000u);
-  const unsigned q0 = __float_as_uint(r0), q1 = __float_as_uint(r1), q2 = __float_as_uint(r2), q3 = __float_as_uint(r3);
-  mid[0] = __builtin_amdgcn_perm(q1, q0, 0x07060302), mid[1] = __builtin_amdgcn_perm(q3, q2, 0x07060302);
-  const float s0 = r0 - __uint_as_float(q0 & 0xffff0000u), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-  const float s2 = r2 - __uint_as_float(q2 & 0xffff0000u), s3 = r3 - __uint_as_float(q3 & 0xffff0000u);
-  lo[0] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-  lo[1] = __builtin_amdgcn_perm(__float_as_uint(s3), __float_as_uint(s2), 0x07060302);
-}
 
 // KG: 16-k groups (K = 16 * KG). Lane (l31, h) of a fragment holds, for group m and element i, k = 16 m + 8 (i >> 2) + 4 h + (i & 3): the two 16-byte loads
 // (k offsets 16 m + 4 h and 16 m + 8 + 4 h) of its row -- on both operands.
@@ -78,12 +56,12 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
       w0.x = bp[0], w0.y = bp[a.b_sk], w0.z = bp[2 * a.b_sk], w0.w = bp[3 * a.b_sk];
       bp += 8 * a.b_sk;
       w1.x = bp[0], w1.y = bp[a.b_sk], w1.z = bp[2 * a.b_sk], w1.w = bp[3 * a.b_sk];
-      unsigned hi[4], mid[4], lo[4];
-      pws_split4(w0, hi, mid, lo), pws_split4(w1, hi + 2, mid + 2, lo + 2);
+      uint2 hi[2], mid[2], lo[2];
+      split4(w0, hi[0], mid[0], lo[0]), split4(w1, hi[1], mid[1], lo[1]);
       char* dst = lds + ((m * 2 + cb) * 3) * 1024 + lane * 16;
-      *reinterpret_cast<uint4*>(dst) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-      *reinterpret_cast<uint4*>(dst + 1024) = make_uint4(mid[0], mid[1], mid[2], mid[3]);
-      *reinterpret_cast<uint4*>(dst + 2048) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+      *reinterpret_cast<uint4*>(dst) = make_uint4(hi[0].x, hi[0].y, hi[1].x, hi[1].y);
+      *reinterpret_cast<uint4*>(dst + 1024) = make_uint4(mid[0].x, mid[0].y, mid[1].x, mid[1].y);
+      *reinterpret_cast<uint4*>(dst + 2048) = make_uint4(lo[0].x, lo[0].y, lo[1].x, lo[1].y);
     }
   }
   // the slab's epilogue constants behind the planes: bias | scale | shift, 64 floats each
@@ -105,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
   auto load = [&](v4f* dst, int tile) {
     const unsigned off = (unsigned)(tile * 32 + l31) * a_row + (unsigned)h * 16u;
 #pragma unroll
-    for (int q = 0; q < 2 * KG; ++q) dst[q] = pws_load(rA, off + (unsigned)q * 32u);
+    for (int q = 0; q < 2 * KG; ++q) dst[q] = bload(rA, off + (unsigned)q * 32u);
   };
   auto tile_out = [&](const v4f* src, int tile) {
     asm volatile("" ::: "memory");      // the weight fragments are re-read from LDS per tile: hoisted out of the tile loop they would pin 24 KG registers
@@ -117,11 +95,11 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
 #pragma unroll
     for (int m = 0; m < KG; ++m) {
       if (m) asm volatile("" ::: "memory");      // ... and the fragments of one 16-k group at a time: requested here, they land under this group's split arithmetic
-      unsigned ah[4], am[4], al[4];
-      pws_split4(src[2 * m], ah, am, al), pws_split4(src[2 * m + 1], ah + 2, am + 2, al + 2);
-      const bf16x8 fah = __builtin_bit_cast(bf16x8, make_uint4(ah[0], ah[1], ah[2], ah[3]));
-      const bf16x8 fam = __builtin_bit_cast(bf16x8, make_uint4(am[0], am[1], am[2], am[3]));
-      const bf16x8 fal = __builtin_bit_cast(bf16x8, make_uint4(al[0], al[1], al[2], al[3]));
+      uint2 ah[2], am[2], al[2];
+      split4(src[2 * m], ah[0], am[0], al[0]), split4(src[2 * m + 1], ah[1], am[1], al[1]);
+      const bf16x8 fah = __builtin_bit_cast(bf16x8, make_uint4(ah[0].x, ah[0].y, ah[1].x, ah[1].y));
+      const bf16x8 fam = __builtin_bit_cast(bf16x8, make_uint4(am[0].x, am[0].y, am[1].x, am[1].y));
+      const bf16x8 fal = __builtin_bit_cast(bf16x8, make_uint4(al[0].x, al[0].y, al[1].x, al[1].y));
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
         const char* src_b = lds + ((m * 2 + cb) * 3) * 1024 + lane * 16;
@@ -159,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void pwstream_kernel(PwsK a) {
         v4f v = *reinterpret_cast<const v4f*>(stg + (rr + 8 * ps) * 144 + cg * 16);
         if (aff) v = (v + bi) * sc + sh;
         if (res) {
-          v4f q = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rR, (int)(row * r_row + (unsigned)(n0 + c) * 4u), 0, 0));
+          v4f q = bload(rR, row * r_row + (unsigned)(n0 + c) * 4u);
           if (msk) {      // rows beyond M: outside the mask's extent as well (reads 0; the row is not stored)
             const unsigned mb = __builtin_amdgcn_raw_buffer_load_b8(rM, (int)(row * m_row + (unsigned)((n0 + c) >> 2)), 0, 0);
             q.x = (mb & 1u) ? q.x : 0.f, q.y = (mb & 2u) ? q.y : 0.f, q.z = (mb & 4u) ? q.z : 0.f, q.w = (mb & 8u) ? q.w : 0.f;
