@@ -8,6 +8,12 @@
  *     tensor memory; scratch comes from the caller through (ws, ws_bytes);
  *   - activations are NHWC fp32: pixel-major rows of `c` channels, `pitch` floats between pixels
  *     (pitch >= c lets a kernel write into a channel slice of a wider concat buffer);
+ *   - a call reads and writes channels [0, c) of each of the n*h*w pixels of a pm_tensor and NOTHING ELSE: not the other `pitch - c` lanes of a pixel, not
+ *     the memory before the first pixel or behind the last one (a ragged last tile is masked, never rounded up). Two exceptions, both the caller's choice:
+ *     an fp32 view with c % 4 != 0 and pitch == roundup4(c) owns its pad lanes -- the caller hands them over as zeros, a call may read them and may write
+ *     zeros there; and PM_TF_ZERO_PAD64 (below) lets a bf16 convolution READ the zero lanes c .. roundup(c, 64) - 1. An input tensor or array is never written.
+ *     A view an entry point cannot serve (no 16-byte rows where it has no element-wise form) is refused with a negative status before anything is launched;
+ *     tests/test_tensor_views.py holds every entry point to this on views inside poisoned memory and lists the refusals;
  *   - conv weights are KRSC fp32 ([Cout][kh][kw][Cin] == a torch channels_last [Cout,Cin,kh,kw] tensor);
  *   - labels are int64 as the reference's callers provide them (transforms/transforms.py:95-97), 255 = ignore;
  *   - all work is enqueued on `stream` (a hipStream_t), no host synchronisation inside;

@@ -203,10 +203,12 @@ constexpr int V = 8;                       // channels per 16-byte lane access
 __global__ __launch_bounds__(256) void to_f32_kernel(const pm_bf16* __restrict__ x, long pitch, int C, long P, float* __restrict__ out, long op) {
   const int cg = (C + V - 1) / V;
   const long total = P * cg;
+  // 16-byte accesses need 16-byte rows: pitches of 8 elements AND aligned bases (an fp32 view may start 8 bytes into a row of a wider buffer)
+  const bool rows16 = ((pitch | op) & 7) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long p = i / cg;
     const int c = (int)(i - p * cg) * V;
-    if (c + V <= C && ((pitch | op) & 7) == 0) {
+    if (c + V <= C && rows16) {
       float v[V];
       pm_ld8(x + p * pitch + c, v);
       PM_ST4(out + p * op + c, make_float4(v[0], v[1], v[2], v[3]));
