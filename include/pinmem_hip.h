@@ -49,8 +49,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * receives a struct built against another header returns PM_EINVAL instead of reading past the caller's object (they grew in rounds 2 and 3).
  * 400 (round 4): pm_tensor carries dtype + flags (bf16 activation tier).
  * 410: pm_aug_image and the augmenting input edge (pm_augment_u8, pm_labels_u8_flip_to_i64); the size of that struct is an ARGUMENT of the calls that read it,
- * because the array lives in device memory where the library cannot look at a first member. */
-#define PM_ABI_VERSION 410
+ * because the array lives in device memory where the library cannot look at a first member.
+ * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS. */
+#define PM_ABI_VERSION 420
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -371,6 +372,39 @@ int pm_augment_u8(const uint8_t* img_nhw3, int n, int H, int W, const pm_aug_ima
                   float* out_nhwc4, uint8_t* out_u8, void* ws, size_t ws_bytes, void* stream);
 /* pm_labels_u8_to_i64 with the columns of image i mirrored where params_dev[i].flip != 0 */
 int pm_labels_u8_flip_to_i64(const uint8_t* lab, int n, int H, int W, const pm_aug_image* params_dev, int32_t struct_size, int64_t* out, void* stream);
+
+/* ---- resampling input edge: joint_transforms.RandomSizeAndCrop (transforms/joint_transforms.py:414-444) with its RandomCrop (:61-141) on uint8 pixels in HBM, in
+ * front of everything above: the whole image resized with PIL's antialiased bicubic (Image.resize(BICUBIC)) and the mask with Image.NEAREST, both padded where the result
+ * is smaller than the crop (image 0, mask ignore_index), then one crop window taken. Only the window is computed: its pixels and their filter footprints.
+ * The bytes are PIL's. Its 8-bit resampling is integer arithmetic (Resample.c): per axis and output position a first source index, a tap count and int32 coefficients
+ * round(w * 2^22); one output byte of a pass = clip8(((1 << 21) + sum of pixel * k) >> 22), arithmetic shift; the horizontal pass runs first and is ROUNDED TO BYTES before
+ * the vertical one. An axis whose size does not change is a copy (PIL skips the pass). NEAREST reads source index (int)xo with xo = a / 2 + a + a + ... accumulated in
+ * double from output position 0 (Geometry.c), a = in / out: the closed form (int)(a * (x + 0.5)) is NOT the same pixels. */
+#define PM_RESAMPLE_MAX_TAPS 24 /* taps per output position and axis the tables hold: enough for every in / out <= 5.75, which covers every scale in [0.25, 4] of every
+                                   image (int() of the resized size makes in / out exceed 1 / scale; with >= 24 source pixels it stays below 4.8, with fewer the taps
+                                   cannot outnumber the pixels) */
+#define PM_RESAMPLE_REC (PM_RESAMPLE_MAX_TAPS + 2)      /* int32 per bicubic table record: first source index, tap count, coefficients (unused ones 0) */
+typedef struct pm_geo_image {   /* the geometry of one image, in DEVICE memory for the kernel and in host memory for pm_resample_tables */
+  int32_t h_in, w_in;           /* the image occupies the top-left h_in x w_in corner of its [Hs][Ws] slab: domains of different sizes share one batch */
+  int32_t h, w;                 /* size after the resize: int(H * scale), int(W * scale) */
+  int32_t pad_h, pad_w;         /* border added on BOTH sides of an axis shorter than the crop: (t - size) / 2 + 1 */
+  int32_t y1, x1;               /* crop origin in padded coordinates: 0 <= y1 <= h + 2 pad_h - th */
+} pm_geo_image;
+/* host only, no device involved: the four tables pm_resample_crop_u8 reads for ONE image, for the th x tw crop window alone. bic_rows [th][PM_RESAMPLE_REC] and
+ * bic_cols [tw][PM_RESAMPLE_REC]: per crop row / column the record above; a pad position has tap count 0, an axis with out == in one tap of 2^22. near_rows [th],
+ * near_cols [tw]: the mask's source index, -1 on the pad. Evaluated in double without fused multiply-adds, as PIL's C is compiled. Hs, Ws: the slab the image lives in.
+ * PM_EINVAL: a null pointer, another struct_size, an empty size, h_in > Hs or w_in > Ws, a crop that does not lie inside the padded image.
+ * PM_EUNSUPPORTED: an output position needs more than PM_RESAMPLE_MAX_TAPS taps (what the tables hold then is unspecified). */
+int pm_resample_tables(const pm_geo_image* geo_host, int32_t struct_size, int Hs, int Ws, int th, int tw, int32_t* bic_rows, int32_t* bic_cols, int32_t* near_rows,
+                       int32_t* near_cols);
+/* img uint8 [n][Hs][Ws][3], lab uint8 [n][Hs][Ws]; geo_dev: n structs of struct_size = sizeof(pm_geo_image) bytes in device memory; the four tables of every image in
+ * device memory, image-major ([n][th][PM_RESAMPLE_REC], [n][tw][PM_RESAMPLE_REC], [n][th], [n][tw]), as pm_resample_tables wrote them. out_img uint8 [n][th][tw][3],
+ * out_lab uint8 [n][th][tw] -- the layouts pm_augment_u8 / pm_labels_u8_flip_to_i64 take. No output may overlap an input. Slab bytes outside h_in x w_in and source
+ * pixels outside the window's footprint are never read. Integer arithmetic, no atomics: the same bytes for every tiling and on every run. A table that did not come from
+ * pm_resample_tables gives undefined bytes, but its indices are clamped to the image: no access outside the slabs. */
+int pm_resample_crop_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo_dev, int32_t struct_size, const int32_t* bic_rows,
+                        const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, uint8_t* out_img, uint8_t* out_lab,
+                        void* stream);
 
 /* ---- layout edges ------------------------------------------------------------------------------------------------ */
 int pm_nchw_to_nhwc(const float* x_nchw, int c_src, const pm_tensor* y, void* stream);   /* zero-fills y.c > c_src */

@@ -752,15 +752,20 @@ def prepare_batch(inputs, gts, aux_gts=None):
     return x, gt, aux
 
 
-def prepare_batch_u8(images_u8, labels_u8, augment=None, hard=None):
+def prepare_batch_u8(images_u8, labels_u8, augment=None, hard=None, geometry=None, sizes=None, centroids=None):
     """GPU-side ToTensor + Normalize(ImageNet) + MaskToTensor for uint8 [.., H, W, 3] images and uint8 [.., H, W] label maps:
     4x / 8x less host->device traffic than the fp32 / int64 tensors the reference's loader ships. Returns the image as a
     logical-NCHW view of NHWC4 memory (what the stem consumes without another conversion) and int64 labels.
     augment (an input_edge.PhotometricAugment; None = the plain conversion): colour jitter, blur and flip on the device first (image and labels flipped alike);
-    hard: one bool per image after the leading axes merged -- those get the hard augmentation of the meta-test domains."""
+    hard: one bool per image after the leading axes merged -- those get the hard augmentation of the meta-test domains.
+    geometry (an input_edge.GeometricAugment; None = none): RandomSizeAndCrop on the device before all of that -- resize, pad and crop of image and labels; sizes
+    ((H, W) per image, the image in the top-left corner of its slab; None: every image fills it) and centroids go to its sampler."""
     h, w = images_u8.shape[-3:-1]
     img_d = images_u8.reshape(-1, h, w, 3).cuda(non_blocking=True).contiguous()
     lab_d = labels_u8.reshape(-1, h, w).cuda(non_blocking=True).contiguous()
+    if geometry is not None:
+        from .input_edge import sample_geometry
+        img_d, lab_d = K.resample_crop_u8(img_d, lab_d, sample_geometry(geometry, img_d.shape, dict(sizes=sizes, centroids=centroids)))
     if augment is None:
         return ops.nchw(K.image_u8_to_nhwc4(img_d)), K.labels_u8_to_i64(lab_d)
     params = K.upload_aug_params(augment.sample(img_d.shape[0], hard), img_d.device)

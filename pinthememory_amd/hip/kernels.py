@@ -809,6 +809,84 @@ def augment_u8(img_u8, params, want_u8=False, mean=IMAGENET_MEAN, std=IMAGENET_S
     return (out, out8) if want_u8 else out
 
 
+# ---- resampling input edge (csrc/resample.hip) ----------------------------------------------------------------------------
+class GeoParams:
+    """The geometry of one batch on the host: `images`, a ctypes array of pm_geo_image (one per image: source size, resized size, pad, crop origin), the crop
+    size (th, tw) all images share, and the label value of the padding. What input_edge.GeometricAugment.sample returns and resample_crop_u8 takes."""
+
+    def __init__(self, n, crop, ignore_index=255):
+        self.images = (L.PmGeoImage * n)()
+        self.crop = (int(crop[0]), int(crop[1]))
+        self.ignore_index = int(ignore_index)
+
+    def __len__(self):
+        return len(self.images)
+
+
+class GeoDevice:
+    """upload_geo's result: one uint8 device tensor holding the pm_geo_image array and the four tables of every image, and where each part starts."""
+
+    def __init__(self, buf, n, crop, ignore_index, slab, offsets):
+        self.buf, self.n, self.crop, self.ignore_index, self.slab, self.offsets = buf, n, crop, ignore_index, slab, offsets
+
+
+def _geo_offsets(n, crop):
+    """Byte offsets of (structs, bicubic rows, bicubic columns, nearest rows, nearest columns) in the staged block, and its size."""
+    th, tw = crop
+    sizes = (n * ctypes.sizeof(L.PmGeoImage), n * th * L.RESAMPLE_REC * 4, n * tw * L.RESAMPLE_REC * 4, n * th * 4, n * tw * 4)
+    offs = [0]
+    for s in sizes:
+        offs.append(offs[-1] + s)
+    return offs[:-1], offs[-1]
+
+
+def resample_tables(g, slab, crop):
+    """The four host tables of ONE pm_geo_image for a th x tw window (pm_resample_tables; no device involved): ctypes int32 arrays bic_rows [th * REC], bic_cols [tw * REC],
+    near_rows [th], near_cols [tw]. Raises PinmemError for a geometry the library refuses (crop outside the padded image, image larger than its slab, too many taps)."""
+    th, tw = int(crop[0]), int(crop[1])
+    assert th > 0 and tw > 0, 'empty crop'
+    i32 = ctypes.c_int32
+    t = ((i32 * (th * L.RESAMPLE_REC))(), (i32 * (tw * L.RESAMPLE_REC))(), (i32 * th)(), (i32 * tw)())
+    check(_lib().pm_resample_tables(ctypes.addressof(g), ctypes.sizeof(L.PmGeoImage), int(slab[0]), int(slab[1]), th, tw, *[ctypes.addressof(a) for a in t]), 'pm_resample_tables')
+    return t
+
+
+def upload_geo(geo, device, slab):
+    """GeoParams -> GeoDevice: the library writes every image's tables straight into one pinned block behind the structs (validating each geometry against the
+    [Hs, Ws] slab on the way), and the block is copied without blocking on the current stream, as upload_aug_params does. A GeoDevice is passed on."""
+    if isinstance(geo, GeoDevice):
+        assert geo.slab == (int(slab[0]), int(slab[1])), 'geometry uploaded for slab %s, batch has %s' % (geo.slab, tuple(slab))
+        return geo
+    n, (th, tw) = len(geo), geo.crop
+    offs, total = _geo_offsets(n, geo.crop)
+    host = torch.empty(max(total, 4), dtype=torch.uint8, pin_memory=True)
+    base, size, lib = host.data_ptr(), ctypes.sizeof(L.PmGeoImage), _lib()
+    ctypes.memmove(base, ctypes.addressof(geo.images), n * size)
+    rec = L.RESAMPLE_REC * 4
+    for i in range(n):
+        check(lib.pm_resample_tables(ctypes.addressof(geo.images[i]), size, int(slab[0]), int(slab[1]), th, tw, base + offs[1] + i * th * rec, base + offs[2] + i * tw * rec,
+                                     base + offs[3] + i * th * 4, base + offs[4] + i * tw * 4), 'pm_resample_tables (image %d)' % i)
+    return GeoDevice(host.to(device, non_blocking=True), n, geo.crop, geo.ignore_index, (int(slab[0]), int(slab[1])), offs)
+
+
+def resample_crop_u8(img_u8, lab_u8, geo):
+    """RandomSizeAndCrop on the device: uint8 [N,Hs,Ws,3] images and uint8 [N,Hs,Ws] label maps (image i in the top-left h_in x w_in corner of its slab) -> the
+    crop window of the bicubic-resized, padded image, uint8 [N,th,tw,3], and of the nearest-resized mask, uint8 [N,th,tw], with PIL's bytes. geo: a GeoParams
+    (input_edge.GeometricAugment.sample) or its upload_geo copy."""
+    n, hs, ws, c = img_u8.shape
+    assert c == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.is_cuda
+    assert lab_u8.shape == (n, hs, ws) and lab_u8.dtype == torch.uint8 and lab_u8.is_contiguous() and lab_u8.device == img_u8.device
+    gd = upload_geo(geo, img_u8.device, (hs, ws))
+    assert gd.n == n, 'geometry for %d images, batch of %d' % (gd.n, n)
+    th, tw = gd.crop
+    out = torch.empty((n, th, tw, 3), dtype=torch.uint8, device=img_u8.device)
+    out_lab = torch.empty((n, th, tw), dtype=torch.uint8, device=img_u8.device)
+    p, o = gd.buf.data_ptr(), gd.offsets
+    check(_lib().pm_resample_crop_u8(img_u8.data_ptr(), lab_u8.data_ptr(), n, hs, ws, p + o[0], ctypes.sizeof(L.PmGeoImage), p + o[1], p + o[2], p + o[3], p + o[4], th, tw,
+                                     gd.ignore_index, out.data_ptr(), out_lab.data_ptr(), stream()), 'pm_resample_crop_u8')
+    return out, out_lab
+
+
 def nchw_to_nhwc(x, c_pad=None):
     n, c, h, w = x.shape
     x = x.contiguous()

@@ -45,6 +45,15 @@ class PmAugImage(ctypes.Structure):
                 ('brightness', c_float), ('contrast', c_float), ('saturation', c_float), ('radius', c_int32), ('w', ctypes.c_double * 6)]
 
 
+class PmGeoImage(ctypes.Structure):
+    """include/pinmem_hip.h pm_geo_image: resize, pad and crop window of one image (host copy for pm_resample_tables, device array for pm_resample_crop_u8)."""
+    _fields_ = [('h_in', c_int32), ('w_in', c_int32), ('h', c_int32), ('w', c_int32), ('pad_h', c_int32), ('pad_w', c_int32), ('y1', c_int32), ('x1', c_int32)]
+
+
+RESAMPLE_MAX_TAPS = 24                     # include/pinmem_hip.h PM_RESAMPLE_MAX_TAPS
+RESAMPLE_REC = RESAMPLE_MAX_TAPS + 2       # PM_RESAMPLE_REC
+
+
 class PmConvEpilogue(ctypes.Structure):
     _fields_ = [('struct_size', c_int64), ('bias', c_void_p), ('scale', c_void_p), ('shift', c_void_p), ('residual', c_void_p),
                 ('residual_pitch', c_int64), ('relu', c_int32), ('bn_partials', c_void_p), ('bn_partials_bytes', c_int64)]
@@ -58,7 +67,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 410          # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 420          # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -131,6 +140,8 @@ SIGNATURES = {
     'pm_augment_workspace': (_sz, [_i]),
     'pm_augment_u8': (_i, [_vp, _i, _i, _i, _vp, c_int32, POINTER(c_float), POINTER(c_float), _vp, _vp, _vp, _sz, _vp]),
     'pm_labels_u8_flip_to_i64': (_i, [_vp, _i, _i, _i, _vp, c_int32, _vp, _vp]),
+    'pm_resample_tables': (_i, [_vp, c_int32, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'pm_resample_crop_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, c_int32, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'pm_nchw_to_nhwc': (_i, [_vp, _i, _T, _vp]),
     'pm_nhwc_to_nchw': (_i, [_T, _vp, _vp]),
     'pm_label_nearest': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),

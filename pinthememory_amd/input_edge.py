@@ -12,6 +12,10 @@ the int64 widening are two small kernels on that same stream (`pm_image_u8_to_nh
 The photometric augmentation the reference's training scripts run per image on the host before ToTensor (`--color_aug 0.5 --gblur`, datasets/__init__.py:63-95;
 the hard ColorJitter(0.8, 0.8, 0.8, 0.3) + blur of the meta-test domains, :128-144; RandomHorizontallyFlip) runs here on the uint8 pixels already in HBM
 (`pm_augment_u8`, `pm_labels_u8_flip_to_i64`): `PhotometricAugment` draws the per-image parameters on the host, the prefetcher launches the kernels on its side stream.
+
+In front of it, the joint transform of the same scripts -- RandomSizeAndCrop (transforms/joint_transforms.py:414-444: bicubic resize by a random scale, nearest for the
+mask, pad, random crop) -- runs on the uint8 pixels in HBM too, for the crop window alone and with PIL's bytes (`pm_resample_crop_u8`): `GeometricAugment` draws scale
+and crop origin. The reference's order is kept: joint transforms, image-only transforms, ToTensor.
 """
 import torch
 
@@ -98,6 +102,66 @@ class PhotometricAugment:
         return arr
 
 
+class GeometricAugment:
+    """Per-image geometry of the device-side RandomSizeAndCrop (`pm_resample_crop_u8`), drawn on the host with the DISTRIBUTIONS of the reference's
+    joint_transforms.RandomSizeAndCrop(crop_size, crop_nopad, scale_min, scale_max, ignore_index, pre_size) and its RandomCrop:
+      scale_amt = (pre_size / shorter edge, or 1) * U[scale_min, scale_max];  w, h = int(W * scale_amt), int(H * scale_amt);
+      crop_nopad=False: an axis shorter than the crop is padded on both sides by (t - size) // 2 + 1 (image 0, mask ignore_index);
+      crop origin: a uniform integer in [0, w - tw] (inclusive, w the padded width); with a centroid (x, y) -- scaled to int(c * scale_amt) and, as in the reference,
+      NOT shifted by the pad -- a uniform integer in [c - tw, c] clamped to [0, w - tw], so the crop covers the centroid wherever one fits.
+    crop_nopad=True is served while the resized image holds the crop; the reference then shrinks the crop to the shorter edge and resamples it back through Resize,
+    which this class does not do: NotImplementedError.
+
+    The STREAM of random numbers is this class's own, as PhotometricAugment's: image j since construction (counted across calls) draws from a host torch.Generator
+    seeded with (seed, j), so the result is the same for the same seed and sequence of images whatever the call sizes. `last` keeps the raw draws of the latest call."""
+
+    def __init__(self, crop_size, scale_min=0.5, scale_max=2.0, pre_size=None, crop_nopad=False, ignore_index=255, seed=0):
+        self.crop = (int(crop_size), int(crop_size)) if isinstance(crop_size, (int, float)) else (int(crop_size[0]), int(crop_size[1]))
+        assert 0 < scale_min <= scale_max and min(self.crop) > 0 and 0 <= ignore_index <= 255
+        self.scale_min, self.scale_max, self.pre_size, self.crop_nopad, self.ignore_index, self.seed = scale_min, scale_max, pre_size, crop_nopad, ignore_index, seed
+        self.count = 0          # images sampled so far
+        self.last = None
+
+    def sample(self, sizes, centroids=None):
+        """K.GeoParams for len(sizes) images. sizes: (H, W) per image; centroids: None, or per image None / (x, y) in source pixels (the dataset chooses them)."""
+        n = len(sizes)
+        centroids = [None] * n if centroids is None else list(centroids)
+        assert len(centroids) == n
+        th, tw = self.crop
+        geo = K.GeoParams(n, self.crop, self.ignore_index)
+        last = dict(u=[], scale=[], size=[], pad=[], origin=[], centroid=[])
+        for i, (H, W) in enumerate(sizes):
+            g = torch.Generator().manual_seed((self.seed * 1000003 + self.count + i) & 0x7fffffffffffffff)
+            u = torch.rand(3, generator=g, dtype=torch.float64).tolist()
+            scale = 1.0 if self.pre_size is None else self.pre_size / min(H, W)
+            scale *= self.scale_min + (self.scale_max - self.scale_min) * u[0]      # random.uniform
+            w, h = int(W * scale), int(H * scale)
+            if w < 1 or h < 1:
+                raise ValueError('image %d: %d x %d at scale %g has no pixel left' % (i, H, W, scale))
+            if self.crop_nopad:
+                if th > h or tw > w:
+                    raise NotImplementedError('crop_nopad=True with a %d x %d image under a %d x %d crop: the reference shrinks the crop and resamples it through '
+                                              'Resize, which the device path does not do' % (h, w, th, tw))
+                pad_h = pad_w = 0
+            else:
+                pad_h = (th - h) // 2 + 1 if th > h else 0
+                pad_w = (tw - w) // 2 + 1 if tw > w else 0
+            max_x, max_y = w + 2 * pad_w - tw, h + 2 * pad_h - th
+            c = None if centroids[i] is None else (int(centroids[i][0] * scale), int(centroids[i][1] * scale))
+            if c is None:
+                x1, y1 = min(int(u[1] * (max_x + 1)), max_x), min(int(u[2] * (max_y + 1)), max_y)
+            else:                                                             # randint(c - t, c), then clamped into the image
+                x1 = min(max_x, max(0, c[0] - tw + min(int(u[1] * (tw + 1)), tw)))
+                y1 = min(max_y, max(0, c[1] - th + min(int(u[2] * (th + 1)), th)))
+            p = geo.images[i]
+            p.h_in, p.w_in, p.h, p.w, p.pad_h, p.pad_w, p.y1, p.x1 = int(H), int(W), h, w, pad_h, pad_w, y1, x1
+            for k, v in zip(('u', 'scale', 'size', 'pad', 'origin', 'centroid'), (u, scale, (h, w), (pad_h, pad_w), (y1, x1), c)):
+                last[k].append(v)
+        self.count += n
+        self.last = last
+        return geo
+
+
 def hard_flags(label_shape, hard_domains):
     """One bool per image of a [B, D, H, W] label batch after the domain axis merged into the batch (image b * D + d): is d one of hard_domains?"""
     if not hard_domains:
@@ -110,6 +174,13 @@ def hard_flags(label_shape, hard_domains):
     return [(i % d) in hard_domains for i in range(total)]
 
 
+def sample_geometry(geometry, image_shape, meta=None):
+    """geometry.sample for a merged [N, Hs, Ws, 3] batch: per-image sizes and centroids from the source's third item (a dict), else every image fills its slab."""
+    n, hs, ws = image_shape[0], image_shape[1], image_shape[2]
+    meta = meta or {}
+    return geometry.sample(meta.get('sizes') or [(hs, ws)] * n, meta.get('centroids'))
+
+
 class DevicePrefetcher:
     """Keeps `depth` batches in flight: H2D of the uint8 buffers and the u8 -> NHWC4 float / int64 kernels run on a side stream, an
     event hands the result to the compute stream (`next()` makes the current stream wait on it; the host never blocks on the GPU
@@ -118,9 +189,12 @@ class DevicePrefetcher:
 
     augment (a PhotometricAugment, default None = exactly the plain conversion): every batch is sampled for and augmented on the side stream, image and labels alike.
     hard_domains: indices on the D axis of the source's [B, D, ...] batches whose images get the hard augmentation (the meta-test domains); an attribute the caller may
-    reassign between batches -- it is read when a batch is ISSUED, i.e. `depth` batches before that batch is returned."""
+    reassign between batches -- it is read when a batch is ISSUED, i.e. `depth` batches before that batch is returned.
+    geometry (a GeometricAugment, default None = no geometry): every batch is resized, padded and cropped on the side stream first (`pm_resample_crop_u8`); the plain
+    conversion or the augmentation then runs on the crop. The source may then yield a third item, a dict with per-image 'sizes' ((H, W): the image lies in the
+    top-left corner of its slab) and / or 'centroids'; without it every image fills its slab."""
 
-    def __init__(self, source, depth=1, device=None, augment=None, hard_domains=None):
+    def __init__(self, source, depth=1, device=None, augment=None, hard_domains=None, geometry=None):
         assert torch.cuda.is_available(), 'the input edge stages into HBM: needs a GPU'
         self.src, self.depth = iter(source), depth
         self.host_ring = max(1, len(getattr(source, 'bufs', [])) or 1)          # pinned buffers the source rotates through
@@ -128,14 +202,15 @@ class DevicePrefetcher:
         self.side = torch.cuda.Stream(device=self.dev)
         self.slots, self.copied, self.ready = [None] * (depth + 1), [], []
         self.n = 0
-        self.augment, self.hard_domains = augment, hard_domains
+        self.augment, self.hard_domains, self.geometry = augment, hard_domains, geometry
         for _ in range(depth):
             self._issue()
 
     def _issue(self):
         if len(self.copied) >= self.host_ring:
             self.copied.pop(0).synchronize()                                   # the buffer the source is about to refill has left the host
-        img_h, lab_h = next(self.src)
+        item = next(self.src)
+        img_h, lab_h = item[0], item[1]
         k = self.n % len(self.slots)
         self.n += 1
         h, w = img_h.shape[-3:-1]
@@ -148,6 +223,8 @@ class DevicePrefetcher:
             lab_d.copy_(lab_h.reshape(-1, h, w), non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.side)
+            if self.geometry is not None:                                      # RandomSizeAndCrop first: what follows sees the crop
+                img_d, lab_d = K.resample_crop_u8(img_d, lab_d, sample_geometry(self.geometry, img_d.shape, item[2] if len(item) > 2 else None))
             if self.augment is None:
                 x = ops.nchw(K.image_u8_to_nhwc4(img_d))
                 gt = K.labels_u8_to_i64(lab_d)
