@@ -459,6 +459,39 @@ size_t pm_label_class_weights_workspace(int n);
 int pm_label_class_weights(const int64_t* labels, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* Relaxed-border training (--jointwtborder): RelaxedBoundaryLossToTensor (transforms/transforms.py:99-148) and ImgWtLossSoftNLL (loss.py:182-263) without the
+ * [n, C + 1, H, W] multi-hot target, the host histogram, the per-image host sync and the up-sampled logits. A pixel's target is a set of classes in one uint32: bit c =
+ * class c < classes, bit `classes` = the ignore class; classes <= 31.
+ *   pm_relax_border_bits: bits[b][Y][X] = OR over the (2 border + 1)^2 window of the one-hot of each neighbour's class; label 255, every other label outside
+ *     [0, classes) and neighbours outside the image count as the ignore class; a pixel whose own class has its bit in strict_mask keeps its plain one-hot
+ *     (cfg.STRICTBORDERCLASS). border 0..3 (0: the one-hot of the labels).
+ *   pm_multihot_to_bits: the reference's uint8 target [n][planes = classes + 1][H][W] (non-zero = set) packed into the same words.
+ *   pm_relax_class_weights: calculate_weights (loss.py:208-220): hist_c = pixels whose set holds c / set bits of the image (ignore bit included), c = 0..classes, then
+ *     the expression of pm_label_class_weights in double, bit-equal to numpy; weights float [n][classes] (the ignore entry is dropped). per_batch: one histogram over
+ *     all images in every row. An image without any set bit gets weights of 1.
+ *   pm_upsample_relax_*: bilinear up-sampling (align_corners) of logits [n][h][w][C] (float, `pitch` floats between pixels, channels [0, C) read) fused with the loss.
+ *     With S the real classes of a pixel's set, k = |S|, p = softmax(inv_temp z): term = - W_S log(sum of p over S), W_S = (sum over S of
+ *     weights[b * weight_stride + c]) / k (weight_stride 0: one row for the batch); k = 0 ignores the pixel. loss_i = sum of terms / (valid_i + 1), loss = sum_i loss_i / n.
+ *     loss_out holds pm_upsample_relax_loss_floats(n) = 2 + 2 n floats: [0] loss, [1] valid pixels of the batch, [2 + i] loss_i, [2 + n + i] (valid_i + 1) n.
+ *     The field is T[n][H][w][C] of W_S (p - [c in S] p / P_S) reduced over the hi-res columns (pm_upsample_relax_field_bytes; 0: the rows do not fit LDS, the
+ *     _fwd_field call then returns PM_EUNSUPPORTED while _fwd serves every shape); _bwd_field is the row pass: dlogits = gscale inv_temp / loss_out[2 + n + i] x (T
+ *     reduced over the supporting hi-res rows), channels [0, C) of every pixel written, dpitch floats between pixels. No atomics on floats: deterministic. */
+int pm_relax_border_bits(const int64_t* labels, int n, int H, int W, int classes, int border, uint32_t strict_mask, uint32_t* bits, void* stream);
+int pm_multihot_to_bits(const uint8_t* multihot, int n, int planes, int H, int W, uint32_t* bits, void* stream);
+size_t pm_relax_class_weights_workspace(int n);
+int pm_relax_class_weights(const uint32_t* bits, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights, void* ws,
+                           size_t ws_bytes, void* stream);
+size_t pm_upsample_relax_workspace(int n, int H, int W);
+size_t pm_upsample_relax_loss_floats(int n);
+size_t pm_upsample_relax_field_bytes(int n, int h, int w, int C, int H, int W);
+int pm_upsample_relax_fwd(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W, const float* weights,
+                          int64_t weight_stride, float* loss_out, void* ws /* pm_upsample_relax_workspace */, size_t ws_bytes, void* stream);
+int pm_upsample_relax_fwd_field(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W,
+                                const float* weights, int64_t weight_stride, float* loss_out, float* field, void* ws /* pm_upsample_relax_workspace */,
+                                size_t ws_bytes, void* stream);
+int pm_upsample_relax_bwd_field(int n, int h, int w, int C, float inv_temp, int H, int W, const float* loss_out, const float* gscale /* nullable: 1 */,
+                                const float* field, float* dlogits, int64_t dpitch, void* stream);
+
 /* Validation sweep (train.py:847-939 per batch: Upsample -> criterion -> output.max(1)[1] -> fast_hist) in one pass over the labels, the up-sampled logits never
  * materialised. Inputs and loss_out as pm_upsample_ce_fwd (same interpolation expression, same fixed-order reduce). Per hi-res pixel: pred = the LOWEST class index
  * among the maxima of the interpolated logits; hist[label][pred] += 1 for 0 <= label < C (fast_hist's mask, utils/misc.py:65-70; 255 and any other value are

@@ -170,11 +170,11 @@ __device__ __forceinline__ float ce_exp_sum(float* v, float mx, int C) {
   return se;
 }
 
-// The field kernels: w (softmax - onehot) of one pixel (v from ce_exp_sum) into A (left-tap weight: stays in the pixel's low-res column) and B (right-tap weight: owed
+// The field kernels: w (softmax - hot) of one pixel (v from ce_exp_sum; hot = the one-hot entry, or the relaxed form's p / P_S on the classes of the set) into A (left-tap weight: stays in the pixel's low-res column) and B (right-tap weight: owed
 // to the next column). w multiplies the difference alone: every other expression stays the unweighted one, so w = 1 leaves its bits.
 template <bool WT>
-__device__ __forceinline__ void ce_grad_tap(float p, bool hot, float wl, float wa, float wb, float& A, float& B) {
-  float gq = p - (hot ? 1.f : 0.f);
+__device__ __forceinline__ void ce_grad_tap(float p, float hot, float wl, float wa, float wb, float& A, float& B) {
+  float gq = p - hot;
   if constexpr (WT) gq *= wl;
   A += wa * gq, B += wb * gq;
 }
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
           const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
           for (int c = 0; c < CR; ++c)
-            if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab, wl, wa, wb, A[c], B[c]);
+            if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab ? 1.f : 0.f, wl, wa, wb, A[c], B[c]);
         }
       }
     }
@@ -529,7 +529,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
         const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab, wl, wa, wb, A[c], B[c]);
+          if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab ? 1.f : 0.f, wl, wa, wb, A[c], B[c]);
       }
     }
     if (lane == 63) {
@@ -1029,8 +1029,10 @@ __device__ __forceinline__ double lcw_weight(double hist, double ub, int norm) {
 }
 
 // block = one output row b: 32 classes x 8 slices of the count blocks of image b (per_batch: of every image)
-__global__ __launch_bounds__(256) void label_weights_kernel(const unsigned* __restrict__ counts, int nblk, int n, int classes, double ub, int norm, int per_batch,
-                                                            float* __restrict__ weights) {
+// bins: the counted entries the divisor sums over (classes; classes + 1 for border sets, whose ignore bit is counted and gets no weight); empty_one: a row without
+// any count is all ones instead of NaN
+__global__ __launch_bounds__(256) void label_weights_kernel(const unsigned* __restrict__ counts, int nblk, int n, int classes, int bins, int empty_one, double ub, int norm,
+                                                            int per_batch, float* __restrict__ weights) {
   __shared__ unsigned long long tot[MAXC];
   const int b = blockIdx.x, c = threadIdx.x & (MAXC - 1), sl = threadIdx.x / MAXC;
   if (threadIdx.x < MAXC) tot[threadIdx.x] = 0ull;
@@ -1042,9 +1044,9 @@ __global__ __launch_bounds__(256) void label_weights_kernel(const unsigned* __re
   __syncthreads();
   if ((int)threadIdx.x < classes) {
     unsigned long long all = 0ull;
-    for (int k = 0; k < classes; ++k) all += tot[k];
+    for (int k = 0; k < bins; ++k) all += tot[k];
     const double hist = (double)tot[threadIdx.x] / (double)all;      // 0 / 0 = NaN for an image without a countable pixel, as numpy
-    weights[(long)b * classes + threadIdx.x] = (float)lcw_weight(hist, ub, norm);
+    weights[(long)b * classes + threadIdx.x] = empty_one && all == 0ull ? 1.f : (float)lcw_weight(hist, ub, norm);
   }
 }
 }  // namespace
@@ -1061,6 +1063,412 @@ extern "C" int pm_label_class_weights(const int64_t* labels, int n, int H, int W
   const int nblk = lcw_blocks(hw);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(label_count_kernel, dim3(nblk, n), dim3(256), 0, st, labels, hw, classes, (unsigned*)ws);
-  hipLaunchKernelGGL(label_weights_kernel, dim3(n), dim3(256), 0, st, (const unsigned*)ws, nblk, n, classes, upper_bound, norm != 0, per_batch != 0, weights);
+  hipLaunchKernelGGL(label_weights_kernel, dim3(n), dim3(256), 0, st, (const unsigned*)ws, nblk, n, classes, classes, 0, upper_bound, norm != 0, per_batch != 0, weights);
   return pm_check_launch("label_class_weights");
+}
+
+
+// ---- relaxed-border training: RelaxedBoundaryLossToTensor (transforms/transforms.py:99-148) + ImgWtLossSoftNLL (loss.py:182-263) ---------------------------------
+// The third label form of the pixel body. A pixel's target is a SET of classes -- one uint32, bit c = class c, bit C = the ignore class --: the classes of the
+// (2 border + 1)^2 window around it, built on the device from the int64 labels (rx_border_kernel) or packed from the reference's uint8 multi-hot (rx_pack_kernel).
+// With S the real classes of the set, k = |S|, p = softmax(z) and P_S = sum of p over S, the reference's max(p_c, P_S) is P_S for every c in S, so the pixel's term is
+//   - W_S log P_S,  W_S = (sum of w_c over S) / k,        gradient  W_S (p_j - [j in S] p_j / P_S);
+// k = 0 ignores the pixel. Image i: sum of terms / (valid_i + 1); batch: sum over images / n. Classes outside S contribute exactly nothing (the reference multiplies
+// 0 by log p_c there: NaN once p_c underflows). The interpolation is ce_lerp, the row staging ce_stage_rows, the exponentials ce_exp_sum, the field scheme the one of
+// ce_fused_rows_kernel (lane group = low-res column, A / B sums, exchange through LDS, fixed order everywhere) and the row pass ce_bwd_cols_kernel itself.
+namespace {
+constexpr int RX_MAXC = 31;            // bit C is the ignore class
+constexpr int RX_MAX_BORDER = 3;
+constexpr int RX_COLS = 1024;          // label columns per block of the border kernel
+
+// block = (hi-res row Y of image b, column chunk): the 2 border + 1 label rows around Y as class bytes in LDS (outside the image and every label that is no class: the
+// ignore class), then the OR over the window. strict: a pixel whose own class is in the mask keeps its one-hot (cfg.STRICTBORDERCLASS).
+__global__ __launch_bounds__(256) void rx_border_kernel(const int64_t* __restrict__ labels, int H, int W, int classes, int border, unsigned strict,
+                                                        uint32_t* __restrict__ bits) {
+  __shared__ unsigned char rows[2 * RX_MAX_BORDER + 1][RX_COLS + 2 * RX_MAX_BORDER];
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);      // neighbouring rows (which share 2 border of their label rows) on one XCD's L2
+  const int Y = bid % H, b = bid / H;
+  const int X0 = (int)blockIdx.y * RX_COLS, ncol = min(RX_COLS, W - X0), span = ncol + 2 * border;
+  for (int r = 0; r <= 2 * border; ++r) {
+    const int yy = Y + r - border;
+    for (int i = threadIdx.x; i < span; i += 256) {
+      const int xx = X0 + i - border;
+      int cls = classes;
+      if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+        const int l = ce_label_byte(labels[((long)b * H + yy) * W + xx]);
+        if (l < classes) cls = l;
+      }
+      rows[r][i] = (unsigned char)cls;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncol; i += 256) {
+    const unsigned own = rows[border][i + border];
+    unsigned s = 0u;
+    if ((strict >> own) & 1u) {
+      s = 1u << own;
+    } else {
+      for (int r = 0; r <= 2 * border; ++r)
+        for (int d = 0; d <= 2 * border; ++d) s |= 1u << rows[r][i + d];
+    }
+    bits[((long)b * H + Y) * W + X0 + i] = s;
+  }
+}
+
+// uint8 multi-hot [n][planes][hw] (non-zero = set) -> the same words; blockIdx.y = image
+__global__ __launch_bounds__(256) void rx_pack_kernel(const uint8_t* __restrict__ mh, long hw, int planes, uint32_t* __restrict__ bits) {
+  const uint8_t* src = mh + (long)blockIdx.y * planes * hw;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < hw; i += (long)gridDim.x * 256) {
+    unsigned s = 0u;
+    for (int c = 0; c < planes; ++c) s |= src[(long)c * hw + i] ? 1u << c : 0u;
+    bits[(long)blockIdx.y * hw + i] = s;
+  }
+}
+
+// Pixels whose set holds class c, c = 0..31, in the count-row layout of label_count_kernel (label_weights_kernel folds them). A wave counts one class per ballot and
+// keeps class c's count in lane c; integer adds only.
+__global__ __launch_bounds__(256) void rx_count_kernel(const uint32_t* __restrict__ bits, long hw, unsigned* __restrict__ counts) {
+  __shared__ unsigned cnt[MAXC];
+  if (threadIdx.x < MAXC) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t* src = bits + (long)blockIdx.y * hw;
+  const int lane = threadIdx.x & 63;
+  unsigned mine = 0u;
+  for (long i0 = (long)blockIdx.x * 256; i0 < hw; i0 += (long)gridDim.x * 256) {      // uniform trip count: every lane votes in every ballot
+    const long i = i0 + threadIdx.x;
+    const unsigned s = i < hw ? src[i] : 0u;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const unsigned v = (unsigned)__popcll(__ballot((s >> c) & 1u));
+      if (lane == c) mine += v;
+    }
+  }
+  if (lane < MAXC && mine) atomicAdd(&cnt[lane], mine);
+  __syncthreads();
+  if (threadIdx.x < MAXC) counts[((long)blockIdx.y * gridDim.x + blockIdx.x) * MAXC + threadIdx.x] = cnt[threadIdx.x];
+}
+
+// One pixel whose set holds the real classes S (not empty), v[0..C) its logits and mx their maximum: v becomes exp(v - mx), se their sum, ps the sum over S, wbar the
+// mean weight over S; returns the pixel's loss term - wbar log P_S.
+template <int C_>
+__device__ __forceinline__ float rx_term(float* v, float mx, unsigned S, const float* wsm, int C, float& se, float& ps, float& wbar) {
+  se = ce_exp_sum<C_, true>(v, mx, C);
+  float ws = 0.f;
+  ps = 0.f;
+#pragma unroll
+  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+    if (c < C && ((S >> c) & 1u)) ps += v[c], ws += wsm[c];
+  wbar = ws / (float)__popc(S);
+  return wbar * (logf(se) - logf(ps));
+}
+// The pixel's logits from the staged rows into v (the expression of interp_logits), returning their maximum
+template <int C_>
+__device__ __forceinline__ float rx_lerp_rows(const pm_lerp& ly, const pm_lerp& lx, const float* L0, const float* L1, int CP, int C, float* v) {
+  const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+    if (c < C) mx = fmaxf(mx, v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]));
+  return mx;
+}
+
+// Flat forward (any shape): blockIdx.y = image, the x blocks stride over its pixels, taps from global memory; (sum of terms, valid pixels) per block.
+template <int C_>
+__global__ __launch_bounds__(256) void rx_fwd_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part) {
+  __shared__ float wsm[MAXC];
+  __shared__ float sm[2][4];
+  const int C = C_ > 0 ? C_ : g.C;
+  const int b = blockIdx.y;
+  const long total = (long)g.H * g.W;
+  const uint32_t* src = bits + (long)b * total;
+  const unsigned real = (1u << C) - 1u;
+  ce_stage_weights(g, b, wsm);
+  __syncthreads();
+  float lsum = 0.f, lcnt = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const unsigned S = src[i] & real;
+    if (!S) continue;
+    const int X = (int)(i % g.W), Y = (int)(i / g.W);
+    const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h), lx = pm_ac_lerp(g.sx, X, g.w);
+    float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, se, ps, wbar;
+    interp_logits<C_>(g, b, ly, lx, v);
+#pragma unroll
+    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+      if (c < C) mx = fmaxf(mx, v[c]);
+    lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
+    lcnt += 1.f;
+  }
+  if (ce_block_partial<4>(lsum, lcnt, sm)) {
+    const long pb = (long)b * gridDim.x + blockIdx.x;
+    part[pb * 2] = lsum, part[pb * 2 + 1] = lcnt;
+  }
+}
+
+// Row-staged forward, the shape of ce_fwd_rows_kernel: block = one hi-res row, its two low-res logit rows in LDS, lane = hi-res pixel.
+template <int C_>
+__global__ __launch_bounds__(256) void rx_fwd_rows_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part) {
+  extern __shared__ float L[];
+  __shared__ float wsm[MAXC];
+  __shared__ float sm[2][4];
+  const int C = C_ > 0 ? C_ : g.C;
+  const int CP = C | 1;
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
+  const int Y = bid % g.H, b = bid / g.H;
+  const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
+  float* L0 = L;
+  float* L1 = L + (size_t)g.w * CP;
+  const uint32_t* brow = bits + ((long)b * g.H + Y) * g.W;
+  const unsigned real = (1u << C) - 1u;
+  ce_stage_weights(g, b, wsm);
+  ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, 256, L0, L1);
+  __syncthreads();
+  float lsum = 0.f, lcnt = 0.f;
+  for (int X = threadIdx.x; X < g.W; X += 256) {
+    const unsigned S = brow[X] & real;
+    if (!S) continue;
+    float v[C_ > 0 ? C_ : MAXC], se, ps, wbar;
+    const float mx = rx_lerp_rows<C_>(ly, pm_ac_lerp(g.sx, X, g.w), L0, L1, CP, C, v);
+    lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
+    lcnt += 1.f;
+  }
+  if (ce_block_partial<4>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
+}
+
+// Training forward: the loss and the column-reduced field T[b][Y][x][c] in one sweep -- ce_fused_rows_kernel with the set words (staged in LDS, four bytes a pixel)
+// in the place of the label bytes and W_S (p - [c in S] p / P_S) in the place of w (softmax - onehot).
+template <int C_, int PARTS>
+__global__ __launch_bounds__(256) void rx_fused_rows_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part, float* __restrict__ T) {
+  extern __shared__ float L[];
+  __shared__ float carry[MAXC];
+  __shared__ float wsm[MAXC];
+  __shared__ float sm[2][4];
+  constexpr int CR = C_ > 0 ? C_ : MAXC;
+  const int C = C_ > 0 ? C_ : g.C;
+  const int CP = C | 1;
+  const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
+  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
+  const int Y = bid % g.H, b = bid / g.H;
+  const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
+  float* L0 = L;
+  float* L1 = L + (size_t)g.w * CP;                                   // (+ C floats of slack behind it: bufB holds one column more than a round)
+  uint32_t* set = reinterpret_cast<uint32_t*>(L1 + (size_t)g.w * CP + C);
+  const uint32_t* brow = bits + ((long)b * g.H + Y) * g.W;
+  const unsigned real = (1u << C) - 1u;
+  ce_stage_weights(g, b, wsm);
+  for (int X = tid; X < g.W; X += nt) set[X] = brow[X] & real;
+  ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1);
+  __syncthreads();
+  float lsum = 0.f, lcnt = 0.f;
+  const int R = nt / PARTS;                       // low-res columns per round
+  const int rounds = (g.w + R - 1) / R;
+  for (int rd = 0; rd < rounds; ++rd) {
+    if (rd > 0) {                                 // the previous round recycled the staged rows as its exchange buffers
+      __syncthreads();
+      ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1);
+      __syncthreads();
+    }
+    const int xr0 = rd * R, xr1 = min(g.w, xr0 + R);
+    const int x = xr0 + tid / PARTS, p = tid % PARTS;
+    const bool live = x < xr1;
+    float A[CR], B[CR];
+#pragma unroll
+    for (int c = 0; c < CR; ++c) A[c] = B[c] = 0.f;
+    if (live) {
+      const int j0 = ce_first_ge(g.sx, x, g.w, g.W), j1 = ce_first_ge(g.sx, x + 1, g.w, g.W);
+      const int per = (j1 - j0 + PARTS - 1) / PARTS;
+      const int ja = j0 + p * per, jb = min(j1, ja + per);
+      for (int X = ja; X < jb; ++X) {
+        const unsigned S = set[X];
+        if (!S) continue;
+        const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
+        float v[CR], se, ps, wbar;
+        const float mx = rx_lerp_rows<C_>(ly, lx, L0, L1, CP, C, v);
+        lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
+        lcnt += 1.f;
+        const float inv = 1.f / se, invs = 1.f / ps;
+        const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
+#pragma unroll
+        for (int c = 0; c < CR; ++c)
+          if (c < C) ce_grad_tap<true>(v[c] * inv, (S >> c) & 1u ? v[c] * invs : 0.f, wbar, wa, wb, A[c], B[c]);
+      }
+    }
+    if constexpr (PARTS > 1) {
+#pragma unroll
+      for (int o = 1; o < PARTS; o <<= 1)
+#pragma unroll
+        for (int c = 0; c < CR; ++c)
+          if (c < C) A[c] += __shfl_xor(A[c], o, 64), B[c] += __shfl_xor(B[c], o, 64);
+    }
+    __syncthreads();                            // every lane is done with the staged rows: they become the exchange buffers
+    float* bufA = L0;                           // A of column x         -> bufA[x - xr0]
+    float* bufB = L1;                           // B of column x (owed to column x + 1) -> bufB[x - xr0 + 1]; bufB[0] = carry of the previous round
+    if (live && p == 0) {
+#pragma unroll
+      for (int c = 0; c < CR; ++c)
+        if (c < C) {
+          bufA[(x - xr0) * C + c] = A[c];
+          bufB[(x - xr0 + 1) * C + c] = B[c];
+        }
+    }
+    if (tid < C) bufB[tid] = rd == 0 ? 0.f : carry[tid];
+    __syncthreads();
+    float* Trow = T + (((long)b * g.H + Y) * g.w + xr0) * C;
+    for (int i = tid; i < (xr1 - xr0) * C; i += nt) Trow[i] = bufB[i] + bufA[i];
+    if (tid < C) carry[tid] = bufB[(xr1 - xr0) * C + tid];
+  }
+  if (ce_block_partial<0>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
+}
+
+// n x per (sum of terms, valid pixels) partials, image-major -> out[0] = sum_i loss_i / n, out[1] = valid pixels of the batch, out[2 + i] = loss_i =
+// terms_i / (valid_i + 1), out[2 + n + i] = (valid_i + 1) n: what the row pass divides image i by. One block, the tree of ce_final_kernel per image, in double.
+__global__ __launch_bounds__(CE_FINAL_T) void rx_final_kernel(const float* __restrict__ part, int per, int n, float* __restrict__ out) {
+  __shared__ double s[2][CE_FINAL_T];
+  double loss = 0.0, valid = 0.0;
+  for (int b = 0; b < n; ++b) {
+    ce_fold_pairs(part, (long)b * per, per, s);
+    if (threadIdx.x == 0) {
+      const double li = s[0][0] / (s[1][0] + 1.0);
+      out[2 + b] = (float)li;
+      out[2 + n + b] = (float)((s[1][0] + 1.0) * (double)n);
+      loss += li;
+      valid += s[1][0];
+    }
+    __syncthreads();      // s is rewritten for the next image
+  }
+  if (threadIdx.x == 0) {
+    out[0] = (float)(loss / (double)n);
+    out[1] = (float)valid;
+  }
+}
+
+// the field kernel's plan: fused_plan with four bytes per staged label instead of one
+inline FusedPlan rx_plan(const CEGeom& g) {
+  FusedPlan p = fused_plan(g);
+  p.lds += (size_t)3 * ((size_t)(g.W + 15) / 16 * 16);
+  return p;
+}
+
+int rx_fill(CEGeom& g, const char* who, const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, int H, int W) {
+  PM_REQUIRE(logits && n > 0 && h > 0 && w > 0 && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
+  PM_REQUIRE(C >= 1 && C <= RX_MAXC, PM_EUNSUPPORTED, "%s: classes %d not in 1..%d", who, C, RX_MAXC);
+  PM_REQUIRE(pitch >= C, PM_EINVAL, "%s: pitch %lld < %d classes", who, (long long)pitch, C);
+  g.logits = logits, g.lp = (long)pitch, g.n = n, g.h = h, g.w = w, g.C = C;
+  g.labels = nullptr, g.H = H, g.W = W;
+  g.sy = pm_ac_scale(h, H), g.sx = pm_ac_scale(w, W), g.inv_temp = inv_temp;
+  g.wts = nullptr, g.wstride = 0, g.per_image = 1;
+  return PM_OK;
+}
+
+int rx_fwd(const char* who, CEGeom& g, const uint32_t* bits, const float* weights, int64_t weight_stride, float* loss_out, float* field, bool want_field, void* ws,
+           size_t ws_bytes, hipStream_t st) {
+  const CEWeights wt{weights, weight_stride, 1};
+  PM_REQUIRE(bits, PM_EINVAL, "%s: null bits", who);
+  if (int e = fill_w(g, wt, who)) return e;
+  PM_REQUIRE(loss_out && ws && ws_bytes >= pm_upsample_relax_workspace(g.n, g.H, g.W) && (field || !want_field), PM_EWORKSPACE, "%s: workspace too small / null field", who);
+  PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "%s: %d images > 65535", who, g.n);
+  int per;
+  if (want_field) {
+    const FusedPlan p = rx_plan(g);
+    PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * g.H <= (1l << 30), PM_EUNSUPPORTED, "%s: logit rows of %d x %d classes do not fit LDS", who, g.w, g.C);
+    per = g.H;
+    auto launch = [&](auto cc, auto pp) {
+      constexpr int CC = decltype(cc)::value, PP = decltype(pp)::value;
+      static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs the opt-in, once per kernel and device
+      (void)optin(reinterpret_cast<const void*>(&rx_fused_rows_kernel<CC, PP>), (int)FUSED_MAX_LDS);
+      hipLaunchKernelGGL((rx_fused_rows_kernel<CC, PP>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, bits, (float*)ws, field);
+    };
+    ce_dispatch(g.C, false, [&](auto cc, auto) {
+      switch (p.parts) {
+        case 1: launch(cc, std::integral_constant<int, 1>{}); break;
+        case 2: launch(cc, std::integral_constant<int, 2>{}); break;
+        case 4: launch(cc, std::integral_constant<int, 4>{}); break;
+        case 8: launch(cc, std::integral_constant<int, 8>{}); break;
+        default: launch(cc, std::integral_constant<int, 16>{}); break;
+      }
+    });
+  } else if (const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float); row_lds <= 48 * 1024 && (long)g.n * g.H <= (1 << 20) && g.W >= 32) {
+    per = g.H;
+    ce_dispatch(g.C, false, [&](auto cc, auto) {
+      hipLaunchKernelGGL((rx_fwd_rows_kernel<decltype(cc)::value>), dim3(g.n * g.H), dim3(256), row_lds, st, g, bits, (float*)ws);
+    });
+  } else {
+    per = wfwd_blocks((long)g.H * g.W);
+    ce_dispatch(g.C, false, [&](auto cc, auto) { hipLaunchKernelGGL((rx_fwd_kernel<decltype(cc)::value>), dim3(per, g.n), dim3(256), 0, st, g, bits, (float*)ws); });
+  }
+  hipLaunchKernelGGL(rx_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)ws, per, g.n, loss_out);
+  return pm_check_launch(who);
+}
+}  // namespace
+
+extern "C" int pm_relax_border_bits(const int64_t* labels, int n, int H, int W, int classes, int border, uint32_t strict_mask, uint32_t* bits, void* stream) {
+  PM_REQUIRE(labels && bits && n > 0 && H > 0 && W > 0, PM_EINVAL, "relax_border_bits: null/empty");
+  PM_REQUIRE(classes >= 1 && classes <= RX_MAXC, PM_EUNSUPPORTED, "relax_border_bits: classes %d not in 1..%d", classes, RX_MAXC);
+  PM_REQUIRE(border >= 0 && border <= RX_MAX_BORDER, PM_EUNSUPPORTED, "relax_border_bits: border %d not in 0..%d", border, RX_MAX_BORDER);
+  const long chunks = ((long)W + RX_COLS - 1) / RX_COLS;
+  PM_REQUIRE((long)n * H <= (1l << 30) && chunks <= 65535, PM_EUNSUPPORTED, "relax_border_bits: %d x %d rows of %d columns", n, H, W);
+  hipLaunchKernelGGL(rx_border_kernel, dim3(n * H, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, labels, H, W, classes, border, strict_mask, bits);
+  return pm_check_launch("relax_border_bits");
+}
+
+extern "C" int pm_multihot_to_bits(const uint8_t* multihot, int n, int planes, int H, int W, uint32_t* bits, void* stream) {
+  PM_REQUIRE(multihot && bits && n > 0 && H > 0 && W > 0, PM_EINVAL, "multihot_to_bits: null/empty");
+  PM_REQUIRE(planes >= 1 && planes <= 32, PM_EUNSUPPORTED, "multihot_to_bits: %d planes not in 1..32", planes);
+  PM_REQUIRE(n <= 65535, PM_EUNSUPPORTED, "multihot_to_bits: %d images > 65535", n);
+  const long hw = (long)H * W;
+  hipLaunchKernelGGL(rx_pack_kernel, dim3(pm_grid_for(hw), n), dim3(256), 0, (hipStream_t)stream, multihot, hw, planes, bits);
+  return pm_check_launch("multihot_to_bits");
+}
+
+extern "C" size_t pm_relax_class_weights_workspace(int n) { return pm_label_class_weights_workspace(n); }
+
+extern "C" int pm_relax_class_weights(const uint32_t* bits, int n, int H, int W, int classes, double upper_bound, int norm, int per_batch, float* weights, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  PM_REQUIRE(bits && weights && n > 0 && H > 0 && W > 0, PM_EINVAL, "relax_class_weights: null/empty");
+  PM_REQUIRE(classes >= 1 && classes <= RX_MAXC, PM_EUNSUPPORTED, "relax_class_weights: classes %d not in 1..%d", classes, RX_MAXC);
+  PM_REQUIRE(n <= 65535, PM_EUNSUPPORTED, "relax_class_weights: %d images > 65535", n);
+  PM_REQUIRE(ws && ws_bytes >= pm_relax_class_weights_workspace(n), PM_EWORKSPACE, "relax_class_weights: workspace too small");
+  const long hw = (long)H * W;
+  const int nblk = lcw_blocks(hw);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rx_count_kernel, dim3(nblk, n), dim3(256), 0, st, bits, hw, (unsigned*)ws);
+  hipLaunchKernelGGL(label_weights_kernel, dim3(n), dim3(256), 0, st, (const unsigned*)ws, nblk, n, classes, classes + 1, 1, upper_bound, norm != 0, per_batch != 0, weights);
+  return pm_check_launch("relax_class_weights");
+}
+
+extern "C" size_t pm_upsample_relax_workspace(int n, int H, int W) {      // one (sum of terms, valid pixels) pair per block of any relaxed forward kernel
+  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H) * 2 * sizeof(float), 256);
+}
+extern "C" size_t pm_upsample_relax_loss_floats(int n) { return (size_t)2 + (size_t)2 * std::max(n, 0); }
+extern "C" size_t pm_upsample_relax_field_bytes(int n, int h, int w, int C, int H, int W) {
+  if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1 || C < 1 || C > RX_MAXC) return 0;
+  CEGeom g{};
+  g.n = n, g.h = h, g.w = w, g.H = H, g.W = W, g.C = C;
+  if (rx_plan(g).lds > FUSED_MAX_LDS || (long)n * H > (1l << 30)) return 0;
+  return (size_t)n * H * w * C * sizeof(float);
+}
+
+extern "C" int pm_upsample_relax_fwd(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W,
+                                     const float* weights, int64_t weight_stride, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
+  CEGeom g;
+  if (int e = rx_fill(g, "upsample_relax_fwd", logits, n, h, w, C, pitch, inv_temp, H, W)) return e;
+  return rx_fwd("upsample_relax_fwd", g, bits, weights, weight_stride, loss_out, nullptr, false, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int pm_upsample_relax_fwd_field(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W,
+                                           const float* weights, int64_t weight_stride, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
+  CEGeom g;
+  if (int e = rx_fill(g, "upsample_relax_fwd_field", logits, n, h, w, C, pitch, inv_temp, H, W)) return e;
+  return rx_fwd("upsample_relax_fwd_field", g, bits, weights, weight_stride, loss_out, field, true, ws, ws_bytes, (hipStream_t)stream);
+}
+// The row pass of ce_bwd_cols_kernel, every image divided by its own out[2 + n + i] (its weighted form reads the divisor of image i at [2 + i] of what it is given).
+extern "C" int pm_upsample_relax_bwd_field(int n, int h, int w, int C, float inv_temp, int H, int W, const float* loss_out, const float* gscale, const float* field,
+                                           float* dlogits, int64_t dpitch, void* stream) {
+  CEGeom g;
+  PM_REQUIRE(dlogits, PM_EINVAL, "upsample_relax_bwd_field: null dlogits");
+  if (int e = rx_fill(g, "upsample_relax_bwd_field", dlogits, n, h, w, C, dpitch, inv_temp, H, W)) return e;
+  PM_REQUIRE(loss_out && field, PM_EINVAL, "upsample_relax_bwd_field: null loss_out / field");
+  PM_REQUIRE(pm_upsample_relax_field_bytes(n, h, w, C, H, W) != 0, PM_EUNSUPPORTED, "upsample_relax_bwd_field: no field for this shape");
+  const long total = (long)n * h * w * C;
+  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
+  hipLaunchKernelGGL(ce_bwd_cols_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, loss_out + n, gscale, dlogits, (long)dpitch);
+  return pm_check_launch("upsample_relax_bwd_field");
 }

@@ -1026,6 +1026,100 @@ def label_class_weights(labels, classes, upper_bound=1.0, norm=False, per_batch=
     return out
 
 
+# ---- relaxed-border training (--jointwtborder): border sets as uint32 words, their class weights, fused up-sample + ImgWtLossSoftNLL (loss.py:182-263) -----------
+# Bit words travel as int32 tensors (torch has no arithmetic on uint32): bit c = class c, bit `classes` = the ignore class.
+def relax_border_bits(labels, classes, border=1, strict_mask=0, out=None):
+    """int64 labels [n,H,W] -> int32 words [n,H,W]: the classes of the (2 border + 1)^2 window around every pixel (RelaxedBoundaryLossToTensor on the device)."""
+    n, H, W = labels.shape
+    labels = labels.contiguous()
+    assert labels.dtype == torch.int64 and labels.is_cuda
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.int32, device=labels.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n * H * W
+    check(_lib().pm_relax_border_bits(labels.data_ptr(), n, H, W, classes, int(border), int(strict_mask) & 0xFFFFFFFF, out.data_ptr(), stream()), 'pm_relax_border_bits')
+    return out
+
+
+def multihot_to_bits(multihot, out=None):
+    """the reference's uint8 target [n, classes + 1, H, W] (non-zero = set) -> the words of relax_border_bits"""
+    n, planes, H, W = multihot.shape
+    multihot = multihot.contiguous()
+    assert multihot.dtype == torch.uint8 and multihot.is_cuda
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.int32, device=multihot.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n * H * W
+    check(_lib().pm_multihot_to_bits(multihot.data_ptr(), n, planes, H, W, out.data_ptr(), stream()), 'pm_multihot_to_bits')
+    return out
+
+
+def relax_class_weights(bits, classes, upper_bound=1.0, norm=False, per_batch=False, out=None):
+    """ImgWtLossSoftNLL.calculate_weights on the device: words [n,H,W] -> float32 [n, classes] weight rows, bit-equal to the numpy expression, no host sync."""
+    n, H, W = bits.shape
+    assert bits.dtype == torch.int32 and bits.is_cuda and bits.is_contiguous()
+    if out is None:
+        out = torch.empty((n, classes), dtype=torch.float32, device=bits.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * classes
+    lib = _lib()
+    nb = lib.pm_relax_class_weights_workspace(n)
+    ws = workspace(nb, bits.device)
+    check(lib.pm_relax_class_weights(bits.data_ptr(), n, H, W, classes, float(upper_bound), int(bool(norm)), int(bool(per_batch)), out.data_ptr(), ptr(ws), nb, stream()),
+          'pm_relax_class_weights')
+    return out
+
+
+def _relax_logits(logits):
+    """NHWC fp32 logits whose pixels are `pitch` floats apart -> the flat arguments (ptr, n, h, w, C, pitch) of the pm_upsample_relax_* entry points"""
+    assert logits.dtype == torch.float32, 'the relaxed-border loss takes fp32 logits'
+    d = tdesc(logits)
+    return d.ptr, d.n, d.h, d.w, d.c, d.pitch
+
+
+def upsample_relax_ok(logits, label_hw):
+    """Can the fused relaxed-loss field kernel take this shape (two low-res logit rows + one row of set words in LDS)?"""
+    n, h, w, C = logits.shape
+    if logits.dtype != torch.float32:      # fp32 tensors only, as pm_upsample_ce_field_bytes answers: the caller composes resize + loss
+        return False
+    return _sizes(('relax', logits.shape, tuple(label_hw)), lambda: _lib().pm_upsample_relax_field_bytes(n, h, w, C, label_hw[0], label_hw[1])) != 0
+
+
+def _relax_fwd(logits, bits, weights, inv_temp, out, want_field):
+    n, H, W = bits.shape
+    assert bits.dtype == torch.int32 and bits.is_contiguous() and bits.shape[0] == logits.shape[0]
+    lib = _lib()
+    need = lib.pm_upsample_relax_loss_floats(n)
+    if out is None:
+        out = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
+    largs = _relax_logits(logits)
+    field = torch.empty(lib.pm_upsample_relax_field_bytes(*largs[1:5], H, W) // 4, dtype=torch.float32, device=logits.device) if want_field else None
+    nb = lib.pm_upsample_relax_workspace(n, H, W)
+    ws = workspace(nb, logits.device)
+    wt, stride = _wce_weights(weights, logits)
+    name = 'pm_upsample_relax_fwd' + ('_field' if want_field else '')
+    fargs = (field.data_ptr(),) if want_field else ()
+    check(getattr(lib, name)(*largs, inv_temp, bits.data_ptr(), H, W, wt.data_ptr(), stride, out.data_ptr(), *fargs, ptr(ws), nb, stream()), name)
+    return (out, field) if want_field else out
+
+
+def upsample_relax_fwd(logits, bits, weights, inv_temp=1.0, out=None):
+    """-> loss_out[2 + 2n]: [0] the loss, [1] the valid pixels, [2 + i] the loss of image i, [2 + n + i] (valid_i + 1) n (include/pinmem_hip.h)."""
+    return _relax_fwd(logits, bits, weights, inv_temp, out, False)
+
+
+def upsample_relax_fwd_field(logits, bits, weights, inv_temp=1.0, out=None):
+    """Training forward: -> (loss_out[2 + 2n], field)."""
+    return _relax_fwd(logits, bits, weights, inv_temp, out, True)
+
+
+def upsample_relax_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp=1.0):
+    H, W = label_hw
+    dl = _ce_dlogits(logits)
+    dptr, n, h, w, C, dpitch = _relax_logits(dl)
+    check(_lib().pm_upsample_relax_bwd_field(n, h, w, C, inv_temp, H, W, loss_out.data_ptr(), ptr(gscale), field.data_ptr(), dptr, dpitch, stream()),
+          'pm_upsample_relax_bwd_field')
+    return dl
+
+
 # ---- validation sweep: loss + argmax + confusion matrix of the up-sampled logits (train.py:847-939) -------------------------------
 def upsample_eval_ok(logits, label_hw):
     """Can the validation kernel take this shape (two low-res logit rows in LDS: up to ~1000 low-res columns at 19 classes)?"""

@@ -159,6 +159,16 @@ SIGNATURES = {
     'pm_upsample_wce_bwd_field': (_i, [_T, _f, _i, _i, _i, _vp, _vp, _vp, _T, _vp]),
     'pm_label_class_weights_workspace': (_sz, [_i]),
     'pm_label_class_weights': (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    'pm_relax_border_bits': (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_uint32, _vp, _vp]),
+    'pm_multihot_to_bits': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'pm_relax_class_weights_workspace': (_sz, [_i]),
+    'pm_relax_class_weights': (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    'pm_upsample_relax_workspace': (_sz, [_i, _i, _i]),
+    'pm_upsample_relax_loss_floats': (_sz, [_i]),
+    'pm_upsample_relax_field_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'pm_upsample_relax_fwd': (_i, [_vp, _i, _i, _i, _i, _i64, _f, _vp, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    'pm_upsample_relax_fwd_field': (_i, [_vp, _i, _i, _i, _i, _i64, _f, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    'pm_upsample_relax_bwd_field': (_i, [_i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     'pm_upsample_eval_workspace': (_sz, [_T, _i, _i]),
     'pm_upsample_eval': (_i, [_T, _f, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'pm_mem_read_fwd': (_i, [_T, _vp, _i, _vp, _T, _vp, _vp, _vp]),

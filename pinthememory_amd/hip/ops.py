@@ -914,6 +914,63 @@ def upsample_wce(logits, labels, weights, per_image, inv_temp=1.0):
     return _UpsampleCE.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad), weights.detach(), per_image)
 
 
+class _UpsampleRelax(torch.autograd.Function):
+    """The relaxed-border loss (ImgWtLossSoftNLL, loss.py:182-263) of bilinearly up-sampled logits against border-set words, logits never materialised. As
+    _UpsampleCE: with a graph attached the forward leaves the column-reduced field and the backward is the row pass. The weights carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, bits, weights, inv_temp, want_grad):
+        lv = nhwc(logits)
+        ctx.inv_temp, ctx.hw = inv_temp, tuple(bits.shape[1:])
+        if not want_grad:
+            return K.upsample_relax_fwd(lv, bits, weights, inv_temp)[0]
+        out, field = K.upsample_relax_fwd_field(lv, bits, weights, inv_temp)
+        ctx.save_for_backward(lv, out, field)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lv, out, field = ctx.saved_tensors
+        dl = K.upsample_relax_bwd_field(lv, ctx.hw, out, field, g.reshape(1).float().contiguous(), ctx.inv_temp)
+        return nchw(dl), None, None, None, None
+
+
+def relax_sets(target, classes):
+    """-> bool [n, classes, H, W]: the real classes of every pixel's border set, from int32 words [n,H,W] or the reference's uint8 multi-hot [n, classes + 1, H, W]."""
+    if target.dim() == 4:
+        return target[:, :classes] != 0
+    return ((target.unsqueeze(1) >> torch.arange(classes, device=target.device).view(1, -1, 1, 1)) & 1).bool()
+
+
+def relaxed_soft_nll(full, target, weights):
+    """The loss of upsample_relax on materialised logits `full` [n,C,H,W], composed from torch ops without a host sync: the route of CPU tensors and of shapes the
+    fused kernel does not take. Per pixel - W_S log P_S with log P_S = logsumexp over the set - logsumexp over all classes; classes outside the set are masked, never
+    multiplied by zero, so an underflowing probability outside the set cannot make a NaN (the reference's 0 * log 0). weights: [C] or [n, C]."""
+    n, C = full.shape[:2]
+    inset = relax_sets(target, C)
+    k = inset.sum(1)
+    valid = k > 0
+    rows = weights.to(device=full.device, dtype=full.dtype)
+    rows = (rows.expand(n, -1) if rows.dim() == 1 else rows).view(n, C, 1, 1)
+    wbar = torch.where(inset, rows, rows.new_zeros(())).sum(1) / k.clamp(min=1).to(full.dtype)
+    # a pixel without a set keeps all its logits (its term is dropped below): a logsumexp over nothing would be -inf with a NaN gradient
+    log_ps = torch.logsumexp(torch.where(inset | ~valid.unsqueeze(1), full, full.new_full((), float('-inf'))), dim=1) - torch.logsumexp(full, dim=1)
+    terms = torch.where(valid, -wbar * log_ps, full.new_zeros(()))
+    per_image = terms.flatten(1).sum(1) / (valid.flatten(1).sum(1).to(full.dtype) + 1)
+    return per_image.sum() / n
+
+
+def upsample_relax(logits, bits, weights, inv_temp=1.0):
+    """ImgWtLossSoftNLL of the bilinearly up-sampled logits [n,C,h,w] against border-set words [n,H,W] (K.relax_border_bits / K.multihot_to_bits), the logits
+    never materialised. weights: [C] or [n, C] rows (K.relax_class_weights). Tiers as upsample_wce: fp32 logits."""
+    size = tuple(bits.shape[1:])
+    if not logits.is_cuda:
+        return relaxed_soft_nll(torch.nn.functional.interpolate(logits, size=size, mode='bilinear', align_corners=True) * float(inv_temp), bits, weights)
+    if not K.upsample_relax_ok(nhwc(logits), size):      # rows too wide for the fused kernel's LDS: as upsample_ce
+        return relaxed_soft_nll(resize(logits, size) * float(inv_temp), bits, weights)
+    return _UpsampleRelax.apply(logits, bits.contiguous(), weights.detach(), float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
+
+
 def mem_read(x, mem, noise=None):
     return _MemRead.apply(x, mem, noise, None, False)
 

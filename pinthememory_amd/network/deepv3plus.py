@@ -43,9 +43,12 @@ def fused_wce_weights(criterion, labels):
 
 def segmentation_loss(criterion, logits, labels, size=None):
     """criterion(Upsample(logits, size), labels) (deepv3plus.py:575-578). For the reference's own criteria -- CrossEntropyLoss(mean, ignore_index=255) with or
-    without class weights, CrossEntropyLoss2d, ImageBasedCrossEntropyLoss2d (loss.py:14-88,120-180) -- the up-sampled logits are never materialised."""
+    without class weights, CrossEntropyLoss2d, ImageBasedCrossEntropyLoss2d, ImgWtLossSoftNLL (loss.py:14-88,120-263) -- the up-sampled logits are never materialised."""
     if fused_ce_ok(criterion) or (isinstance(criterion, _loss.CrossEntropyLoss2d) and _plain_nll(criterion) and criterion.weight is None):
         return ops.upsample_ce(logits, labels)
+    if isinstance(criterion, _loss.ImgWtLossSoftNLL):      # relaxed borders (loss.py:193-263): set words from int64 labels or the multi-hot, their weights, fused loss
+        bits = criterion.border_bits(labels)
+        return ops.upsample_relax(logits, bits, criterion.class_weights(bits))
     weighted = fused_wce_weights(criterion, labels)
     if weighted is not None:
         return ops.upsample_wce(logits, labels, weighted[0], weighted[1])
@@ -142,6 +145,9 @@ class _Base(nn.Module):
             a = self.dsn[3](a)
         a = ops.conv(a, self.dsn[4])
         if aux_gts.dim() == 1:
+            if gts.dim() == 4:
+                raise ValueError('a multi-hot relaxed-border target cannot stand in for the auxiliary labels (the reference fails here too): pass int64 labels '
+                                 'as gts, the relaxed criterion builds the border sets from them')
             aux_gts = gts
         small = K.label_nearest(aux_gts, a.shape[2:])
         return segmentation_loss(self.criterion_aux, a, small)
@@ -161,6 +167,9 @@ class _Base(nn.Module):
         return outputs
 
     def _run_memory(self, dec0_up, gts, memory_writing, writing_detach):
+        if gts is not None and gts.dim() == 4:
+            raise ValueError('the memory needs class indices, not a multi-hot relaxed-border target (the reference fails here too): pass int64 labels as gts, '
+                             'the relaxed criterion builds the border sets from them')
         dec0_up, sq, sm, readloss, writeloss = self.memory(dec0_up, gts, memory_writing, writing_detach)
         return dec0_up, [sq, sm, dec0_up.detach()], readloss, writeloss
 
