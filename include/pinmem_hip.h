@@ -50,8 +50,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * 400 (round 4): pm_tensor carries dtype + flags (bf16 activation tier).
  * 410: pm_aug_image and the augmenting input edge (pm_augment_u8, pm_labels_u8_flip_to_i64); the size of that struct is an ARGUMENT of the calls that read it,
  * because the array lives in device memory where the library cannot look at a first member.
- * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS. */
-#define PM_ABI_VERSION 420
+ * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS.
+ * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8). */
+#define PM_ABI_VERSION 430
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -405,6 +406,44 @@ int pm_resample_tables(const pm_geo_image* geo_host, int32_t struct_size, int Hs
 int pm_resample_crop_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo_dev, int32_t struct_size, const int32_t* bic_rows,
                         const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, uint8_t* out_img, uint8_t* out_lab,
                         void* stream);
+
+/* ---- label-decoding input edge: colour- and id-coded masks -> train ids on the device (csrc/resample.hip) ----------------------------------------------------------
+ * The per-image host loops of the reference's datasets over their label dicts, as one table lookup per pixel; uint8 in, uint8 out, exact.
+ *   PM_LABEL_COLORS {(r, g, b): v} (datasets/gtav.py:440-445): the output starts as `fill`; entries with v == 255 or v == -1 are dropped; a pixel equal to an entry's
+ *     colour on all three channels gets (uint8) v; every other pixel keeps `fill`. A colour listed twice keeps its last kept value (a dict cannot hold one twice).
+ *   PM_LABEL_IDS {k: v} (datasets/synthia.py:254-257, cityscapes.py): the output starts as the input id (channel 0); pixels whose ORIGINAL id equals k get (uint8) v
+ *     (-1 becomes 255); assignments do not chain; keys outside 0..255 never match; a key listed twice keeps its last value.
+ * The table is plain data: built on the host (no device involved, as pm_resample_tables), copied to device memory by the caller, read there. Colours sit in an
+ * open-addressed hash of PM_LABEL_SLOTS slots, linear probing from slot ((r | g << 8 | b << 16) * 0x9E3779B1 mod 2^32) >> 24, an empty slot's key 0xFFFFFFFF; at most
+ * PM_LABEL_MAX_COLORS kept entries, so a miss meets an empty slot after a short walk. */
+#define PM_LABEL_SLOTS 256
+#define PM_LABEL_MAX_COLORS 128
+#define PM_LABEL_IDS 0
+#define PM_LABEL_COLORS 1
+typedef struct pm_label_table {       /* 1 544 bytes; an array of these lives in DEVICE memory, its struct size is an argument of the calls that read it */
+  int32_t mode;                       /* PM_LABEL_IDS / PM_LABEL_COLORS */
+  int32_t fill;                       /* colours: the value of a pixel whose colour the table does not hold (0..255) */
+  uint8_t lut[256];                   /* ids: lut[id]; the identity for a colour table */
+  uint32_t keys[PM_LABEL_SLOTS];      /* colours: r | g << 8 | b << 16, 0xFFFFFFFF = empty; all empty for an id table */
+  uint8_t vals[PM_LABEL_SLOTS];       /* colours: the value of the slot's key */
+} pm_label_table;
+/* host only. keys / vals: `count` int32 pairs; rgb: `count` int32 triples. PM_EINVAL: a null pointer (count > 0 with null arrays, or a null table), another struct_size,
+ * count < 0, fill outside 0..255. A colour with a channel outside 0..255 never matches, as a key outside 0..255. PM_EUNSUPPORTED: more than PM_LABEL_MAX_COLORS distinct kept colours (the table is then unspecified). */
+int pm_label_table_ids(const int32_t* keys, const int32_t* vals, int count, pm_label_table* table, int32_t struct_size);
+int pm_label_table_colors(const int32_t* rgb, const int32_t* vals, int count, int fill, pm_label_table* table, int32_t struct_size);
+/* lab uint8 [n][H][W][lab_c], lab_c 1 or 3; tables_dev: ntables structs of struct_size = sizeof(pm_label_table) bytes in device memory; image_table_dev: n int32 in device
+ * memory, -1 (any negative) = pass-through (channel 0 unchanged), otherwise an index the kernel clamps into [0, ntables); out uint8 [n][H][W], which may not overlap lab.
+ * A colour table on a one-channel slab writes its `fill`. ntables == 0: tables_dev may be null and every image passes through. A table that did not come from the
+ * builders gives unspecified bytes, but the probe walk is bounded by PM_LABEL_SLOTS and every index is clamped: no access outside the arrays, no unbounded loop. */
+int pm_labels_decode_u8(const uint8_t* lab, int n, int H, int W, int lab_c, const pm_label_table* tables_dev, int ntables, int32_t struct_size,
+                        const int32_t* image_table_dev, uint8_t* out, void* stream);
+/* pm_resample_crop_u8 with the mask decoded in its gather: lab is uint8 [n][Hs][Ws][lab_c] read through the same nearest tables, each gathered pixel decoded as
+ * pm_labels_decode_u8 decodes it, the pad written as ignore_index. A per-pixel map commutes with a gather, so out_lab carries the bytes of pm_labels_decode_u8 over the
+ * whole slab followed by pm_resample_crop_u8, for the window's pixels alone; out_img carries pm_resample_crop_u8's bytes. Everything else as pm_resample_crop_u8. */
+int pm_resample_crop_decode_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo_dev, int32_t struct_size, const int32_t* bic_rows,
+                               const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, int lab_c,
+                               const pm_label_table* tables_dev, int ntables, int32_t struct_size_table, const int32_t* image_table_dev, uint8_t* out_img,
+                               uint8_t* out_lab, void* stream);
 
 /* ---- layout edges ------------------------------------------------------------------------------------------------ */
 int pm_nchw_to_nhwc(const float* x_nchw, int c_src, const pm_tensor* y, void* stream);   /* zero-fills y.c > c_src */

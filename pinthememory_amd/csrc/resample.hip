@@ -34,11 +34,48 @@ __device__ __forceinline__ void load_records(int* dst, const int32_t* __restrict
   __syncthreads();
 }
 
+// The decode step of the label-decoding edge (include/pinmem_hip.h, pm_label_table): one label pixel through its image's table, which the block holds in LDS; a null
+// table is the pass-through. The probe walk ends at the key, at an empty slot or after PM_LABEL_SLOTS steps, and every index is a byte or masked to the slot count.
+constexpr unsigned LABEL_EMPTY = 0xFFFFFFFFu, LABEL_HASH = 0x9E3779B1u;
+__host__ __device__ __forceinline__ unsigned label_slot(unsigned key) { return (key * LABEL_HASH) >> 24; }
+static_assert(PM_LABEL_SLOTS == 256, "label_slot keeps the top 8 bits of the product");
+constexpr int TABLE_WORDS = (int)(sizeof(pm_label_table) / 4);
+static_assert(sizeof(pm_label_table) % 4 == 0, "the table is copied to LDS as dwords");
+
+__device__ __forceinline__ uint8_t decode_label(const pm_label_table* T, const uint8_t* p, int lab_c) {
+  if (!T) return p[0];
+  if (T->mode != PM_LABEL_COLORS) return T->lut[p[0]];
+  if (lab_c != 3) return (uint8_t)T->fill;
+  const unsigned key = (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16;
+  unsigned s = label_slot(key);
+  for (int i = 0; i < PM_LABEL_SLOTS; ++i, s = (s + 1) & (PM_LABEL_SLOTS - 1)) {
+    const unsigned k = T->keys[s];
+    if (k == key) return T->vals[s];
+    if (k == LABEL_EMPTY) break;
+  }
+  return (uint8_t)T->fill;
+}
+
+// The table of image n into `dst` (LDS; every thread of the block calls this): null for the pass-through (a negative entry, or no tables at all); the index is clamped.
+template <int THREADS>
+__device__ __forceinline__ const pm_label_table* load_label_table(unsigned* dst, const pm_label_table* __restrict__ tables, int ntables,
+                                                                  const int32_t* __restrict__ image_table, int n, int tid) {
+  const int t = image_table[n];
+  if (t < 0 || ntables <= 0) return nullptr;      // uniform over the block
+  const unsigned* src = reinterpret_cast<const unsigned*>(tables + min(t, ntables - 1));
+  for (int i = tid; i < TABLE_WORDS; i += THREADS) dst[i] = src[i];
+  __syncthreads();
+  return reinterpret_cast<const pm_label_table*>(dst);
+}
+
+// DECODE: the mask is [n][Hs][Ws][lab_c] and every gathered pixel goes through its image's pm_label_table; without it the plain gather of pm_resample_crop_u8.
+template <bool DECODE>
 __global__ __launch_bounds__(NT) void resample_crop_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab, int Hs, int Ws,
                                                             const pm_geo_image* __restrict__ geo, const int32_t* __restrict__ bic_rows,
                                                             const int32_t* __restrict__ bic_cols, const int32_t* __restrict__ near_rows,
-                                                            const int32_t* __restrict__ near_cols, int th, int tw, int ignore, uint8_t* __restrict__ out_img,
-                                                            uint8_t* __restrict__ out_lab) {
+                                                            const int32_t* __restrict__ near_cols, int th, int tw, int ignore, int lab_c,
+                                                            const pm_label_table* __restrict__ tables, int ntables, const int32_t* __restrict__ image_table,
+                                                            uint8_t* __restrict__ out_img, uint8_t* __restrict__ out_lab) {
   extern __shared__ __align__(16) unsigned char smem[];
   int* rtab = reinterpret_cast<int*>(smem);                  // [TH][REC]
   int* ctab = rtab + TH * REC;                               // [TW][REC]
@@ -50,16 +87,25 @@ __global__ __launch_bounds__(NT) void resample_crop_kernel(const uint8_t* __rest
   const int nr = min(TH, th - y0), nc = min(TW, tw - x0);
   const long slab = (long)Hs * Ws;
 
-  // labels: a gather through the two nearest tables
+  // labels: a gather through the two nearest tables, with DECODE each pixel through the image's label table (parked in `stage`, which the image passes claim only
+  // behind the barriers of load_records)
   {
-    const uint8_t* src = lab + (long)n * slab;
+    const int lc = DECODE ? lab_c : 1;
+    const pm_label_table* T = nullptr;
+    if constexpr (DECODE) T = load_label_table<NT>(reinterpret_cast<unsigned*>(stage), tables, ntables, image_table, n, tid);
+    const uint8_t* src = lab + (long)n * slab * lc;
     const int32_t *ry = near_rows + (long)n * th + y0, *rx = near_cols + (long)n * tw + x0;
     uint8_t* dst = out_lab + ((long)n * th + y0) * tw + x0;
     for (int i = tid; i < nr * TW; i += NT) {
       const int ly = i / TW, lx = i - ly * TW;
       if (lx >= nc) continue;
       const int sy = ry[ly], sx = rx[lx];
-      dst[(long)ly * tw + lx] = (sy < 0 || sx < 0) ? (uint8_t)ignore : src[(long)min(sy, h_in - 1) * Ws + min(sx, w_in - 1)];
+      if (sy < 0 || sx < 0) {
+        dst[(long)ly * tw + lx] = (uint8_t)ignore;
+        continue;
+      }
+      const uint8_t* p = src + ((long)min(sy, h_in - 1) * Ws + min(sx, w_in - 1)) * lc;
+      dst[(long)ly * tw + lx] = DECODE ? decode_label(T, p, lc) : p[0];
     }
   }
 
@@ -224,22 +270,149 @@ extern "C" int pm_resample_tables(const pm_geo_image* g, int32_t struct_size, in
   return PM_OK;
 }
 
+namespace {
+bool overlap(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) { return a < b + nb && b < a + na; }
+
+// the checks and the launch both resampling entry points share; DECODE: lab holds lab_c channels per pixel and goes through the label tables
+template <bool DECODE>
+int resample_crop(const char* who, const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo, int32_t struct_size, const int32_t* bic_rows,
+                  const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, int lab_c, const pm_label_table* tables,
+                  int ntables, const int32_t* image_table, uint8_t* out_img, uint8_t* out_lab, void* stream) {
+  PM_REQUIRE(struct_size == (int32_t)sizeof(pm_geo_image), PM_EINVAL, "%s: pm_geo_image struct_size %d != %zu (caller built against another pinmem_hip.h; ABI %d)", who,
+             struct_size, sizeof(pm_geo_image), PM_ABI_VERSION);
+  PM_REQUIRE(img && lab && geo && bic_rows && bic_cols && near_rows && near_cols && out_img && out_lab, PM_EINVAL, "%s: null pointer", who);
+  PM_REQUIRE(n >= 0 && Hs > 0 && Ws > 0 && th > 0 && tw > 0 && ignore_index >= 0 && ignore_index <= 255, PM_EINVAL,
+             "%s: bad args (n %d, slab %d x %d, crop %d x %d, ignore_index %d)", who, n, Hs, Ws, th, tw, ignore_index);
+  PM_REQUIRE(n <= 65535 && pm_cdiv(th, TH) <= 65535, PM_EUNSUPPORTED, "%s: n %d / crop height %d beyond the launch grid", who, n, th);
+  const size_t in_px = (size_t)n * Hs * Ws, out_px = (size_t)n * th * tw, lab_b = in_px * lab_c;
+  PM_REQUIRE(n == 0 || !(overlap(out_img, out_px * 3, img, in_px * 3) || overlap(out_img, out_px * 3, lab, lab_b) || overlap(out_lab, out_px, img, in_px * 3) ||
+                         overlap(out_lab, out_px, lab, lab_b) || overlap(out_img, out_px * 3, out_lab, out_px)),
+             PM_EINVAL, "%s: an output overlaps an input (or the other output): a tile would read resampled pixels", who);
+  if (n == 0) return PM_OK;
+  hipLaunchKernelGGL(resample_crop_kernel<DECODE>, dim3(pm_cdiv(tw, TW), pm_cdiv(th, TH), n), dim3(NT), LDS_BYTES, (hipStream_t)stream, img, lab, Hs, Ws, geo, bic_rows,
+                     bic_cols, near_rows, near_cols, th, tw, ignore_index, lab_c, tables, ntables, image_table, out_img, out_lab);
+  return pm_check_launch(who);
+}
+
+// what both decoding entry points ask of their table arguments
+int check_label_tables(const char* who, int lab_c, const pm_label_table* tables, int ntables, int32_t struct_size, const int32_t* image_table) {
+  PM_REQUIRE(struct_size == (int32_t)sizeof(pm_label_table), PM_EINVAL, "%s: pm_label_table struct_size %d != %zu (caller built against another pinmem_hip.h; ABI %d)", who,
+             struct_size, sizeof(pm_label_table), PM_ABI_VERSION);
+  PM_REQUIRE(lab_c == 1 || lab_c == 3, PM_EINVAL, "%s: label slabs of 1 or 3 channels (got %d)", who, lab_c);
+  PM_REQUIRE(ntables >= 0 && (ntables == 0 || tables) && image_table, PM_EINVAL, "%s: %d tables at %p, image_table %p", who, ntables, (const void*)tables,
+             (const void*)image_table);
+  PM_REQUIRE((reinterpret_cast<uintptr_t>(tables) & 3) == 0 && (reinterpret_cast<uintptr_t>(image_table) & 3) == 0, PM_EINVAL, "%s: tables and image_table must be 4-byte aligned",
+             who);
+  return PM_OK;
+}
+
+// Whole-slab decode: blocks (x, image); a block parks its image's table in LDS and strides over the image's pixels, four to a thread (VEC: dword loads and one dword
+// store; else pixel by pixel).
+constexpr int DT = 256;
+template <bool VEC>
+__global__ __launch_bounds__(DT) void labels_decode_kernel(const uint8_t* __restrict__ lab, long hw, int lab_c, const pm_label_table* __restrict__ tables, int ntables,
+                                                           const int32_t* __restrict__ image_table, uint8_t* __restrict__ out) {
+  __shared__ unsigned tab[TABLE_WORDS];
+  const int n = blockIdx.y, tid = threadIdx.x;
+  const pm_label_table* T = load_label_table<DT>(tab, tables, ntables, image_table, n, tid);
+  const uint8_t* src = lab + (long)n * hw * lab_c;
+  uint8_t* dst = out + (long)n * hw;
+  const long step = (long)gridDim.x * DT, first = (long)blockIdx.x * DT + tid;
+  if constexpr (VEC) {      // hw % 4 == 0 and both bases on a dword: every group of four pixels is whole dwords
+    for (long q = first; q < (hw >> 2); q += step) {
+      unsigned w[3] = {0u, 0u, 0u};
+      for (int j = 0; j < lab_c; ++j) w[j] = reinterpret_cast<const unsigned*>(src)[q * lab_c + j];
+      uint8_t px[12];
+      __builtin_memcpy(px, w, 12);
+      unsigned o = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o |= (unsigned)decode_label(T, px + e * lab_c, lab_c) << (8 * e);
+      reinterpret_cast<unsigned*>(dst)[q] = o;
+    }
+  } else {
+    for (long i = first; i < hw; i += step) dst[i] = decode_label(T, src + i * lab_c, lab_c);
+  }
+}
+
+// one kept entry into the hash; false: the table is full of other keys
+bool label_insert(pm_label_table* t, unsigned key, uint8_t val) {
+  unsigned s = label_slot(key);
+  for (int i = 0; i < PM_LABEL_SLOTS; ++i, s = (s + 1) & (PM_LABEL_SLOTS - 1)) {
+    if (t->keys[s] == LABEL_EMPTY || t->keys[s] == key) {
+      t->keys[s] = key, t->vals[s] = val;
+      return true;
+    }
+  }
+  return false;
+}
+
+void label_table_clear(pm_label_table* t, int mode, int fill) {
+  t->mode = mode, t->fill = fill;
+  for (int i = 0; i < 256; ++i) t->lut[i] = (uint8_t)i;
+  for (int i = 0; i < PM_LABEL_SLOTS; ++i) t->keys[i] = LABEL_EMPTY, t->vals[i] = (uint8_t)fill;
+}
+}  // namespace
+
 extern "C" int pm_resample_crop_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo, int32_t struct_size, const int32_t* bic_rows,
                                    const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, uint8_t* out_img,
                                    uint8_t* out_lab, void* stream) {
-  PM_REQUIRE(struct_size == (int32_t)sizeof(pm_geo_image), PM_EINVAL, "resample_crop_u8: pm_geo_image struct_size %d != %zu (caller built against another pinmem_hip.h; ABI %d)",
-             struct_size, sizeof(pm_geo_image), PM_ABI_VERSION);
-  PM_REQUIRE(img && lab && geo && bic_rows && bic_cols && near_rows && near_cols && out_img && out_lab, PM_EINVAL, "resample_crop_u8: null pointer");
-  PM_REQUIRE(n >= 0 && Hs > 0 && Ws > 0 && th > 0 && tw > 0 && ignore_index >= 0 && ignore_index <= 255, PM_EINVAL,
-             "resample_crop_u8: bad args (n %d, slab %d x %d, crop %d x %d, ignore_index %d)", n, Hs, Ws, th, tw, ignore_index);
-  PM_REQUIRE(n <= 65535 && pm_cdiv(th, TH) <= 65535, PM_EUNSUPPORTED, "resample_crop_u8: n %d / crop height %d beyond the launch grid", n, th);
-  const size_t in_px = (size_t)n * Hs * Ws, out_px = (size_t)n * th * tw;
-  auto overlap = [](const uint8_t* a, size_t na, const uint8_t* b, size_t nb) { return a < b + nb && b < a + na; };
-  PM_REQUIRE(n == 0 || !(overlap(out_img, out_px * 3, img, in_px * 3) || overlap(out_img, out_px * 3, lab, in_px) || overlap(out_lab, out_px, img, in_px * 3) ||
-                         overlap(out_lab, out_px, lab, in_px) || overlap(out_img, out_px * 3, out_lab, out_px)),
-             PM_EINVAL, "resample_crop_u8: an output overlaps an input (or the other output): a tile would read resampled pixels");
+  return resample_crop<false>("resample_crop_u8", img, lab, n, Hs, Ws, geo, struct_size, bic_rows, bic_cols, near_rows, near_cols, th, tw, ignore_index, 1, nullptr, 0,
+                              nullptr, out_img, out_lab, stream);
+}
+
+extern "C" int pm_resample_crop_decode_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo, int32_t struct_size,
+                                          const int32_t* bic_rows, const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw,
+                                          int ignore_index, int lab_c, const pm_label_table* tables, int ntables, int32_t struct_size_table, const int32_t* image_table,
+                                          uint8_t* out_img, uint8_t* out_lab, void* stream) {
+  if (int rc = check_label_tables("resample_crop_decode_u8", lab_c, tables, ntables, struct_size_table, image_table)) return rc;
+  return resample_crop<true>("resample_crop_decode_u8", img, lab, n, Hs, Ws, geo, struct_size, bic_rows, bic_cols, near_rows, near_cols, th, tw, ignore_index, lab_c, tables,
+                             ntables, image_table, out_img, out_lab, stream);
+}
+
+extern "C" int pm_labels_decode_u8(const uint8_t* lab, int n, int H, int W, int lab_c, const pm_label_table* tables, int ntables, int32_t struct_size,
+                                   const int32_t* image_table, uint8_t* out, void* stream) {
+  if (int rc = check_label_tables("labels_decode_u8", lab_c, tables, ntables, struct_size, image_table)) return rc;
+  PM_REQUIRE(lab && out, PM_EINVAL, "labels_decode_u8: null pointer");
+  PM_REQUIRE(n >= 0 && H > 0 && W > 0, PM_EINVAL, "labels_decode_u8: bad args (n %d, %d x %d)", n, H, W);
+  PM_REQUIRE(n <= 65535, PM_EUNSUPPORTED, "labels_decode_u8: n %d beyond the launch grid", n);
+  const long hw = (long)H * W;
+  PM_REQUIRE(n == 0 || !overlap(out, (size_t)n * hw, lab, (size_t)n * hw * lab_c), PM_EINVAL, "labels_decode_u8: out overlaps lab");
   if (n == 0) return PM_OK;
-  hipLaunchKernelGGL(resample_crop_kernel, dim3(pm_cdiv(tw, TW), pm_cdiv(th, TH), n), dim3(NT), LDS_BYTES, (hipStream_t)stream, img, lab, Hs, Ws, geo, bic_rows, bic_cols,
-                     near_rows, near_cols, th, tw, ignore_index, out_img, out_lab);
-  return pm_check_launch("resample_crop_u8");
+  const bool vec = (hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(lab) | reinterpret_cast<uintptr_t>(out)) & 3) == 0;
+  // about 2048 blocks in all (eight per CU), each image's share striding over its pixels: a block's copy of the table is paid once per several thousand pixels
+  const dim3 grid((unsigned)std::min<long>(pm_cdiv(vec ? hw >> 2 : hw, DT), pm_cdiv(2048, n)), n);
+  if (vec) hipLaunchKernelGGL(labels_decode_kernel<true>, grid, dim3(DT), 0, (hipStream_t)stream, lab, hw, lab_c, tables, ntables, image_table, out);
+  else hipLaunchKernelGGL(labels_decode_kernel<false>, grid, dim3(DT), 0, (hipStream_t)stream, lab, hw, lab_c, tables, ntables, image_table, out);
+  return pm_check_launch("labels_decode_u8");
+}
+
+extern "C" int pm_label_table_ids(const int32_t* keys, const int32_t* vals, int count, pm_label_table* table, int32_t struct_size) {
+  PM_REQUIRE(struct_size == (int32_t)sizeof(pm_label_table), PM_EINVAL, "label_table_ids: pm_label_table struct_size %d != %zu (caller built against another pinmem_hip.h; ABI %d)",
+             struct_size, sizeof(pm_label_table), PM_ABI_VERSION);
+  PM_REQUIRE(table && count >= 0 && (count == 0 || (keys && vals)), PM_EINVAL, "label_table_ids: null pointer or negative count (%d)", count);
+  label_table_clear(table, PM_LABEL_IDS, 255);
+  for (int i = 0; i < count; ++i)
+    if (keys[i] >= 0 && keys[i] <= 255) table->lut[keys[i]] = (uint8_t)vals[i];      // -1 wraps to 255, as the assignment into a uint8 array does
+  return PM_OK;
+}
+
+extern "C" int pm_label_table_colors(const int32_t* rgb, const int32_t* vals, int count, int fill, pm_label_table* table, int32_t struct_size) {
+  PM_REQUIRE(struct_size == (int32_t)sizeof(pm_label_table), PM_EINVAL,
+             "label_table_colors: pm_label_table struct_size %d != %zu (caller built against another pinmem_hip.h; ABI %d)", struct_size, sizeof(pm_label_table), PM_ABI_VERSION);
+  PM_REQUIRE(table && count >= 0 && (count == 0 || (rgb && vals)), PM_EINVAL, "label_table_colors: null pointer or negative count (%d)", count);
+  PM_REQUIRE(fill >= 0 && fill <= 255, PM_EINVAL, "label_table_colors: fill %d outside 0..255", fill);
+  label_table_clear(table, PM_LABEL_COLORS, fill);
+  int kept = 0;
+  for (int i = 0; i < count; ++i) {
+    const int32_t* c = rgb + 3l * i;
+    if (vals[i] == 255 || vals[i] == -1) continue;                                                            // gtav.py:444
+    if (c[0] < 0 || c[0] > 255 || c[1] < 0 || c[1] > 255 || c[2] < 0 || c[2] > 255) continue;                 // no uint8 pixel equals it
+    const unsigned key = (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16;
+    bool known = false;
+    for (int s = 0; s < PM_LABEL_SLOTS; ++s) known |= table->keys[s] == key;
+    PM_REQUIRE(known || kept < PM_LABEL_MAX_COLORS, PM_EUNSUPPORTED, "label_table_colors: more than PM_LABEL_MAX_COLORS = %d colours", PM_LABEL_MAX_COLORS);
+    kept += known ? 0 : 1;
+    label_insert(table, key, (uint8_t)vals[i]);
+  }
+  return PM_OK;
 }

@@ -455,7 +455,7 @@ def miou(hist):
 
 
 # ---- the validation loop every training script runs after each epoch (train.py:847-939) ---------------------------------------
-def validate(net, batches, criterion=None, classes=19, dump=10):
+def validate(net, batches, criterion=None, classes=19, dump=10, decode=None, tables=None):
     """train.py:847-939 without the logging, the checkpointing and the distributed reduce (the caller sums `hist` across ranks where the reference
     all-reduces iou_acc). Per batch: one eval forward that returns the head's LOW-RES logits, then one kernel that up-samples them, evaluates the
     criterion, takes output.max(1)[1] and adds fast_hist into the running histogram (K.upsample_eval) -- the [n,19,H,W] logits are never written and
@@ -463,6 +463,8 @@ def validate(net, batches, criterion=None, classes=19, dump=10):
     other than the plain CrossEntropyLoss(ignore_index=255), or a shape the kernel does not take, goes through resize + criterion + argmax + fast_hist
     on the device (correct, not tuned). The loss means carry the reference's AverageMeter weighting: each batch's mean by n*H*W, ignored pixels
     included (:880,903). The class maps of the first `dump` batches are kept (the reference's image dumps). Leaves the net in eval mode.
+    decode (an input_edge.LabelDecode; None = gt holds train ids) with tables (one table index of `decode` for every image, or one entry per image of a batch after
+    the leading axes merged; -1 / None = pass-through): gt is the dataset's raw uint8 mask, [.., H, W] ids or [.., H, W, 3] colours, decoded on the device first.
     -> dict(val_loss, read_loss (None without the memory), hist int64 [C,C] on the device, mean_iu, iu, predictions: list of uint8 [n,H,W])."""
     from .network.deepv3plus import fused_ce_ok
     m = net.module if hasattr(net, 'module') else net
@@ -479,6 +481,11 @@ def validate(net, batches, criterion=None, classes=19, dump=10):
         with torch.no_grad():
             for idx, data in enumerate(batches):
                 inputs, gt = data[0], data[1]
+                if decode is not None:                                     # raw masks: decoded on the device before anything else
+                    h, w = inputs.shape[-2:]
+                    raw = gt.to(device).reshape(-1, *((h, w, 3) if gt.dim() == inputs.dim() else (h, w))).contiguous()
+                    entries = [tables] * raw.shape[0] if tables is None or isinstance(tables, int) else tables
+                    gt = K.labels_u8_to_i64(decode.decode(raw, entries))
                 if inputs.dim() == 5:
                     inputs = inputs.reshape(-1, *inputs.shape[2:])
                     gt = gt.reshape(-1, *inputs.shape[2:])
@@ -752,20 +759,35 @@ def prepare_batch(inputs, gts, aux_gts=None):
     return x, gt, aux
 
 
-def prepare_batch_u8(images_u8, labels_u8, augment=None, hard=None, geometry=None, sizes=None, centroids=None):
+def prepare_batch_u8(images_u8, labels_u8, augment=None, hard=None, geometry=None, sizes=None, centroids=None, decode=None, tables=None):
     """GPU-side ToTensor + Normalize(ImageNet) + MaskToTensor for uint8 [.., H, W, 3] images and uint8 [.., H, W] label maps:
     4x / 8x less host->device traffic than the fp32 / int64 tensors the reference's loader ships. Returns the image as a
     logical-NCHW view of NHWC4 memory (what the stem consumes without another conversion) and int64 labels.
     augment (an input_edge.PhotometricAugment; None = the plain conversion): colour jitter, blur and flip on the device first (image and labels flipped alike);
     hard: one bool per image after the leading axes merged -- those get the hard augmentation of the meta-test domains.
     geometry (an input_edge.GeometricAugment; None = none): RandomSizeAndCrop on the device before all of that -- resize, pad and crop of image and labels; sizes
-    ((H, W) per image, the image in the top-left corner of its slab; None: every image fills it) and centroids go to its sampler."""
+    ((H, W) per image, the image in the top-left corner of its slab; None: every image fills it) and centroids go to its sampler.
+    decode (an input_edge.LabelDecode; None = the masks hold train ids) with tables (one entry per image after the leading axes merged: a table index of `decode`,
+    -1 or None for the pass-through): labels_u8 is raw, [.., H, W] ids or [.., H, W, 3] colours, and is decoded on the device first -- inside the geometry's mask
+    gather where there is one, else in a pass of its own."""
     h, w = images_u8.shape[-3:-1]
     img_d = images_u8.reshape(-1, h, w, 3).cuda(non_blocking=True).contiguous()
-    lab_d = labels_u8.reshape(-1, h, w).cuda(non_blocking=True).contiguous()
+    if decode is None:
+        assert tables is None, 'tables without a LabelDecode'
+        lab_d = labels_u8.reshape(-1, h, w).cuda(non_blocking=True).contiguous()
+    else:
+        lab_tail = (h, w, 3) if labels_u8.dim() == images_u8.dim() else (h, w)
+        table = decode.image_table([None] * img_d.shape[0] if tables is None else tables, img_d.shape[0], 3 if len(lab_tail) == 3 else 1)
+        lab_d = labels_u8.reshape(-1, *lab_tail).cuda(non_blocking=True).contiguous()
+        if geometry is None:
+            lab_d = K.labels_decode_u8(lab_d, decode.device_tables(lab_d.device), table)
     if geometry is not None:
         from .input_edge import sample_geometry
-        img_d, lab_d = K.resample_crop_u8(img_d, lab_d, sample_geometry(geometry, img_d.shape, dict(sizes=sizes, centroids=centroids)))
+        geo = sample_geometry(geometry, img_d.shape, dict(sizes=sizes, centroids=centroids))
+        if decode is None:
+            img_d, lab_d = K.resample_crop_u8(img_d, lab_d, geo)
+        else:
+            img_d, lab_d = K.resample_crop_decode_u8(img_d, lab_d, geo, decode.device_tables(lab_d.device), table)
     if augment is None:
         return ops.nchw(K.image_u8_to_nhwc4(img_d)), K.labels_u8_to_i64(lab_d)
     params = K.upload_aug_params(augment.sample(img_d.shape[0], hard), img_d.device)

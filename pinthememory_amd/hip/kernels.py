@@ -830,10 +830,10 @@ class GeoDevice:
         self.buf, self.n, self.crop, self.ignore_index, self.slab, self.offsets = buf, n, crop, ignore_index, slab, offsets
 
 
-def _geo_offsets(n, crop):
-    """Byte offsets of (structs, bicubic rows, bicubic columns, nearest rows, nearest columns) in the staged block, and its size."""
+def _geo_offsets(n, crop, with_image_table=False):
+    """Byte offsets of (structs, bicubic rows, bicubic columns, nearest rows, nearest columns[, the label decode's image_table]) in the staged block, and its size."""
     th, tw = crop
-    sizes = (n * ctypes.sizeof(L.PmGeoImage), n * th * L.RESAMPLE_REC * 4, n * tw * L.RESAMPLE_REC * 4, n * th * 4, n * tw * 4)
+    sizes = (n * ctypes.sizeof(L.PmGeoImage), n * th * L.RESAMPLE_REC * 4, n * tw * L.RESAMPLE_REC * 4, n * th * 4, n * tw * 4) + ((n * 4,) if with_image_table else ())
     offs = [0]
     for s in sizes:
         offs.append(offs[-1] + s)
@@ -851,17 +851,23 @@ def resample_tables(g, slab, crop):
     return t
 
 
-def upload_geo(geo, device, slab):
+def upload_geo(geo, device, slab, image_table=None):
     """GeoParams -> GeoDevice: the library writes every image's tables straight into one pinned block behind the structs (validating each geometry against the
-    [Hs, Ws] slab on the way), and the block is copied without blocking on the current stream, as upload_aug_params does. A GeoDevice is passed on."""
+    [Hs, Ws] slab on the way), and the block is copied without blocking on the current stream, as upload_aug_params does. A GeoDevice is passed on.
+    image_table (the label decode's table index per image, -1 = pass-through): n int32 staged behind the tables in the same block, at offsets[5]."""
     if isinstance(geo, GeoDevice):
         assert geo.slab == (int(slab[0]), int(slab[1])), 'geometry uploaded for slab %s, batch has %s' % (geo.slab, tuple(slab))
+        assert image_table is None or len(geo.offsets) == 6, 'geometry uploaded without an image_table'
         return geo
     n, (th, tw) = len(geo), geo.crop
-    offs, total = _geo_offsets(n, geo.crop)
+    offs, total = _geo_offsets(n, geo.crop, image_table is not None)
     host = torch.empty(max(total, 4), dtype=torch.uint8, pin_memory=True)
     base, size, lib = host.data_ptr(), ctypes.sizeof(L.PmGeoImage), _lib()
     ctypes.memmove(base, ctypes.addressof(geo.images), n * size)
+    if image_table is not None:
+        assert len(image_table) == n, 'image_table for %d images, geometry for %d' % (len(image_table), n)
+        staged = _i32(image_table)
+        ctypes.memmove(base + offs[5], ctypes.addressof(staged), n * 4)
     rec = L.RESAMPLE_REC * 4
     for i in range(n):
         check(lib.pm_resample_tables(ctypes.addressof(geo.images[i]), size, int(slab[0]), int(slab[1]), th, tw, base + offs[1] + i * th * rec, base + offs[2] + i * tw * rec,
@@ -884,6 +890,97 @@ def resample_crop_u8(img_u8, lab_u8, geo):
     p, o = gd.buf.data_ptr(), gd.offsets
     check(_lib().pm_resample_crop_u8(img_u8.data_ptr(), lab_u8.data_ptr(), n, hs, ws, p + o[0], ctypes.sizeof(L.PmGeoImage), p + o[1], p + o[2], p + o[3], p + o[4], th, tw,
                                      gd.ignore_index, out.data_ptr(), out_lab.data_ptr(), stream()), 'pm_resample_crop_u8')
+    return out, out_lab
+
+
+# ---- label-decoding input edge (csrc/resample.hip) -------------------------------------------------------------------------
+def _i32(values):
+    return (ctypes.c_int32 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def label_table_ids(mapping):
+    """{id: value} as a dataset holds it (synthia.trainid_to_trainid, cityscapes.id_to_trainid) -> a host pm_label_table (pm_label_table_ids; no device involved)."""
+    items = list(dict(mapping).items())
+    t, keys, vals = L.PmLabelTable(), _i32([k for k, _ in items]), _i32([v for _, v in items])
+    check(_lib().pm_label_table_ids(ctypes.addressof(keys), ctypes.addressof(vals), len(items), ctypes.addressof(t), ctypes.sizeof(L.PmLabelTable)), 'pm_label_table_ids')
+    return t
+
+
+def label_table_colors(mapping, fill=255):
+    """{(r, g, b): value} (gtav.color_to_trainid) -> a host pm_label_table (pm_label_table_colors): entries of value 255 / -1 dropped, every other colour `fill`."""
+    items = list(dict(mapping).items())
+    for k, _ in items:
+        if len(k) != 3:
+            raise ValueError('colour key %r is not an (r, g, b) triple' % (k,))
+    t, rgb, vals = L.PmLabelTable(), _i32([c for k, _ in items for c in k]), _i32([v for _, v in items])
+    check(_lib().pm_label_table_colors(ctypes.addressof(rgb), ctypes.addressof(vals), len(items), int(fill), ctypes.addressof(t), ctypes.sizeof(L.PmLabelTable)),
+          'pm_label_table_colors')
+    return t
+
+
+def upload_label_tables(tables, device):
+    """A list of host pm_label_table -> the uint8 device tensor the kernels read, staged in pinned memory and copied without blocking on the current stream."""
+    size = ctypes.sizeof(L.PmLabelTable)
+    host = torch.zeros(max(len(tables), 1) * size, dtype=torch.uint8).pin_memory()
+    for i, t in enumerate(tables):
+        assert isinstance(t, L.PmLabelTable)
+        ctypes.memmove(host.data_ptr() + i * size, ctypes.addressof(t), size)
+    return host.to(device, non_blocking=True)
+
+
+def upload_image_table(image_table, device):
+    """Table index per image (-1 = pass-through) -> int32 device tensor, staged in pinned memory and copied without blocking on the current stream. A tensor is passed on."""
+    if isinstance(image_table, torch.Tensor):
+        assert image_table.is_cuda and image_table.dtype == torch.int32 and image_table.is_contiguous(), 'not an upload_image_table tensor'
+        return image_table
+    host = torch.tensor([int(v) for v in image_table], dtype=torch.int32).pin_memory()
+    return host.to(device, non_blocking=True)
+
+
+def _label_channels(lab_u8, lead):
+    """1 for a [*lead] mask, 3 for [*lead, 3]"""
+    if tuple(lab_u8.shape) == tuple(lead):
+        return 1
+    assert tuple(lab_u8.shape) == tuple(lead) + (3,), 'label slab %s, expected %s or %s' % (tuple(lab_u8.shape), tuple(lead), tuple(lead) + (3,))
+    return 3
+
+
+def labels_decode_u8(lab_u8, tables_dev, image_table):
+    """Colour- or id-coded masks, uint8 [N,H,W,3] or [N,H,W] -> uint8 train ids [N,H,W] (pm_labels_decode_u8). tables_dev: upload_label_tables' tensor (or
+    input_edge.LabelDecode.device_tables); image_table: per image the index of its table, -1 for the pass-through (channel 0 unchanged) -- a list or its
+    upload_image_table copy. A colour table on a one-channel slab gives its fill: input_edge.LabelDecode refuses that on the host."""
+    assert lab_u8.dim() in (3, 4) and lab_u8.dtype == torch.uint8 and lab_u8.is_contiguous() and lab_u8.is_cuda
+    n, h, w = lab_u8.shape[:3]
+    c = _label_channels(lab_u8, (n, h, w))
+    size = ctypes.sizeof(L.PmLabelTable)
+    assert tables_dev.is_cuda and tables_dev.dtype == torch.uint8 and tables_dev.is_contiguous() and tables_dev.numel() % size == 0, 'not an upload_label_tables tensor'
+    it = upload_image_table(image_table, lab_u8.device)
+    assert it.numel() == n, 'image_table for %d images, batch of %d' % (it.numel(), n)
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=lab_u8.device)
+    check(_lib().pm_labels_decode_u8(lab_u8.data_ptr(), n, h, w, c, tables_dev.data_ptr(), tables_dev.numel() // size, size, it.data_ptr(), out.data_ptr(), stream()),
+          'pm_labels_decode_u8')
+    return out
+
+
+def resample_crop_decode_u8(img_u8, lab_u8, geo, tables_dev, image_table):
+    """resample_crop_u8 with the mask decoded in its gather (pm_resample_crop_decode_u8): lab_u8 is the raw uint8 [N,Hs,Ws,3] or [N,Hs,Ws] slab, tables_dev and
+    image_table as labels_decode_u8 takes them. The label crop equals labels_decode_u8 of the whole slab followed by resample_crop_u8, the image crop resample_crop_u8's.
+    image_table travels in the geometry's pinned block (upload_geo); with an uploaded GeoDevice it must have been uploaded with one."""
+    n, hs, ws, c = img_u8.shape
+    assert c == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.is_cuda
+    assert lab_u8.dtype == torch.uint8 and lab_u8.is_contiguous() and lab_u8.device == img_u8.device
+    lc = _label_channels(lab_u8, (n, hs, ws))
+    size = ctypes.sizeof(L.PmLabelTable)
+    assert tables_dev.is_cuda and tables_dev.dtype == torch.uint8 and tables_dev.is_contiguous() and tables_dev.numel() % size == 0, 'not an upload_label_tables tensor'
+    gd = upload_geo(geo, img_u8.device, (hs, ws), image_table)
+    assert gd.n == n, 'geometry for %d images, batch of %d' % (gd.n, n)
+    th, tw = gd.crop
+    out = torch.empty((n, th, tw, 3), dtype=torch.uint8, device=img_u8.device)
+    out_lab = torch.empty((n, th, tw), dtype=torch.uint8, device=img_u8.device)
+    p, o = gd.buf.data_ptr(), gd.offsets
+    check(_lib().pm_resample_crop_decode_u8(img_u8.data_ptr(), lab_u8.data_ptr(), n, hs, ws, p + o[0], ctypes.sizeof(L.PmGeoImage), p + o[1], p + o[2], p + o[3], p + o[4],
+                                            th, tw, gd.ignore_index, lc, tables_dev.data_ptr(), tables_dev.numel() // size, size, p + o[5], out.data_ptr(),
+                                            out_lab.data_ptr(), stream()), 'pm_resample_crop_decode_u8')
     return out, out_lab
 
 

@@ -50,7 +50,16 @@ class PmGeoImage(ctypes.Structure):
     _fields_ = [('h_in', c_int32), ('w_in', c_int32), ('h', c_int32), ('w', c_int32), ('pad_h', c_int32), ('pad_w', c_int32), ('y1', c_int32), ('x1', c_int32)]
 
 
-RESAMPLE_MAX_TAPS = 24                     # include/pinmem_hip.h PM_RESAMPLE_MAX_TAPS
+LABEL_SLOTS, LABEL_MAX_COLORS = 256, 128   # include/pinmem_hip.h PM_LABEL_SLOTS, PM_LABEL_MAX_COLORS
+LABEL_IDS, LABEL_COLORS = 0, 1             # pm_label_table.mode
+
+
+class PmLabelTable(ctypes.Structure):
+    """include/pinmem_hip.h pm_label_table: the decoding table of one dataset's masks (built on the host, an array of these lives in device memory)."""
+    _fields_ = [('mode', c_int32), ('fill', c_int32), ('lut', ctypes.c_uint8 * 256), ('keys', ctypes.c_uint32 * LABEL_SLOTS), ('vals', ctypes.c_uint8 * LABEL_SLOTS)]
+
+
+RESAMPLE_MAX_TAPS = 24                # include/pinmem_hip.h PM_RESAMPLE_MAX_TAPS
 RESAMPLE_REC = RESAMPLE_MAX_TAPS + 2       # PM_RESAMPLE_REC
 
 
@@ -67,7 +76,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 420          # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 430         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -142,6 +151,10 @@ SIGNATURES = {
     'pm_labels_u8_flip_to_i64': (_i, [_vp, _i, _i, _i, _vp, c_int32, _vp, _vp]),
     'pm_resample_tables': (_i, [_vp, c_int32, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'pm_resample_crop_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, c_int32, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'pm_label_table_ids': (_i, [_vp, _vp, _i, _vp, c_int32]),
+    'pm_label_table_colors': (_i, [_vp, _vp, _i, _i, _vp, c_int32]),
+    'pm_labels_decode_u8': (_i, [_vp, _i, _i, _i, _i, _vp, _i, c_int32, _vp, _vp, _vp]),
+    'pm_resample_crop_decode_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, c_int32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, c_int32, _vp, _vp, _vp, _vp]),
     'pm_nchw_to_nhwc': (_i, [_vp, _i, _T, _vp]),
     'pm_nhwc_to_nchw': (_i, [_T, _vp, _vp]),
     'pm_label_nearest': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),

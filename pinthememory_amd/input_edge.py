@@ -16,6 +16,11 @@ the hard ColorJitter(0.8, 0.8, 0.8, 0.3) + blur of the meta-test domains, :128-1
 In front of it, the joint transform of the same scripts -- RandomSizeAndCrop (transforms/joint_transforms.py:414-444: bicubic resize by a random scale, nearest for the
 mask, pad, random crop) -- runs on the uint8 pixels in HBM too, for the crop window alone and with PIL's bytes (`pm_resample_crop_u8`): `GeometricAugment` draws scale
 and crop origin. The reference's order is kept: joint transforms, image-only transforms, ToTensor.
+
+And in front of that, the datasets' own label decoding -- the loop over `color_to_trainid` of datasets/gtav.py:440-445 (three whole-image compares per entry) and over
+`trainid_to_trainid` / `id_to_trainid` of synthia.py:254-257 and cityscapes.py -- is a table lookup per pixel (`pm_labels_decode_u8`), and with a geometry a step of its
+mask gather (`pm_resample_crop_decode_u8`: a per-pixel map commutes with a nearest gather, so only the crop window is decoded, to the same bytes). `LabelDecode` holds
+the tables the datasets hand over.
 """
 import torch
 
@@ -162,6 +167,91 @@ class GeometricAugment:
         return geo
 
 
+class LabelDecode:
+    """The label tables of the datasets behind one loader, for decoding raw masks on the device (`pm_labels_decode_u8`, `pm_resample_crop_decode_u8`) instead of in
+    the per-image host loops of the reference's datasets. The package carries no table of its own: a dataset passes the dicts it already has --
+      add_colors(gtav.color_to_trainid): {(r, g, b): train id}; a pixel whose colour is not listed, or is listed with 255 / -1, becomes ignore_index (gtav.py:440-445);
+      add_ids(synthia.trainid_to_trainid / cityscapes.id_to_trainid): {id: train id}, unlisted ids unchanged, -1 stored as 255 (synthia.py:254-257)
+    -- and gets the table's index back. A batch then names one table per image (-1 or None: the mask holds train ids already, channel 0 is passed through). Tables are
+    built by the library's host builders and uploaded once per device."""
+
+    def __init__(self, ignore_index=255):
+        if not 0 <= int(ignore_index) <= 255:
+            raise ValueError('ignore_index %r outside 0..255' % (ignore_index,))
+        self.ignore_index = int(ignore_index)
+        self.tables, self.kinds = [], []
+        self._dev = {}          # device -> (uint8 tensor of the tables, event of its upload)
+
+    def __len__(self):
+        return len(self.tables)
+
+    def _add(self, table, kind):
+        self.tables.append(table)
+        self.kinds.append(kind)
+        self._dev.clear()
+        return len(self.tables) - 1
+
+    def add_colors(self, mapping):
+        if not isinstance(mapping, dict) or not mapping:
+            raise ValueError('add_colors takes a non-empty dict {(r, g, b): value}')
+        for k, v in mapping.items():
+            if not (isinstance(k, (tuple, list)) and len(k) == 3 and all(int(c) == c for c in k)) or int(v) != v:
+                raise ValueError('colour entry %r: %r is not (r, g, b): integer' % (k, v))
+        return self._add(K.label_table_colors(mapping, self.ignore_index), 'colors')
+
+    def add_ids(self, mapping):
+        if not isinstance(mapping, dict) or not mapping:
+            raise ValueError('add_ids takes a non-empty dict {id: value}')
+        for k, v in mapping.items():
+            if isinstance(k, (tuple, list)) or int(k) != k or int(v) != v:
+                raise ValueError('id entry %r: %r is not integer: integer' % (k, v))
+        return self._add(K.label_table_ids(mapping), 'ids')
+
+    def image_table(self, entries, n, channels):
+        """One table index per image (-1 = pass-through) from `entries` (index, -1 or None each), checked on the host for what the device cannot report."""
+        entries = list(entries)
+        if len(entries) != n:
+            raise ValueError('%d table entries for %d images' % (len(entries), n))
+        out = []
+        for i, e in enumerate(entries):
+            e = -1 if e is None else int(e)
+            if not -1 <= e < len(self.tables):
+                raise ValueError('image %d: table %d, have %d' % (i, e, len(self.tables)))
+            if e >= 0 and self.kinds[e] == 'colors' and channels != 3:
+                raise ValueError('image %d: a colour table on a %d-channel label slab' % (i, channels))
+            out.append(e)
+        return out
+
+    def device_tables(self, device):
+        """The tables in device memory (uploaded at the first call per device), ready on the current stream."""
+        device = torch.device(device)
+        if device not in self._dev:
+            ev = torch.cuda.Event()
+            buf = K.upload_label_tables(self.tables, device)
+            ev.record(torch.cuda.current_stream(device))
+            self._dev[device] = (buf, ev)
+        buf, ev = self._dev[device]
+        torch.cuda.current_stream(device).wait_event(ev)
+        return buf
+
+    def decode(self, lab_d, entries):
+        """Raw uint8 [N,H,W] or [N,H,W,3] masks on the device -> uint8 train ids [N,H,W]."""
+        table = self.image_table(entries, lab_d.shape[0], 3 if lab_d.dim() == 4 else 1)
+        return K.labels_decode_u8(lab_d, self.device_tables(lab_d.device), table)
+
+
+def domain_entries(domain_tables, lead):
+    """Table entry per merged image of a [B, D, ...] batch (image b * D + d takes domain_tables[d]); lead: the axes in front of H, W."""
+    d = lead[-1] if len(lead) >= 2 else 1
+    domain_tables = [None] * d if domain_tables is None else list(domain_tables)
+    if len(domain_tables) != d:
+        raise ValueError('%d domain_tables for %d domains' % (len(domain_tables), d))
+    total = 1
+    for v in lead:
+        total *= v
+    return [domain_tables[i % d] for i in range(total)]
+
+
 def hard_flags(label_shape, hard_domains):
     """One bool per image of a [B, D, H, W] label batch after the domain axis merged into the batch (image b * D + d): is d one of hard_domains?"""
     if not hard_domains:
@@ -192,9 +282,13 @@ class DevicePrefetcher:
     reassign between batches -- it is read when a batch is ISSUED, i.e. `depth` batches before that batch is returned.
     geometry (a GeometricAugment, default None = no geometry): every batch is resized, padded and cropped on the side stream first (`pm_resample_crop_u8`); the plain
     conversion or the augmentation then runs on the crop. The source may then yield a third item, a dict with per-image 'sizes' ((H, W): the image lies in the
-    top-left corner of its slab) and / or 'centroids'; without it every image fills its slab."""
+    top-left corner of its slab) and / or 'centroids'; without it every image fills its slab.
+    decode (a LabelDecode, default None = the masks hold train ids) with domain_tables (one entry per index of the D axis: a table index of `decode`, -1 or None for
+    the pass-through): the source's masks are raw, [B, D, H, W] ids or [B, D, H, W, 3] colours (an id-coded domain of a mixed batch keeps its id in channel 0), and
+    are decoded on the side stream -- inside the mask gather of the geometry where there is one (`pm_resample_crop_decode_u8`), else by `pm_labels_decode_u8` in front
+    of the conversion. What follows sees decoded uint8 train ids."""
 
-    def __init__(self, source, depth=1, device=None, augment=None, hard_domains=None, geometry=None):
+    def __init__(self, source, depth=1, device=None, augment=None, hard_domains=None, geometry=None, decode=None, domain_tables=None):
         assert torch.cuda.is_available(), 'the input edge stages into HBM: needs a GPU'
         self.src, self.depth = iter(source), depth
         self.host_ring = max(1, len(getattr(source, 'bufs', [])) or 1)          # pinned buffers the source rotates through
@@ -203,6 +297,8 @@ class DevicePrefetcher:
         self.slots, self.copied, self.ready = [None] * (depth + 1), [], []
         self.n = 0
         self.augment, self.hard_domains, self.geometry = augment, hard_domains, geometry
+        assert decode is not None or domain_tables is None, 'domain_tables without a LabelDecode'
+        self.decode, self.domain_tables = decode, domain_tables
         for _ in range(depth):
             self._issue()
 
@@ -214,22 +310,33 @@ class DevicePrefetcher:
         k = self.n % len(self.slots)
         self.n += 1
         h, w = img_h.shape[-3:-1]
+        lead = tuple(img_h.shape[:-3])                                         # the axes that merge into the batch
+        lab_tail = (h, w)
+        if self.decode is not None:                                            # raw masks: [.., H, W] ids or [.., H, W, 3] colours
+            lab_tail = (h, w, 3) if lab_h.dim() == img_h.dim() else (h, w)
+            table = self.decode.image_table(domain_entries(self.domain_tables, lead), img_h.numel() // (h * w * 3), 3 if len(lab_tail) == 3 else 1)
         with torch.cuda.stream(self.side):
             if self.slots[k] is None:
                 self.slots[k] = (torch.empty(img_h.reshape(-1, h, w, 3).shape, dtype=torch.uint8, device=self.dev),
-                                 torch.empty(lab_h.reshape(-1, h, w).shape, dtype=torch.uint8, device=self.dev))
+                                 torch.empty(lab_h.reshape(-1, *lab_tail).shape, dtype=torch.uint8, device=self.dev))
             img_d, lab_d = self.slots[k]
             img_d.copy_(img_h.reshape(-1, h, w, 3), non_blocking=True)        # train.py:297-307: the domain axis merges into the batch
-            lab_d.copy_(lab_h.reshape(-1, h, w), non_blocking=True)
+            lab_d.copy_(lab_h.reshape(-1, *lab_tail), non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.side)
             if self.geometry is not None:                                      # RandomSizeAndCrop first: what follows sees the crop
-                img_d, lab_d = K.resample_crop_u8(img_d, lab_d, sample_geometry(self.geometry, img_d.shape, item[2] if len(item) > 2 else None))
+                geo = sample_geometry(self.geometry, img_d.shape, item[2] if len(item) > 2 else None)
+                if self.decode is None:
+                    img_d, lab_d = K.resample_crop_u8(img_d, lab_d, geo)
+                else:                                                          # the masks are decoded in the gather
+                    img_d, lab_d = K.resample_crop_decode_u8(img_d, lab_d, geo, self.decode.device_tables(self.dev), table)
+            elif self.decode is not None:
+                lab_d = K.labels_decode_u8(lab_d, self.decode.device_tables(self.dev), table)
             if self.augment is None:
                 x = ops.nchw(K.image_u8_to_nhwc4(img_d))
                 gt = K.labels_u8_to_i64(lab_d)
             else:
-                params = K.upload_aug_params(self.augment.sample(img_d.shape[0], hard_flags(lab_h.shape, self.hard_domains)), self.dev)
+                params = K.upload_aug_params(self.augment.sample(img_d.shape[0], hard_flags(lead + (h, w), self.hard_domains)), self.dev)
                 x = ops.nchw(K.augment_u8(img_d, params))
                 gt = K.labels_u8_to_i64(lab_d, params)
             ev = torch.cuda.Event()
