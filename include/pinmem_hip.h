@@ -51,8 +51,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * 410: pm_aug_image and the augmenting input edge (pm_augment_u8, pm_labels_u8_flip_to_i64); the size of that struct is an ARGUMENT of the calls that read it,
  * because the array lives in device memory where the library cannot look at a first member.
  * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS.
- * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8). */
-#define PM_ABI_VERSION 430
+ * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8).
+ * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace). */
+#define PM_ABI_VERSION 440
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -335,6 +336,31 @@ int pm_softmax_mean_update(const pm_tensor* logits, double* buffer, int counter,
  * the covering tiles (tile order) / tile count, written to acc[C][H][W] at the un-flipped column (flip_w); accumulate != 0 adds to acc. */
 int pm_sliding_stitch(const pm_tensor* logits, const int32_t* tiles_xyxy, int ntiles, int H, int W, int flip_w, double* acc, int accumulate, void* stream);
 int pm_argmax_f64(const double* buffer, int n, int h, int w, int c, int64_t* out_cls, double* out_prob /*nullable*/, void* stream);
+/* Sliding-window evaluation of one (image, scale) from the heads' LOW-RES logits (eval.py:340-405 inference_sliding, :158-194 the tiles, :210-274 reverse_mapping /
+ * reverse_sliding_window, :197-207 resize_thread). logits: [flips * ntiles][h][w] pixels of `pitch` >= C floats, the un-flipped tiles first, then those of the mirrored
+ * image, both in table order. tiles_xyxy: HOST array of ntiles x (x1, y1, x2, y2) in the scaled image Hs x Ws, all of one size th x tw (th != tw allowed), together
+ * covering every pixel; the library copies it into the workspace, so any number of tiles is taken and the array need not outlive the call. Per scaled-image pixel and
+ * flip: the covering tiles, in table order, are up-sampled to th x tw (bilinear, align_corners=True, fp32: the arithmetic of pm_resize_bilinear_fwd), widened to double,
+ * summed and divided by the cover count; the mirrored stack is read at column Ws - 1 - x (np.fliplr). Neither the up-sampled tiles nor the stitched map is written.
+ *   acc == NULL (one scale; Hs == H, Ws == W): the pixel's value is (flip0 + flip1) / flips (np.mean(batch_return, axis=0)). pred (nullable, uint8 [H][W]): the LOWEST
+ *     class among the maxima, as pm_upsample_eval. labels (nullable, int64 [H][W]): hist[label][pred] += 1 for 0 <= label < C (fast_hist, utils/misc.py:65-70),
+ *     int64 [C][C], accumulate 0: overwritten, 1: added to; integer counts, deterministic; without labels hist is not touched. logits_out (nullable, float64
+ *     [C][H][W]): the mean logits.
+ *   acc != NULL (float64 [C][H][W]; labels, hist, pred and logits_out must be NULL): each flip's stitched map is resampled to H x W as cv2.resize(INTER_LINEAR) does
+ *     for float64 -- per axis f = float((d + 0.5) * (double(S) / D) - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= S - 1: s = S - 1, one tap; float weights
+ *     1.f - f and f; horizontal a * w0 + b * w1 in double, then vertical -- from at most four scaled-image pixels stitched on the fly. The mean over the flips is
+ *     written to acc (acc_add 0, the first scale) or added to it (1). pm_sliding_eval_finish then takes acc / nscales (np.mean over the scales, eval.py:647) to
+ *     pred / hist / logits_out as above; logits_out may be acc itself.
+ * ws: pm_sliding_eval_workspace(ntiles, C, H, W) bytes (the finish call: ntiles = 0). PM_EINVAL: null pointers, flips not 1 or 2, a tile outside Hs x Ws or of another
+ * size than the first, an uncovered pixel; PM_EUNSUPPORTED: C > 32; PM_EWORKSPACE: too few bytes -- each before any launch. The cover check is host work of
+ * O(ntiles log ntiles + cells) per call, cells between the tiles' distinct edges: (columns + 1) x (rows + 1) for a regular grid, at most (2 ntiles + 1)^2.
+ * A 16-byte aligned `logits` with pitch % 4 == 0 (the heads' padded rows) is read with 16-byte loads; any other with 4-byte loads, about 2.6 times slower, same bits. */
+size_t pm_sliding_eval_workspace(int ntiles, int C, int H, int W);
+int pm_sliding_eval(const float* logits, int n, int h, int w, int C, int64_t pitch, int flips, const int32_t* tiles_xyxy, int ntiles, int Hs, int Ws, int H, int W,
+                    const int64_t* labels /*nullable*/, int64_t* hist, int accumulate, uint8_t* pred /*nullable*/, double* logits_out /*nullable*/,
+                    double* acc /*nullable*/, int acc_add, void* ws, size_t ws_bytes, void* stream);
+int pm_sliding_eval_finish(const double* acc, int C, int H, int W, int nscales, const int64_t* labels /*nullable*/, int64_t* hist, int accumulate,
+                           uint8_t* pred /*nullable*/, double* logits_out /*nullable*/, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- input edge: ToTensor + Normalize(ImageNet) (datasets/gtav.py:284-289) and MaskToTensor
  * (transforms/transforms.py:95-97) on the GPU: uint8 HWC images -> normalised NHWC4 fp32 (zero 4th channel, the stem's layout),

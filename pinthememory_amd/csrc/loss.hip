@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int MAXC = 32;
+constexpr int MAXC = PM_MAX_CLASSES;
 
 struct CEGeom {
   const float* logits;
@@ -861,7 +861,6 @@ extern "C" int pm_upsample_ce_bwd(const pm_tensor* logits, float inv_temp, const
 namespace {
 constexpr int EVAL_MAX_ROWS = 8;                   // hi-res rows per block, at most
 constexpr size_t EVAL_MAX_LDS = 159 * 1024;        // dynamic part (two staged rows + the counters); the kernel also declares 256 B of static LDS
-constexpr int EVAL_FOLD_T = 1024;                  // fold kernel: 32 histogram entries x 32 slices of the count rows
 
 struct EvalPlan {
   bool ok;
@@ -952,20 +951,6 @@ __global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int r
   for (int i = threadIdx.x; i < C * C; i += 256) counts[(long)bid * C * C + i] = cnt[i];
 }
 
-// hist[e] (+)= sum over the blocks' count rows: 32 entries x 32 slices of the rows per block, integer adds only
-__global__ __launch_bounds__(EVAL_FOLD_T) void eval_fold_kernel(const unsigned* __restrict__ counts, int nblk, int entries, int accumulate, int64_t* __restrict__ hist) {
-  __shared__ unsigned long long tot[32];
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), sl = threadIdx.x >> 5;
-  if (threadIdx.x < 32) tot[threadIdx.x] = 0ull;
-  __syncthreads();
-  unsigned long long a = 0ull;
-  if (e < entries)
-    for (int r = sl; r < nblk; r += EVAL_FOLD_T / 32) a += counts[(long)r * entries + e];
-  if (a) atomicAdd(&tot[threadIdx.x & 31], a);
-  __syncthreads();
-  if (threadIdx.x < 32 && e < entries) hist[e] = (accumulate ? hist[e] : 0) + (int64_t)tot[threadIdx.x];
-}
-
 template <int CC>
 void eval_launch(const CEGeom& g, const EvalPlan& p, float* part, unsigned* counts, uint8_t* pred, hipStream_t st) {
   static pm_lds_optin optin;      // > 64 KB of dynamic LDS (rows wider than ~420 pixels x 19 classes: one Cityscapes image has 512) needs the opt-in
@@ -994,7 +979,7 @@ extern "C" int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const i
   unsigned* counts = (unsigned*)((char*)ws + p.part_bytes);
   ce_dispatch(g.C, false, [&](auto cc, auto) { eval_launch<decltype(cc)::value>(g, p, part, counts, pred, st); });
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, g.n * H, loss_out);
-  hipLaunchKernelGGL(eval_fold_kernel, dim3((g.C * g.C + 31) / 32), dim3(EVAL_FOLD_T), 0, st, (const unsigned*)counts, g.n * p.chunks, g.C * g.C, accumulate, hist);
+  hipLaunchKernelGGL(pm_hist_fold_kernel, dim3((g.C * g.C + 31) / 32), dim3(PM_HIST_FOLD_T), 0, st, (const unsigned*)counts, g.n * p.chunks, g.C * g.C, accumulate, hist);
   return pm_check_launch("upsample_eval");
 }
 

@@ -265,6 +265,27 @@ __device__ __forceinline__ float pm_wave_max(float v) {
   return v;
 }
 
+// the class limit of the loss and evaluation kernels (per-class registers, C x C LDS counters)
+constexpr int PM_MAX_CLASSES = 32;
+
+// Confusion-matrix fold of the evaluation kernels (loss.hip, sliding_eval.hip): hist[e] (+)= sum over the blocks' count rows: 32 entries x 32 slices of the rows per
+// block, integer adds only -- order-free, so deterministic. `static`: each of the two translation units that launch it compiles its own copy, and one that
+// never names it emits no code for it, so the other sources' code objects are what they were.
+constexpr int PM_HIST_FOLD_T = 1024;
+static __global__ __launch_bounds__(PM_HIST_FOLD_T) void pm_hist_fold_kernel(const unsigned* __restrict__ counts, int nblk, int entries, int accumulate,
+                                                                             int64_t* __restrict__ hist) {
+  __shared__ unsigned long long tot[32];
+  const int e = blockIdx.x * 32 + (threadIdx.x & 31), sl = threadIdx.x >> 5;
+  if (threadIdx.x < 32) tot[threadIdx.x] = 0ull;
+  __syncthreads();
+  unsigned long long a = 0ull;
+  if (e < entries)
+    for (int r = sl; r < nblk; r += PM_HIST_FOLD_T / 32) a += counts[(long)r * entries + e];
+  if (a) atomicAdd(&tot[threadIdx.x & 31], a);
+  __syncthreads();
+  if (threadIdx.x < 32 && e < entries) hist[e] = (accumulate ? hist[e] : 0) + (int64_t)tot[threadIdx.x];
+}
+
 // ATen's align_corners=True source-index math, in fp32 exactly as area_pixel_compute_scale /
 // area_pixel_compute_source_index do it (scale = (in-1)/(out-1) in float, src = scale*dst).
 struct pm_lerp {

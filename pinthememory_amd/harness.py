@@ -520,6 +520,121 @@ def validate(net, batches, criterion=None, classes=19, dump=10, decode=None, tab
                 predictions=predictions)
 
 
+# ---- sliding-window evaluation: what every eval_*.sh runs (eval.py --inference_mode sliding; :340-405, :630-653, :695-702) ----------------------------
+def _scaled_u8(img, scale):
+    """eval.py:357-358: img.resize((int(w * scale), int(h * scale)), Image.BILINEAR) of a HOST uint8 [H, W, 3] image."""
+    import numpy as np
+    from PIL import Image
+    if img.is_cuda:
+        raise ValueError('evaluate_sliding: a scale other than 1 is resized by PIL on the host -- pass the image as a host tensor')
+    h, w = img.shape[:2]
+    pil = Image.fromarray(img.contiguous().numpy()).resize((int(w * scale), int(h * scale)), Image.BILINEAR)
+    return torch.from_numpy(np.array(pil))
+
+
+def tile_stack(parts):
+    """The heads' low-res logits of every forward of one (image, scale), NHWC views [n_i, h, w, C] in the order K.sliding_eval reads them -> ONE [sum n_i, h, w, C] view
+    whose pixels keep the heads' 16-byte pitch (K.new(pitch_pad=True): 20 floats for 19 classes), which the kernels' 16-byte loads need. torch.cat would pack the
+    pixels to C floats and send every launch to the 4-byte loads (profiles/sliding_eval_probe.txt). A single part that has that pitch is handed on as it is."""
+    if len(parts) == 1 and parts[0].stride(2) % 4 == 0 and parts[0].data_ptr() % 16 == 0:
+        return parts[0]
+    _, h, w, c = parts[0].shape
+    low = K.new((sum(p.shape[0] for p in parts), h, w, c), parts[0], pitch_pad=True, dtype=torch.float32)
+    at = 0
+    for p in parts:
+        low[at:at + p.shape[0]].copy_(p)
+        at += p.shape[0]
+    return low
+
+
+def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3, flips=(False, True), hist=None, want_logits=False, batch_tiles=True):
+    """eval.py:340-405 (inference_sliding) and :647-653 (mean over the scales, argmax, fast_hist) for ONE image. Per scale: the image is scaled (PIL on the host; scale 1
+    is sliced on the device as it is), normalised (K.image_u8_to_nhwc4), cut into sliding_tiles and forwarded -- mirrored too unless flips=(False,) -- with the heads
+    returning their LOW-RES logits; one K.sliding_eval launch sequence then up-samples, stitches, un-flips and averages them without writing the up-sampled tiles or
+    a stitched map. At scales=(1.0,) the same launch takes the argmax and adds fast_hist(pred, gt) into `hist`; with more scales each one is resampled to the image's
+    size (cv2.resize INTER_LINEAR) into a float64 accumulator and K.sliding_eval_finish yields the class map and the histogram. Nothing is copied to the host.
+    img: uint8 [H, W, 3], host or device; a normalised float [3, H, W] is taken when every scale is 1. gt: [H, W] train ids (255 = ignore) or None. hist: int64
+    [C, C] on the device to add into (None: a fresh one when gt is given). batch_tiles=False forwards tile by tile (eval.py:383-390, without --faster).
+    -> dict(pred uint8 [H, W], hist, logits float64 [C, H, W] with want_logits else None). Leaves the net in eval mode."""
+    m = net.module if hasattr(net, 'module') else net
+    device = next(m.parameters()).device
+    scales, flips = tuple(float(s) for s in scales), tuple(bool(f) for f in flips)
+    assert len(scales) >= 1 and flips in ((False,), (False, True)), 'flips: (False,) or (False, True) -- the image, then its mirror (eval.py:362-370)'
+    as_u8 = img.dtype == torch.uint8
+    if as_u8:
+        assert img.dim() == 3 and img.shape[2] == 3, 'uint8 images are [H, W, 3]'
+        H, W = img.shape[:2]
+    else:
+        if any(s != 1.0 for s in scales):
+            raise ValueError('evaluate_sliding: a normalised float image cannot be re-scaled as the reference scales its uint8 image; pass uint8 [H, W, 3]')
+        assert img.dim() == 3 and img.shape[0] == 3 and img.is_floating_point(), 'float images are normalised [3, H, W]'
+        H, W = img.shape[1:]
+    if gt is not None:
+        gt = gt.to(device=device, dtype=torch.int64).reshape(H, W).contiguous()
+    single = scales == (1.0,)
+    net.eval()
+    acc = None
+    was = m.eval_logits_lowres
+    m.eval_logits_lowres = True
+    try:
+        with torch.no_grad():
+            for i, s in enumerate(scales):
+                if as_u8:
+                    x = K.image_u8_to_nhwc4((img if s == 1.0 else _scaled_u8(img, s)).to(device)[None].contiguous())[0]      # [Hs, Ws, 4]
+                    Hs, Ws = x.shape[:2]
+                else:
+                    x, Hs, Ws = img.to(device), H, W
+                tiles = sliding_tiles(Hs, Ws, crop, overlap, s)
+                lows = []
+                for flip in flips:
+                    if as_u8:
+                        src = torch.flip(x, dims=[1]) if flip else x
+                        crops = ops.nchw(torch.stack([src[y1:y2, x1:x2] for (x1, y1, x2, y2) in tiles]))
+                    else:
+                        src = torch.flip(x, dims=[2]) if flip else x
+                        crops = torch.stack([src[:, y1:y2, x1:x2] for (x1, y1, x2, y2) in tiles])
+                    lows += [ops.nhwc(net(crops)[0])] if batch_tiles else [ops.nhwc(net(cr[None])[0]) for cr in crops]
+                low = tile_stack(lows)
+                assert low.stride(2) % 4 == 0, 'evaluate_sliding: the logits handed to K.sliding_eval lost the 16-byte pixel pitch of the heads (%d floats)' % low.stride(2)
+                if single:
+                    pred, hist, logits = K.sliding_eval(low, tiles, (Hs, Ws), (H, W), len(flips), labels=gt, hist=hist, want_pred=True, want_logits=want_logits)
+                else:
+                    if acc is None:
+                        acc = torch.empty((low.shape[3], H, W), dtype=torch.float64, device=device)
+                    K.sliding_eval(low, tiles, (Hs, Ws), (H, W), len(flips), acc=acc, acc_add=i > 0)
+            if not single:
+                pred, hist, logits = K.sliding_eval_finish(acc, len(scales), labels=gt, hist=hist, want_pred=True, logits_out=acc if want_logits else None)
+    finally:
+        m.eval_logits_lowres = was
+    return dict(pred=pred, hist=hist, logits=logits)
+
+
+def eval_metrics(hist):
+    """utils/misc.py:132-148 evaluate_eval_for_inference on the device, in float64: (acc, acc_cls, mean_iu, fwavacc) as a [4] tensor."""
+    h = hist.double()
+    diag, rows, total = torch.diag(h), h.sum(1), h.sum()
+    iu = diag / (rows + h.sum(0) - diag)
+    freq = rows / total
+    return torch.stack([diag.sum() / total, torch.nanmean(diag / rows), torch.nanmean(iu), torch.where(freq > 0, freq * iu, torch.zeros_like(iu)).sum()])
+
+
+def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, classes=19, dump=0):
+    """The loop of eval.py:756-779 over RunEval.inf (:630-653) and final_dump (:695-702) without the image files: `loader` yields (image, gt, ...) with the image
+    uint8 [H, W, 3] (or [1, H, W, 3]) and gt [H, W] (or [1, H, W]); every image goes through evaluate_sliding into ONE histogram on the device, and nothing is
+    copied to the host before the last image. -> dict(hist int64 [classes, classes] on the device, acc, acc_cls, mean_iu, fwavacc as evaluate_eval_for_inference
+    computes them, predictions: the uint8 class maps of the first `dump` images)."""
+    m = net.module if hasattr(net, 'module') else net
+    hist = torch.zeros((classes, classes), dtype=torch.int64, device=next(m.parameters()).device)
+    predictions = []
+    for idx, data in enumerate(loader):
+        img, gt = data[0], data[1]
+        res = evaluate_sliding(net, img[0] if img.dim() == 4 else img, gt, crop, scales, overlap, (False,) if no_flip else (False, True), hist=hist)
+        if idx < dump:
+            predictions.append(res['pred'])
+    acc, acc_cls, mean_iu, fwavacc = eval_metrics(hist).tolist()
+    return dict(hist=hist, acc=acc, acc_cls=acc_cls, mean_iu=mean_iu, fwavacc=fwavacc, predictions=predictions)
+
+
 # ---- the meta-learning regime every pinmem script runs: train_memory_mldg (train.py:493-632) ----------------------------
 def put_theta(model, theta):
     """train.py:262-277: rewire every leaf module's _parameters with (non-leaf) tensors; the HIP ops take weights as

@@ -702,6 +702,65 @@ def sliding_stitch(logits, tiles, H, W, flip_w, acc=None):
     return out
 
 
+def _sliding_outputs(C, H, W, device, labels, hist, pred, want_pred, logits_out, want_logits):
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (H, W)
+        if hist is None:
+            hist = torch.zeros((C, C), dtype=torch.int64, device=device)
+    if hist is not None:
+        assert hist.dtype == torch.int64 and hist.is_cuda and hist.is_contiguous() and tuple(hist.shape) == (C, C)
+    if pred is None and want_pred:
+        pred = torch.empty((H, W), dtype=torch.uint8, device=device)
+    if pred is not None:
+        assert pred.dtype == torch.uint8 and pred.is_cuda and pred.is_contiguous() and tuple(pred.shape) == (H, W)
+    if logits_out is None and want_logits:
+        logits_out = torch.empty((C, H, W), dtype=torch.float64, device=device)
+    if logits_out is not None:
+        assert logits_out.dtype == torch.float64 and logits_out.is_cuda and logits_out.is_contiguous() and tuple(logits_out.shape) == (C, H, W)
+    return hist, pred, logits_out
+
+
+def sliding_eval(logits, tiles, scaled_hw, out_hw, flips=2, labels=None, hist=None, accumulate=True, pred=None, want_pred=False, logits_out=None,
+                 want_logits=False, acc=None, acc_add=False):
+    """Sliding-window evaluation of one (image, scale) from the low-res logits NHWC [flips * T, h, w, C] of the tiles [(x1, y1, x2, y2)] in the scaled image
+    `scaled_hw` (the un-flipped tiles first, then the mirrored image's), include/pinmem_hip.h pm_sliding_eval.
+    acc None (one scale, scaled_hw == out_hw) -> (pred, hist, logits_out): the uint8 [H, W] class map (want_pred, or `pred` to write into), hist[label][pred] (int64
+    [C, C]; only with `labels`; created zeroed when None, else added to -- overwritten with accumulate=False) and the float64 [C, H, W] mean logits (want_logits).
+    acc given (float64 [C, H, W]) -> acc: this scale's map resampled to out_hw as cv2.resize(INTER_LINEAR) and written to it (acc_add=False) or added
+    (acc_add=True); sliding_eval_finish then yields the class map and the histogram."""
+    n, h, w, C = logits.shape
+    (Hs, Ws), (H, W) = scaled_hw, out_hw
+    T = len(tiles)
+    ld = tdesc(logits)
+    assert ld.dtype == L.PM_F32, 'sliding_eval: fp32 logits'
+    arr = (ctypes.c_int32 * (4 * T))(*[int(v) for t in tiles for v in t])
+    if acc is None:
+        hist, pred, logits_out = _sliding_outputs(C, H, W, logits.device, labels, hist, pred, want_pred, logits_out, want_logits)
+    else:
+        assert labels is None and pred is None and logits_out is None and not want_pred and not want_logits
+        assert acc.dtype == torch.float64 and acc.is_cuda and acc.is_contiguous() and tuple(acc.shape) == (C, H, W)
+    lib = _lib()
+    nb = lib.pm_sliding_eval_workspace(T, C, H, W)
+    ws = workspace(nb, logits.device)
+    check(lib.pm_sliding_eval(logits.data_ptr(), n, h, w, C, ld.pitch, int(flips), arr, T, Hs, Ws, H, W, ptr(labels), ptr(hist) if labels is not None else None,
+                              int(bool(accumulate)), ptr(pred), ptr(logits_out), ptr(acc), int(bool(acc_add)), ptr(ws), nb, stream()), 'pm_sliding_eval')
+    return acc if acc is not None else (pred, hist, logits_out)
+
+
+def sliding_eval_finish(acc, nscales, labels=None, hist=None, accumulate=True, pred=None, want_pred=False, logits_out=None, want_logits=False):
+    """The accumulator of sliding_eval after the last scale -> (pred, hist, logits_out) as sliding_eval yields them at one scale: acc / nscales (np.mean over the
+    scales, eval.py:647), its argmax and the histogram. logits_out may be `acc` itself."""
+    C, H, W = acc.shape
+    assert acc.dtype == torch.float64 and acc.is_cuda and acc.is_contiguous()
+    hist, pred, logits_out = _sliding_outputs(C, H, W, acc.device, labels, hist, pred, want_pred, logits_out, want_logits)
+    lib = _lib()
+    nb = lib.pm_sliding_eval_workspace(0, C, H, W)
+    ws = workspace(nb, acc.device)
+    check(lib.pm_sliding_eval_finish(acc.data_ptr(), C, H, W, int(nscales), ptr(labels), ptr(hist) if labels is not None else None, int(bool(accumulate)), ptr(pred),
+                                     ptr(logits_out), ptr(ws), nb, stream()), 'pm_sliding_eval_finish')
+    return pred, hist, logits_out
+
+
 def argmax_f64(buffer):
     n, h, w, c = buffer.shape
     cls = torch.empty((n, h, w), dtype=torch.int64, device=buffer.device)

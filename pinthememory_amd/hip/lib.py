@@ -76,7 +76,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 430         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 440         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -143,6 +143,9 @@ SIGNATURES = {
     'pm_softmax_mean_update': (_i, [_T, _vp, _i, _vp]),
     'pm_sliding_stitch': (_i, [_T, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     'pm_argmax_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'pm_sliding_eval_workspace': (_sz, [_i, _i, _i, _i]),
+    'pm_sliding_eval': (_i, [_vp, _i, _i, _i, _i, _i64, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    'pm_sliding_eval_finish': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'pm_image_u8_to_nhwc4': (_i, [_vp, _i64, POINTER(c_float), POINTER(c_float), _vp, _vp]),
     'pm_labels_u8_to_i64': (_i, [_vp, _i64, _vp, _vp]),
     'pm_aug_blur_weights': (_i, [ctypes.c_double, POINTER(c_int32), POINTER(ctypes.c_double)]),
