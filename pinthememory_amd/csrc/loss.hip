@@ -7,7 +7,7 @@
 // Backward: the transposed bilinear operator is separable, so the gradient is gathered in two passes without atomics
 // (deterministic): (1) per hi-res row, softmax - onehot of every hi-res pixel once (staged in LDS) reduced over its columns to the
 // low-res columns -> T[n][H][w][C]; (2) per low-res pixel, T reduced over the supporting hi-res rows.
-// Weighted forms (bool template parameter WT; the WT = false instantiations are the kernels above, unchanged): CrossEntropyLoss(weight=...), CrossEntropyLoss2d and
+// Label forms (class template parameter Form, below: hard labels unweighted / weighted, class sets). Weighted: CrossEntropyLoss(weight=...), CrossEntropyLoss2d and
 // ImageBasedCrossEntropyLoss2d (/root/reference/loss.py:20-43,71-88,120-180). Every pixel's terms are multiplied by w[image][label] and the divisor is a weight sum
 // (of the batch, or of each image with the per-image losses added in image order); pm_label_class_weights builds the image-based weight rows from the labels on
 // the device (loss.py:136-146), so the criterion needs neither the materialised logits nor a host round trip.
@@ -18,15 +18,16 @@
 namespace {
 
 constexpr int MAXC = PM_MAX_CLASSES;
+constexpr int RX_MAXC = 31;            // class sets: bit C is the ignore class
 
 struct CEGeom {
   const float* logits;
   long lp;           // pitch
   int n, h, w, C;
-  const int64_t* labels;
+  const void* labels;      // [n][H][W] words of the label form (Form::word): int64 labels or uint32 class sets
   int H, W;
   float sy, sx, inv_temp;
-  // weighted forms only (WT): w = wts[b * wstride + label]; per_image: every image is divided by its own weight sum
+  // weighted forms only: w = wts[b * wstride + class]; per_image: every image is divided by its own weight sum
   const float* wts;
   long wstride;
   int per_image;
@@ -83,51 +84,7 @@ __device__ __forceinline__ bool ce_block_partial(float& lsum, float& lcnt, float
   return true;
 }
 
-// WT: blockIdx.y = image (the final reduce needs every image's partials apart), the x blocks stride over that image's pixels; (sum w nll, sum w) per block.
-template <int C_, bool WT = false>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __restrict__ part) {
-  const int C = C_ > 0 ? C_ : g.C;
-  const long total = WT ? (long)g.H * g.W : (long)g.n * g.H * g.W;
-  const int64_t* labels = WT ? g.labels + (long)blockIdx.y * total : g.labels;
-  float lsum = 0.f, lcnt = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int64_t lab = labels[i];
-    if (lab == 255) continue;
-    if constexpr (WT) {
-      if (lab < 0 || lab >= C) continue;      // only labels of a class carry a weight
-    }
-    const int X = (int)(i % g.W), Y = (int)((i / g.W) % g.H), b = WT ? (int)blockIdx.y : (int)(i / ((long)g.W * g.H));
-    const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h), lx = pm_ac_lerp(g.sx, X, g.w);
-    float v[C_ > 0 ? C_ : MAXC];
-    interp_logits<C_>(g, b, ly, lx, v);
-    float mx = -INFINITY, vl = 0.f;
-#pragma unroll
-    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) {
-        mx = fmaxf(mx, v[c]);
-        if (c == (int)lab) vl = v[c];
-      }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) se += expf(v[c] - mx);
-    if constexpr (WT) {
-      const float wl = g.wts[(long)b * g.wstride + lab];
-      lsum += wl * ((mx + logf(se)) - vl);
-      lcnt += wl;
-    } else {
-      lsum += (mx + logf(se)) - vl;
-      lcnt += 1.f;
-    }
-  }
-  __shared__ float sm[2][4];
-  if (ce_block_partial<4>(lsum, lcnt, sm)) {
-    const long pb = WT ? (long)blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
-    part[pb * 2] = lsum, part[pb * 2 + 1] = lcnt;
-  }
-}
-
-// WT kernels whose block belongs to one image: that image's C weights, staged once per block (visible after the block's next barrier)
+// Weighted forms, kernels whose block belongs to one image: that image's C weights, staged once per block (visible after the block's next barrier)
 __device__ __forceinline__ void ce_stage_weights(const CEGeom& g, int b, float* wsm) {
   if ((int)threadIdx.x < g.C) wsm[threadIdx.x] = g.wts[(long)b * g.wstride + threadIdx.x];
 }
@@ -145,8 +102,8 @@ __device__ __forceinline__ void ce_stage_rows(const CEGeom& g, int C, int CP, in
 // int64 label -> byte: a class below 254 as itself, 255 (ignored) as 255, everything else 254: a label no class matches (as the kernels reading int64 treat it)
 __device__ __forceinline__ unsigned char ce_label_byte(int64_t l) { return (l >= 0 && l < 254) ? (unsigned char)l : (l == 255 ? 255 : 254); }
 
-// One hi-res pixel from the staged rows (L0 / L1 hold the low-res columns from x0 on): its interpolated logits v[0..C) -- the expression of interp_logits --, their
-// maximum mx and the label's logit vl. ARGMAX: the maximum by a strict > scan (not fmaxf), returning the lowest index among the maxima as output.max(1)[1].
+// Class c of a pixel, its logit vc just interpolated: the running maximum mx and the label's logit vl. ARGMAX: the maximum by a strict > scan (not fmaxf), returning
+// the lowest index among the maxima as output.max(1)[1].
 template <bool ARGMAX, typename Lab>
 __device__ __forceinline__ void ce_class_step(float vc, int c, Lab lab, float& mx, float& vl, int& arg) {
   if constexpr (ARGMAX) {
@@ -179,10 +136,199 @@ __device__ __forceinline__ void ce_grad_tap(float p, float hot, float wl, float 
   A += wa * gq, B += wb * gq;
 }
 
+// One pixel whose set holds the real classes S (not empty), v[0..C) its logits and mx their maximum: v becomes exp(v - mx), se their sum, ps the sum over S, wbar the
+// mean weight over S; returns the pixel's loss term - wbar log P_S.
+template <int C_>
+__device__ __forceinline__ float rx_term(float* v, float mx, unsigned S, const float* wsm, int C, float& se, float& ps, float& wbar) {
+  se = ce_exp_sum<C_, true>(v, mx, C);
+  float ws = 0.f;
+  ps = 0.f;
+#pragma unroll
+  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+    if (c < C && ((S >> c) & 1u)) ps += v[c], ws += wsm[c];
+  wbar = ws / (float)__popc(S);
+  return wbar * (logf(se) - logf(ps));
+}
+
+// ---- the label forms: everything the three losses differ in, as a compile-time parameter (Form) of the kernels below -------------------------------------------------
+// HardForm<false>: int64 labels, CE(ignore 255); HardForm<true>: the same with w[image][label]; SetForm: uint32 class sets, the relaxed-border loss (see the relaxed
+// section below for its terms). A form names its label word in global memory (word) and in LDS (staged), how a word is held in a register (ld) and staged (stage), when
+// a pixel is skipped, whether the image's weight row is staged (weighted) and what a pixel contributes: its loss term and count (term), its one-hot entry (hot) and
+// weight (CEPix::wl) for ce_grad_tap, and how an image's folded partials become loss_out (fold_image / fold_batch).
+enum CEWhere { CE_FLAT, CE_ROWS, CE_FIELD };      // the kernel a pixel is evaluated in: flat forward; row-staged forward and validation; a field kernel (v is kept as
+                                                  // exp(v - mx) for the taps)
+struct CEPix {      // what a pixel's term leaves for its taps
+  float se, wl, invs;      // sum of exp(v - mx); the weight on (p - hot); sets: 1 / P_S
+};
+
+template <bool WT>
+struct HardForm {
+  using word = int64_t;
+  using staged = unsigned char;
+  using held = int;      // a staged label in a register
+  static constexpr bool weighted = WT, sets = false;
+  static constexpr bool prefetch = true;      // the row-staged forward loads a lane's first three words before it stages the logit rows
+  static constexpr word none = 255;      // a word that skips its pixel
+  // Weighted field kernel of a generic class count: a label that is no class weighs 0 by a select, not by a skip -- the skip's branch tells the compiler that C > 0, it
+  // then lays out the class loop differently and contracts the interpolation of class 0 into another fma than the unweighted kernel does (1 ulp)
+  template <int C_, CEWhere K>
+  static constexpr bool select = WT && C_ == 0 && K == CE_FIELD;
+  // The row-staged forward of that class count meets the same through its skip once the lerp loop is a function of its own (the flat forward does not): there the
+  // class count enters the comparison through a readfirstlane, which the compiler's value tracking does not see through
+  template <int C_, CEWhere K>
+  static constexpr bool opaque = WT && C_ == 0 && K == CE_ROWS;
+  static __device__ __forceinline__ word ld(word l, int) { return l; }
+  static __device__ __forceinline__ staged stage(word l, int) { return ce_label_byte(l); }
+  template <int C_, CEWhere K, typename Lab>
+  static __device__ __forceinline__ bool skip(Lab lab, int C) {
+    if (lab == 255) return true;
+    if constexpr (WT && !select<C_, K>) return lab < 0 || lab >= (opaque<C_, K> ? __builtin_amdgcn_readfirstlane(C) : C);      // only labels of a class carry a weight
+    else return false;
+  }
+  template <typename Lab>
+  static __device__ __forceinline__ Lab pick(Lab lab) { return lab; }      // the class whose logit ce_class_step picks out of the lerp loop
+  // v: the pixel's logits, mx their maximum, vl the label's; own: the pixel counts for this block's partial
+  template <int C_, CEWhere K, typename Lab>
+  static __device__ __forceinline__ CEPix term(float* v, float mx, float vl, Lab lab, const float* wsm, int C, bool own, float& lsum, float& lcnt) {
+    CEPix q{0.f, 1.f, 0.f};
+    if constexpr (K == CE_FLAT) {      // libm's expf, as this kernel always had it (ce_exp_sum came with the row-staged forward)
+#pragma unroll
+      for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+        if (c < C) q.se += expf(v[c] - mx);
+    } else {
+      q.se = ce_exp_sum<C_, K == CE_FIELD>(v, mx, C);
+    }
+    if constexpr (WT) {
+      if constexpr (select<C_, K>) q.wl = lab < C ? wsm[min((int)lab, MAXC - 1)] : 0.f;
+      else q.wl = wsm[lab];
+      if (own) lsum += q.wl * ((mx + logf(q.se)) - vl), lcnt += q.wl;
+    } else {
+      if (own) lsum += (mx + logf(q.se)) - vl, lcnt += 1.f;
+    }
+    return q;
+  }
+  template <typename Lab>
+  static __device__ __forceinline__ float hot(const CEPix&, float, int c, Lab lab) { return c == lab ? 1.f : 0.f; }
+  // (sum w nll, sum w) = (s, d) of image b: out[2 + b] = its weight sum; per_image: out[0] = sum over b, in index order, of s_b / d_b -- 0 / 0 = NaN for an image without
+  // a weighted pixel, as nll_loss -- and out[1] = total weight sum. Without per_image, out[0] and out[1] are ce_final_kernel's (same order as the unweighted loss).
+  static __device__ __forceinline__ void fold_image(double s, double d, int b, int, float* out, double& loss, double& den) {
+    out[2 + b] = (float)d;
+    loss += s / d;
+    den += d;
+  }
+  static __device__ __forceinline__ void fold_batch(double loss, double den, int, int per_image, float* out) {
+    if (per_image) {
+      out[0] = (float)loss;
+      out[1] = (float)den;
+    }
+  }
+};
+
+struct SetForm {
+  using word = uint32_t;
+  using staged = uint32_t;      // four bytes a pixel
+  using held = uint32_t;
+  static constexpr bool weighted = true, sets = true;
+  static constexpr bool prefetch = false;
+  static constexpr word none = 0u;
+  static __device__ __forceinline__ word ld(word s, int C) { return s & ((1u << C) - 1u); }      // the real classes of the set
+  static __device__ __forceinline__ staged stage(word s, int C) { return ld(s, C); }
+  template <int C_, CEWhere K>
+  static __device__ __forceinline__ bool skip(unsigned S, int) { return !S; }
+  static __device__ __forceinline__ int pick(unsigned) { return -1; }      // no label logit
+  template <int C_, CEWhere K>
+  static __device__ __forceinline__ CEPix term(float* v, float mx, float, unsigned S, const float* wsm, int C, bool own, float& lsum, float& lcnt) {
+    CEPix q;
+    float ps;
+    const float t = rx_term<C_>(v, mx, S, wsm, C, q.se, ps, q.wl);
+    if (own) lsum += t, lcnt += 1.f;
+    q.invs = 1.f / ps;
+    return q;
+  }
+  static __device__ __forceinline__ float hot(const CEPix& q, float e, int c, unsigned S) { return (S >> c) & 1u ? e * q.invs : 0.f; }
+  // (sum of terms, valid pixels) = (s, d) of image i: out[2 + i] = loss_i = s / (d + 1), out[2 + n + i] = (d + 1) n: what the row pass divides image i by;
+  // out[0] = sum_i loss_i / n, out[1] = valid pixels of the batch
+  static __device__ __forceinline__ void fold_image(double s, double d, int b, int n, float* out, double& loss, double& den) {
+    const double li = s / (d + 1.0);
+    out[2 + b] = (float)li;
+    out[2 + n + b] = (float)((d + 1.0) * (double)n);
+    loss += li;
+    den += d;
+  }
+  static __device__ __forceinline__ void fold_batch(double loss, double den, int n, int, float* out) {
+    out[0] = (float)(loss / (double)n);
+    out[1] = (float)den;
+  }
+};
+template <class Form>
+__device__ __forceinline__ const typename Form::word* ce_words(const CEGeom& g) { return static_cast<const typename Form::word*>(g.labels); }
+
+// One hi-res pixel from the staged rows (L0 / L1 hold the low-res columns from x0 on): its interpolated logits v[0..C) -- the expression of interp_logits --, their
+// maximum mx (ARGMAX: and its index) and the logit vl of class `lab`
+template <int C_, bool ARGMAX, typename Lab>
+__device__ __forceinline__ void ce_pixel_logits(const pm_lerp& ly, const pm_lerp& lx, const float* L0, const float* L1, int x0, int CP, int C, Lab lab, float* v, float& mx,
+                                                float& vl, int& arg) {
+  const float *p00 = L0 + (lx.i0 - x0) * CP, *p01 = L0 + (lx.i1 - x0) * CP, *p10 = L1 + (lx.i0 - x0) * CP, *p11 = L1 + (lx.i1 - x0) * CP;
+  mx = -INFINITY, vl = 0.f, arg = 0;
+#pragma unroll
+  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+    if (c < C) ce_class_step<ARGMAX>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
+}
+// ... and, in the field kernels after the form's term<.., CE_FIELD>, what its taps share: 1 / se and the pixel's weight on its left and right low-res column. Class c
+// then adds ce_grad_tap<Form::weighted>(v[c] * inv, Form::hot(q, v[c], c, lab), q.wl, wa, wb, A[c], B[c]); that class loop stays in the kernels: as a function of
+// its own the compiler lays the generic class count's loops out differently and packs the adds of the loss partial instead of fusing them (other bits).
+struct CETaps {
+  float inv, wa, wb;
+};
+__device__ __forceinline__ CETaps ce_taps(const CEPix& q, const pm_lerp& lx) {
+  const float inv = 1.f / q.se;
+  const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
+  return {inv, wa, wb};
+}
+
+// Flat forward (any shape), taps from global memory. Unweighted: one grid over the batch. Weighted forms: blockIdx.y = image (the final fold needs every image's
+// partials apart), the x blocks stride over that image's pixels. (loss sum, count or weight sum) per block.
+template <int C_, class Form>
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const CEGeom g, float* __restrict__ part) {
+  constexpr bool IMG = Form::weighted;
+  const int C = C_ > 0 ? C_ : g.C;
+  const long total = IMG ? (long)g.H * g.W : (long)g.n * g.H * g.W;
+  const typename Form::word* labels = ce_words<Form>(g) + (IMG ? (long)blockIdx.y * total : 0);
+  const float* wsm = nullptr;
+  if constexpr (Form::sets) {      // a weight per class of the set: the image's row, staged
+    __shared__ float wrow[MAXC];
+    ce_stage_weights(g, blockIdx.y, wrow);
+    __syncthreads();
+    wsm = wrow;
+  } else if constexpr (Form::weighted) {      // one weight per pixel: from global memory
+    wsm = g.wts + (long)blockIdx.y * g.wstride;
+  }
+  float lsum = 0.f, lcnt = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const auto lab = Form::ld(labels[i], C);
+    if (Form::template skip<C_, CE_FLAT>(lab, C)) continue;
+    const int X = (int)(i % g.W), Y = IMG ? (int)(i / g.W) : (int)((i / g.W) % g.H), b = IMG ? (int)blockIdx.y : (int)(i / ((long)g.W * g.H));
+    const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h), lx = pm_ac_lerp(g.sx, X, g.w);
+    float v[C_ > 0 ? C_ : MAXC];
+    interp_logits<C_>(g, b, ly, lx, v);
+    float mx = -INFINITY, vl = 0.f;
+    [[maybe_unused]] int arg = 0;
+#pragma unroll
+    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
+      if (c < C) ce_class_step<false>(v[c], c, Form::pick(lab), mx, vl, arg);
+    Form::template term<C_, CE_FLAT>(v, mx, vl, lab, wsm, C, true, lsum, lcnt);
+  }
+  __shared__ float sm[2][4];
+  if (ce_block_partial<4>(lsum, lcnt, sm)) {
+    const long pb = IMG ? (long)blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
+    part[pb * 2] = lsum, part[pb * 2 + 1] = lcnt;
+  }
+}
+
 // Row-staged forward: block = one hi-res row (Y, image b). The two low-res logit rows that row interpolates between are staged in LDS
 // once (coalesced, pre-scaled by 1/T); every hi-res pixel then gathers its 4 x C taps from LDS instead of issuing 4 x C scattered global
-// loads. The interpolation expression is the one of interp_logits / ce_bwd_rows_kernel, so the per-pixel logits carry the same bits.
-template <int C_, bool WT = false>
+// loads. The interpolation expression is the one of interp_logits, so the per-pixel logits carry the same bits.
+template <int C_, class Form>
 __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float* __restrict__ part) {
   extern __shared__ float L[];
   const int C = C_ > 0 ? C_ : g.C;
@@ -190,7 +336,7 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
   const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
   float* wsm = nullptr;
-  if constexpr (WT) {
+  if constexpr (Form::weighted) {
     __shared__ float wrow[MAXC];
     wsm = wrow;
     ce_stage_weights(g, b, wsm);
@@ -198,35 +344,20 @@ __global__ __launch_bounds__(256) void ce_fwd_rows_kernel(const CEGeom g, float*
   const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
   float* L0 = L;
   float* L1 = L + (size_t)g.w * CP;
-  const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
-  int64_t labs[3];
+  const typename Form::word* lrow = ce_words<Form>(g) + ((long)b * g.H + Y) * g.W;
+  typename Form::word labs[3];
 #pragma unroll
-  for (int u = 0; u < 3; ++u) labs[u] = (int)threadIdx.x + 256 * u < g.W ? lrow[threadIdx.x + 256 * u] : 255;   // in flight while the rows are staged
+  for (int u = 0; u < 3; ++u) labs[u] = Form::prefetch && (int)threadIdx.x + 256 * u < g.W ? lrow[threadIdx.x + 256 * u] : Form::none;   // in flight while the rows are staged
   ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, 256, L0, L1);
   __syncthreads();
   float lsum = 0.f, lcnt = 0.f;
   for (int X = threadIdx.x, u = 0; X < g.W; X += 256, ++u) {
-    const int64_t lab = u < 3 ? (u == 0 ? labs[0] : (u == 1 ? labs[1] : labs[2])) : lrow[X];
-    if (lab == 255) continue;
-    if constexpr (WT) {
-      if (lab < 0 || lab >= C) continue;
-    }
-    const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
-    const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-    float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, vl = 0.f;
-    [[maybe_unused]] int arg = 0;
-#pragma unroll
-    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
-    const float se = ce_exp_sum<C_, false>(v, mx, C);
-    if constexpr (WT) {
-      const float wl = wsm[lab];
-      lsum += wl * ((mx + logf(se)) - vl);
-      lcnt += wl;
-    } else {
-      lsum += (mx + logf(se)) - vl;
-      lcnt += 1.f;
-    }
+    const auto lab = Form::ld(Form::prefetch && u < 3 ? (u == 0 ? labs[0] : (u == 1 ? labs[1] : labs[2])) : lrow[X], C);
+    if (Form::template skip<C_, CE_ROWS>(lab, C)) continue;
+    float v[C_ > 0 ? C_ : MAXC], mx, vl;
+    [[maybe_unused]] int arg;
+    ce_pixel_logits<C_, false>(ly, pm_ac_lerp(g.sx, X, g.w), L0, L1, 0, CP, C, Form::pick(lab), v, mx, vl, arg);
+    Form::template term<C_, CE_ROWS>(v, mx, vl, lab, wsm, C, true, lsum, lcnt);
   }
   __shared__ float sm[2][4];
   if (ce_block_partial<4>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
@@ -259,24 +390,17 @@ __global__ __launch_bounds__(CE_FINAL_T) void ce_final_kernel(const float* __res
 }
 
 // Weighted forms: the block partials are image-major, `per` consecutive ones per image. One block folds image after image (the tree of ce_final_kernel per image, in
-// double): out[2 + b] = weight sum of image b; per_image: out[0] = sum over b, in index order, of (sum w nll)_b / (sum w)_b -- 0 / 0 = NaN for an image without a
-// weighted pixel, as nll_loss -- and out[1] = total weight sum. Without per_image, out[0] and out[1] are ce_final_kernel's (same order as the unweighted loss).
+// double); what an image's pair and the batch leave in out is the form's (fold_image / fold_batch).
+template <class Form>
 __global__ __launch_bounds__(CE_FINAL_T) void ce_final_img_kernel(const float* __restrict__ part, int per, int n, int per_image, float* __restrict__ out) {
   __shared__ double s[2][CE_FINAL_T];
   double loss = 0.0, den = 0.0;
   for (int b = 0; b < n; ++b) {
     ce_fold_pairs(part, (long)b * per, per, s);
-    if (threadIdx.x == 0) {
-      out[2 + b] = (float)s[1][0];
-      loss += s[0][0] / s[1][0];
-      den += s[1][0];
-    }
+    if (threadIdx.x == 0) Form::fold_image(s[0][0], s[1][0], b, n, out, loss, den);
     __syncthreads();      // s is rewritten for the next image
   }
-  if (threadIdx.x == 0 && per_image) {
-    out[0] = (float)loss;
-    out[1] = (float)den;
-  }
+  if (threadIdx.x == 0) Form::fold_batch(loss, den, n, per_image, out);
 }
 
 // pass 2: thread per (low-res pixel, class): supporting hi-res rows in ascending order, then the loss scale (WT, per_image: the image's own weight sum divides)
@@ -326,7 +450,7 @@ __device__ __forceinline__ int ce_first_ge(float sx, int k, int w, int W) {   //
   return X;
 }
 
-template <int C_, int PARTS, bool WITH_T, bool WT = false>
+template <int C_, int PARTS, class Form>
 __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, float* __restrict__ part, float* __restrict__ T) {
   extern __shared__ float L[];
   __shared__ float carry[MAXC];   // B of the last column of a round, owed to the first column of the next (rows wider than one round only)
@@ -336,7 +460,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
   const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
   const int Y = bid % g.H, b = bid / g.H;
   float* wsm = nullptr;
-  if constexpr (WT) {
+  if constexpr (Form::weighted) {
     __shared__ float wrow[MAXC];
     wsm = wrow;
     ce_stage_weights(g, b, wsm);
@@ -344,9 +468,9 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
   const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
   float* L0 = L;
   float* L1 = L + (size_t)g.w * CP;                                   // (+ C floats of slack behind it: bufB holds one column more than a round)
-  unsigned char* lab8 = reinterpret_cast<unsigned char*>(L1 + (size_t)g.w * CP + C);
-  const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
-  for (int X = tid; X < g.W; X += nt) lab8[X] = ce_label_byte(lrow[X]);
+  typename Form::staged* labs = reinterpret_cast<typename Form::staged*>(L1 + (size_t)g.w * CP + C);
+  const typename Form::word* lrow = ce_words<Form>(g) + ((long)b * g.H + Y) * g.W;
+  for (int X = tid; X < g.W; X += nt) labs[X] = Form::stage(lrow[X], C);
   auto stage_rows = [&]() { ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1); };
   stage_rows();
   __syncthreads();
@@ -371,64 +495,42 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
       const int per = (j1 - j0 + PARTS - 1) / PARTS;
       const int ja = j0 + p * per, jb = min(j1, ja + per);
       for (int X = ja; X < jb; ++X) {
-        const int lab = lab8[X];
-        if (lab == 255) continue;
-        if constexpr (WT && C_ > 0) {
-          if (lab >= C) continue;      // only labels of a class carry a weight
-        }
+        const typename Form::held lab = labs[X];
+        if (Form::template skip<C_, CE_FIELD>(lab, C)) continue;
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
-        const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-        float v[CR], mx = -INFINITY, vl = 0.f;
-        [[maybe_unused]] int arg = 0;
+        float v[CR], mx, vl;
+        [[maybe_unused]] int arg;
+        ce_pixel_logits<C_, false>(ly, lx, L0, L1, 0, CP, C, Form::pick(lab), v, mx, vl, arg);
+        const CEPix q = Form::template term<C_, CE_FIELD>(v, mx, vl, lab, wsm, C, true, lsum, lcnt);
+        const CETaps t = ce_taps(q, lx);
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
-        const float se = ce_exp_sum<C_, true>(v, mx, C);
-        float wl = 1.f;
-        if constexpr (WT) {
-          // generic class count: a label that is no class weighs 0 by a select, not by the branch above -- the branch tells the compiler that C > 0, it then
-          // lays out the class loop differently and contracts the interpolation of class 0 into another fma than the unweighted kernel does (1 ulp)
-          wl = C_ > 0 || lab < C ? wsm[min(lab, MAXC - 1)] : 0.f;
-          lsum += wl * ((mx + logf(se)) - vl);
-          lcnt += wl;
-        } else {
-          lsum += (mx + logf(se)) - vl;
-          lcnt += 1.f;
-        }
-        if constexpr (WITH_T) {
-          const float inv = 1.f / se;
-          const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
-#pragma unroll
-          for (int c = 0; c < CR; ++c)
-            if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab ? 1.f : 0.f, wl, wa, wb, A[c], B[c]);
-        }
+          if (c < C) ce_grad_tap<Form::weighted>(v[c] * t.inv, Form::hot(q, v[c], c, lab), q.wl, t.wa, t.wb, A[c], B[c]);
       }
     }
-    if constexpr (WITH_T) {
-      if constexpr (PARTS > 1) {
+    if constexpr (PARTS > 1) {
 #pragma unroll
-        for (int o = 1; o < PARTS; o <<= 1)
-#pragma unroll
-          for (int c = 0; c < CR; ++c)
-            if (c < C) A[c] += __shfl_xor(A[c], o, 64), B[c] += __shfl_xor(B[c], o, 64);
-      }
-      __syncthreads();                            // every lane is done with the staged rows: they become the exchange buffers
-      float* bufA = L0;                           // A of column x         -> bufA[x - xr0]
-      float* bufB = L1;                           // B of column x (owed to column x + 1) -> bufB[x - xr0 + 1]; bufB[0] = carry of the previous round
-      if (live && p == 0) {
+      for (int o = 1; o < PARTS; o <<= 1)
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) {
-            bufA[(x - xr0) * C + c] = A[c];
-            bufB[(x - xr0 + 1) * C + c] = B[c];
-          }
-      }
-      if (tid < C) bufB[tid] = rd == 0 ? 0.f : carry[tid];
-      __syncthreads();
-      float* Trow = T + (((long)b * g.H + Y) * g.w + xr0) * C;
-      for (int i = tid; i < (xr1 - xr0) * C; i += nt) Trow[i] = bufB[i] + bufA[i];
-      if (tid < C) carry[tid] = bufB[(xr1 - xr0) * C + tid];
+          if (c < C) A[c] += __shfl_xor(A[c], o, 64), B[c] += __shfl_xor(B[c], o, 64);
     }
+    __syncthreads();                            // every lane is done with the staged rows: they become the exchange buffers
+    float* bufA = L0;                           // A of column x         -> bufA[x - xr0]
+    float* bufB = L1;                           // B of column x (owed to column x + 1) -> bufB[x - xr0 + 1]; bufB[0] = carry of the previous round
+    if (live && p == 0) {
+#pragma unroll
+      for (int c = 0; c < CR; ++c)
+        if (c < C) {
+          bufA[(x - xr0) * C + c] = A[c];
+          bufB[(x - xr0 + 1) * C + c] = B[c];
+        }
+    }
+    if (tid < C) bufB[tid] = rd == 0 ? 0.f : carry[tid];
+    __syncthreads();
+    float* Trow = T + (((long)b * g.H + Y) * g.w + xr0) * C;
+    for (int i = tid; i < (xr1 - xr0) * C; i += nt) Trow[i] = bufB[i] + bufA[i];
+    if (tid < C) carry[tid] = bufB[(xr1 - xr0) * C + tid];
   }
   __shared__ float sm[2][4];
   if (ce_block_partial<0>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
@@ -446,7 +548,7 @@ __global__ __launch_bounds__(256) void ce_fused_rows_kernel(const CEGeom g, floa
 //     for all rounds put the 1 024-thread block 27 registers over its 128-register budget and the spills into the pixel loop: 190 instead of 120 us), loss
 //     partials per block: all fixed-order, deterministic.
 __host__ __device__ __forceinline__ int ce2_rows_per_interval(int h, int H) { return (H + h - 1) / h + 1; }
-template <int C_, bool WT = false>
+template <int C_, class Form>      // hard-label forms only
 __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, float* __restrict__ part, float* __restrict__ FA, float* __restrict__ FB, int tpr, int rg, int nseg, int ws) {
   extern __shared__ float L[];
   __shared__ float sm2[2][16];
@@ -464,7 +566,7 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
   const int seg = bid % nseg, y = (bid / nseg) % g.h, b = bid / (nseg * g.h);
   const int y1 = min(y + 1, g.h - 1);
   float* wsm = nullptr;
-  if constexpr (WT) {
+  if constexpr (Form::weighted) {
     __shared__ float wrow[MAXC];
     wsm = wrow;
     ce_stage_weights(g, b, wsm);
@@ -495,8 +597,8 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
     const bool rowlive = Y < Yb;
     unsigned char* mylab = lab8 + (size_t)gi * Wp;
     if (rowlive) {
-      const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
-      for (int X = Xlo + x; X < Xhi; X += tpr) mylab[X - Xlo] = ce_label_byte(lrow[X]);
+      const typename Form::word* lrow = ce_words<Form>(g) + ((long)b * g.H + Y) * g.W;
+      for (int X = Xlo + x; X < Xhi; X += tpr) mylab[X - Xlo] = Form::stage(lrow[X], C);
     }
     __syncthreads();                                 // labels (and, in the first round, the logit rows) are staged
     float A[CR], B[CR];
@@ -505,31 +607,17 @@ __global__ __launch_bounds__(1024) void ce_fused_rows2_kernel(const CEGeom g, fl
     pm_lerp ly = pm_ac_lerp(g.sy, rowlive ? Y : Ya, g.h);
     if (rowlive && colive) {
       for (int X = j0; X < j1; ++X) {
-        const int lab = mylab[X - Xlo];
-        if (lab == 255) continue;
-        if constexpr (WT) {
-          if (lab >= C) continue;
-        }
+        const typename Form::held lab = mylab[X - Xlo];
+        if (Form::template skip<C_, CE_FIELD>(lab, C)) continue;
         const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
-        const float *p00 = L0 + (lx.i0 - cb) * CP, *p01 = L0 + (lx.i1 - cb) * CP, *p10 = L1 + (lx.i0 - cb) * CP, *p11 = L1 + (lx.i1 - cb) * CP;
-        float v[CR], mx = -INFINITY, vl = 0.f;
-        [[maybe_unused]] int arg = 0;
+        float v[CR], mx, vl;
+        [[maybe_unused]] int arg;
+        ce_pixel_logits<C_, false>(ly, lx, L0, L1, cb, CP, C, Form::pick(lab), v, mx, vl, arg);
+        const CEPix q = Form::template term<C_, CE_FIELD>(v, mx, vl, lab, wsm, C, own, lsum, lcnt);      // own: the left-neighbour lane's pixels are counted by their segment
+        const CETaps t = ce_taps(q, lx);
 #pragma unroll
         for (int c = 0; c < CR; ++c)
-          if (c < C) ce_class_step<false>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
-        const float se = ce_exp_sum<C_, true>(v, mx, C);
-        float wl = 1.f;
-        if constexpr (WT) {
-          wl = wsm[lab];
-          if (own) lsum += wl * ((mx + logf(se)) - vl), lcnt += wl;
-        } else {
-          if (own) lsum += (mx + logf(se)) - vl, lcnt += 1.f;      // the left-neighbour lane's pixels are counted by the segment that owns them
-        }
-        const float inv = 1.f / se;
-        const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
-#pragma unroll
-        for (int c = 0; c < CR; ++c)
-          if (c < C) ce_grad_tap<WT>(v[c] * inv, c == lab ? 1.f : 0.f, wl, wa, wb, A[c], B[c]);
+          if (c < C) ce_grad_tap<Form::weighted>(v[c] * t.inv, Form::hot(q, v[c], c, lab), q.wl, t.wa, t.wb, A[c], B[c]);
       }
     }
     if (lane == 63) {
@@ -607,24 +695,39 @@ inline Rows2Plan rows2_plan(const CEGeom& g) {
   return p;
 }
 
-template <bool WT = false>
+template <class Form>
 inline void rows2_launch(const CEGeom& g, const Rows2Plan& r, float* part, float* field, hipStream_t st) {
   static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs the opt-in, once per device
-  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19, WT>), (int)ROWS2_MAX_LDS);
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows2_kernel<19, Form>), (int)ROWS2_MAX_LDS);
   const long half = (long)g.n * g.h * g.w * g.C;
-  hipLaunchKernelGGL((ce_fused_rows2_kernel<19, WT>), dim3(g.n * g.h * r.nseg), dim3(r.tpr * r.rg), r.lds, st, g, part, field, field + half, r.tpr, r.rg, r.nseg, r.ws);
+  hipLaunchKernelGGL((ce_fused_rows2_kernel<19, Form>), dim3(g.n * g.h * r.nseg), dim3(r.tpr * r.rg), r.lds, st, g, part, field, field + half, r.tpr, r.rg, r.nseg, r.ws);
 }
 
 inline int fwd_blocks(long total) { return (int)std::min<long>((total + 255) / 256, 4096); }
-inline int wfwd_blocks(long hw) { return (int)std::min<long>((hw + 255) / 256, 512); }      // x blocks per image of the flat weighted forward
+inline int wfwd_blocks(long hw) { return (int)std::min<long>((hw + 255) / 256, 512); }      // x blocks per image of the flat forward of the weighted forms
 
-int fill(CEGeom& g, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const char* who) {
-  PM_REQUIRE(logits && logits->ptr && labels && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
-  PM_REQUIRE(logits->c >= 1 && logits->c <= MAXC, PM_EUNSUPPORTED, "%s: classes %d > %d", who, logits->c, MAXC);
+enum CEForm { CE_HARD, CE_WEIGHTED, CE_SETS };      // the run-time names of HardForm<false>, HardForm<true>, SetForm
+// one pair of block partials per block of any forward or field kernel of the form
+inline size_t ce_workspace(CEForm form, int n, int H, int W) {
+  const long flat = form == CE_HARD ? fwd_blocks((long)n * H * W) : (long)n * wfwd_blocks((long)H * W);
+  const long rows = (long)n * H * (form == CE_SETS ? 1 : 2);      // hard labels: the interval form has <= 2 n H blocks (rows2_plan)
+  return pm_align_up((size_t)std::max<long>(flat, rows) * 2 * sizeof(float), 256);
+}
+
+// The geometry of a call of any form (the relaxed entry points hand their flat logit arguments over as a pm_tensor of their own); each form keeps its checks.
+int fill(CEGeom& g, const char* who, CEForm form, const pm_tensor* logits, float inv_temp, const void* labels, int H, int W) {
+  if (form == CE_SETS) {
+    PM_REQUIRE(logits->ptr && logits->n > 0 && logits->h > 0 && logits->w > 0 && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
+    PM_REQUIRE(logits->c >= 1 && logits->c <= RX_MAXC, PM_EUNSUPPORTED, "%s: classes %d not in 1..%d", who, logits->c, RX_MAXC);
+    PM_REQUIRE(logits->pitch >= logits->c, PM_EINVAL, "%s: pitch %lld < %d classes", who, (long long)logits->pitch, logits->c);
+  } else {
+    PM_REQUIRE(logits && logits->ptr && labels && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
+    PM_REQUIRE(logits->c >= 1 && logits->c <= MAXC, PM_EUNSUPPORTED, "%s: classes %d > %d", who, logits->c, MAXC);
+  }
   g.logits = (const float*)logits->ptr, g.lp = logits->pitch, g.n = logits->n, g.h = logits->h, g.w = logits->w, g.C = logits->c;
   g.labels = labels, g.H = H, g.W = W;
   g.sy = pm_ac_scale(logits->h, H), g.sx = pm_ac_scale(logits->w, W), g.inv_temp = inv_temp;
-  g.wts = nullptr, g.wstride = 0, g.per_image = 0;
+  g.wts = nullptr, g.wstride = 0, g.per_image = form == CE_SETS;      // sets: the row pass divides every image by its own divisor
   return PM_OK;
 }
 
@@ -642,141 +745,146 @@ int fill_w(CEGeom& g, const CEWeights& wt, const char* who) {
   return PM_OK;
 }
 
-// f(class count as a constant: 19 or 0 = generic, weighted as a constant): the one place where the run-time (C == 19, weighted) pair picks a kernel instantiation
+// f(class count as a constant: 19 or 0 = generic, the form as an object): the one place where the run-time (C == 19, form) pair picks a kernel instantiation
 template <class F>
-inline void ce_dispatch(int C, bool weighted, F&& f) {
-  using C19 = std::integral_constant<int, 19>;
-  using C0 = std::integral_constant<int, 0>;
-  if (C == 19) weighted ? f(C19{}, std::true_type{}) : f(C19{}, std::false_type{});
-  else weighted ? f(C0{}, std::true_type{}) : f(C0{}, std::false_type{});
-}
-
-// Final reduce of n x per block partials (image-major when weighted). Unweighted, or weighted over the batch: loss and divisor in the order of ce_final_kernel; the
-// weighted forms then add the per-image weight sums (and, per_image, the sum of the images' own means).
-inline void ce_finish(const float* part, int per, int n, const CEWeights* wt, float* loss_out, hipStream_t st) {
-  if (!wt || !wt->per_image) hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, n * per, loss_out);
-  if (wt) hipLaunchKernelGGL(ce_final_img_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, part, per, n, wt->per_image, loss_out);
+inline void ce_dispatch(int C, CEForm form, F&& f) {
+  auto with = [&](auto cc) {
+    if (form == CE_HARD) f(cc, HardForm<false>{});
+    else if (form == CE_WEIGHTED) f(cc, HardForm<true>{});
+    else f(cc, SetForm{});
+  };
+  if (C == 19) with(std::integral_constant<int, 19>{});
+  else with(std::integral_constant<int, 0>{});
 }
 
 struct FusedPlan {
   int parts, threads;
   size_t lds;
 };
-inline FusedPlan fused_plan(const CEGeom& g) {
+inline FusedPlan fused_plan(const CEGeom& g, size_t label_bytes) {      // label_bytes: of a staged label, sizeof(Form::staged)
   FusedPlan p;
   // ~4 hi-res pixels per lane: PARTS lanes share a low-res column when the up-sampling ratio is large (the read loss: 768 / 48 = 16)
   const int ratio = std::max(1, g.W / std::max(1, g.w));
   p.parts = 1;
   while (p.parts < 16 && p.parts * 8 <= ratio && g.w * p.parts * 2 <= 256) p.parts *= 2;
   p.threads = std::min(256, std::max(64, (g.w * p.parts + 63) / 64 * 64));
-  p.lds = ((size_t)2 * g.w * (g.C | 1) + g.C) * sizeof(float) + (size_t)(g.W + 15) / 16 * 16;
+  p.lds = ((size_t)2 * g.w * (g.C | 1) + g.C) * sizeof(float) + label_bytes * ((size_t)(g.W + 15) / 16 * 16);
   return p;
 }
-constexpr size_t FUSED_MAX_LDS = 159 * 1024;   // dynamic part; the kernel also declares 160 B of static LDS
-template <int CC, int PP, bool WT>
+constexpr size_t FUSED_MAX_LDS = 159 * 1024;   // dynamic part; the kernel also declares up to 288 B of static LDS
+inline size_t ce_label_bytes(CEForm form) { return form == CE_SETS ? sizeof(SetForm::staged) : sizeof(HardForm<false>::staged); }
+template <int CC, int PP, class Form>
 void fused_launch_one(const CEGeom& g, const FusedPlan& p, float* part, float* T, hipStream_t st) {
   // > 64 KB of dynamic LDS (logit rows wider than ~420 pixels x 19 classes) needs an explicit opt-in, once per kernel AND device
   static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, true, WT>), (int)FUSED_MAX_LDS);
-  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, true, WT>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
+  (void)optin(reinterpret_cast<const void*>(&ce_fused_rows_kernel<CC, PP, Form>), (int)FUSED_MAX_LDS);
+  hipLaunchKernelGGL((ce_fused_rows_kernel<CC, PP, Form>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, part, T);
 }
-int fused_launch(const CEGeom& g, const FusedPlan& p, bool weighted, float* part, float* T, hipStream_t st) {
-  ce_dispatch(g.C, weighted, [&](auto cc, auto wt) {
+
+// ---- the one host route: every forward and field entry point ends here --------------------------------------------------------------------------------------------
+// Chooses the kernel -- field: interval form (hard labels) or PARTS form; forward: row-staged or flat --, launches it with block partials into `part` and, given a
+// loss_out, folds them. `who` is the entry point's name (it leads every message); the caller has filled g and checked its own arguments.
+enum CERoute { CE_INTERVAL, CE_PARTS, CE_ROW_STAGED, CE_FLAT_GRID };
+int ce_run(const char* who, const CEGeom& g, CEForm form, bool want_field, float* loss_out, float* field, float* part, hipStream_t st) {
+  Rows2Plan r{};
+  FusedPlan p{};
+  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);     // the two staged low-res rows
+  CERoute route;
+  if (want_field) route = form != CE_SETS && (r = rows2_plan(g)).ok ? CE_INTERVAL : CE_PARTS;
+  else route = row_lds <= 48 * 1024 && (long)g.n * g.H <= (1 << 20) && g.W >= 32 ? CE_ROW_STAGED : CE_FLAT_GRID;      // row-staged: one block per hi-res row
+  // image-major grids (blockIdx.y = image): the flat forward of the weighted forms; the relaxed entry points refuse such a batch on every route
+  PM_REQUIRE(g.n <= 65535 || form == CE_HARD || (form == CE_WEIGHTED && route != CE_FLAT_GRID), PM_EUNSUPPORTED, "%s: %d images > 65535", who, g.n);
+  if (route == CE_PARTS) {
+    p = fused_plan(g, ce_label_bytes(form));
+    PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * g.H <= (1l << 30), PM_EUNSUPPORTED, "%s: logit rows of %d x %d classes do not fit LDS", who, g.w, g.C);
+  }
+  int per = g.H, n = g.n;      // block partials per image, images
+  ce_dispatch(g.C, form, [&](auto cc, auto fm) {
     constexpr int CC = decltype(cc)::value;
-    constexpr bool WT = decltype(wt)::value;
-    switch (p.parts) {
-      case 1: fused_launch_one<CC, 1, WT>(g, p, part, T, st); break;
-      case 2: fused_launch_one<CC, 2, WT>(g, p, part, T, st); break;
-      case 4: fused_launch_one<CC, 4, WT>(g, p, part, T, st); break;
-      case 8: fused_launch_one<CC, 8, WT>(g, p, part, T, st); break;
-      default: fused_launch_one<CC, 16, WT>(g, p, part, T, st); break;
+    using Form = decltype(fm);
+    switch (route) {
+      case CE_INTERVAL:
+        per = g.h * r.nseg;
+        if constexpr (CC == 19 && !Form::sets) rows2_launch<Form>(g, r, part, field, st);
+        break;
+      case CE_PARTS:
+        switch (p.parts) {
+          case 1: fused_launch_one<CC, 1, Form>(g, p, part, field, st); break;
+          case 2: fused_launch_one<CC, 2, Form>(g, p, part, field, st); break;
+          case 4: fused_launch_one<CC, 4, Form>(g, p, part, field, st); break;
+          case 8: fused_launch_one<CC, 8, Form>(g, p, part, field, st); break;
+          default: fused_launch_one<CC, 16, Form>(g, p, part, field, st); break;
+        }
+        break;
+      case CE_ROW_STAGED: hipLaunchKernelGGL((ce_fwd_rows_kernel<CC, Form>), dim3(g.n * g.H), dim3(256), row_lds, st, g, part); break;
+      case CE_FLAT_GRID:
+        if (Form::weighted) {      // image-major grid: the final fold needs every image's partials apart
+          per = wfwd_blocks((long)g.H * g.W);
+          hipLaunchKernelGGL((ce_fwd_kernel<CC, Form>), dim3(per, g.n), dim3(256), 0, st, g, part);
+        } else {                   // one grid over the batch
+          per = fwd_blocks((long)g.n * g.H * g.W), n = 1;
+          hipLaunchKernelGGL((ce_fwd_kernel<CC, Form>), dim3(per), dim3(256), 0, st, g, part);
+        }
+        break;
     }
   });
-  return pm_check_launch("upsample_ce_fused");
-}
-
-// ---- one function per operation; `who` is the entry point's name (it leads every message), wt its weights or null -----------------------------------------------
-int ce_fwd(const char* who, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const CEWeights* wt, float* loss_out, void* ws,
-           size_t ws_bytes, hipStream_t st) {
-  PM_REQUIRE_F32(logits, who);
-  CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, who)) return e;
-  if (wt)
-    if (int e = fill_w(g, *wt, who)) return e;
-  PM_REQUIRE(loss_out && ws && ws_bytes >= (wt ? pm_upsample_wce_workspace(g.n, H, W) : pm_upsample_ce_workspace(g.n, H, W)), PM_EWORKSPACE, "%s: workspace too small", who);
-  int per, n = g.n;      // block partials per image, images
-  const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float);     // the two staged low-res rows
-  if (row_lds <= 48 * 1024 && (long)g.n * H <= (1 << 20) && W >= 32) {     // row-staged kernel: one block per hi-res row
-    per = H;
-    ce_dispatch(g.C, wt != nullptr, [&](auto cc, auto w) {
-      hipLaunchKernelGGL((ce_fwd_rows_kernel<decltype(cc)::value, decltype(w)::value>), dim3(g.n * H), dim3(256), row_lds, st, g, (float*)ws);
-    });
-  } else if (wt) {      // flat kernel, image-major grid: the final reduce needs every image's partials apart
-    PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "%s: %d images > 65535", who, g.n);
-    per = wfwd_blocks((long)H * W);
-    ce_dispatch(g.C, true, [&](auto cc, auto) { hipLaunchKernelGGL((ce_fwd_kernel<decltype(cc)::value, true>), dim3(per, g.n), dim3(256), 0, st, g, (float*)ws); });
-  } else {              // flat kernel, one grid over the batch
-    per = fwd_blocks((long)g.n * H * W), n = 1;
-    ce_dispatch(g.C, false, [&](auto cc, auto) { hipLaunchKernelGGL((ce_fwd_kernel<decltype(cc)::value, false>), dim3(per), dim3(256), 0, st, g, (float*)ws); });
+  // Final fold of n x per block partials (image-major for the weighted forms). Hard labels, unweighted or weighted over the batch: loss and divisor in the order of
+  // ce_final_kernel; the weighted forms then add what they keep per image (and, per_image, the sum of the images' own means).
+  if (loss_out) {
+    if (form == CE_HARD || (form == CE_WEIGHTED && !g.per_image)) hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, n * per, loss_out);
+    if (form == CE_WEIGHTED) hipLaunchKernelGGL(ce_final_img_kernel<HardForm<true>>, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, per, n, g.per_image, loss_out);
+    if (form == CE_SETS) hipLaunchKernelGGL(ce_final_img_kernel<SetForm>, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, per, n, 1, loss_out);
   }
-  ce_finish((const float*)ws, per, n, wt, loss_out, st);
   return pm_check_launch(who);
 }
 
-int ce_fwd_field(const char* who, const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const CEWeights* wt, float* loss_out, float* field,
-                 void* ws, size_t ws_bytes, hipStream_t st) {
+// Every forward and training-forward entry point: its argument checks, then the route. wt: the weights, or null (CE_HARD).
+int ce_fwd(const char* who, CEForm form, const pm_tensor* logits, float inv_temp, const void* labels, int H, int W, const CEWeights* wt, bool want_field, float* loss_out,
+           float* field, void* ws, size_t ws_bytes, hipStream_t st) {
   PM_REQUIRE_F32(logits, who);
   CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, who)) return e;
+  if (int e = fill(g, who, form, logits, inv_temp, labels, H, W)) return e;
+  PM_REQUIRE(labels, PM_EINVAL, "%s: null bits", who);      // (null int64 labels: refused by fill)
   if (wt)
     if (int e = fill_w(g, *wt, who)) return e;
-  PM_REQUIRE(loss_out && field && ws && ws_bytes >= (wt ? pm_upsample_wce_workspace(g.n, H, W) : pm_upsample_ce_workspace(g.n, H, W)), PM_EWORKSPACE,
-             "%s: workspace too small / null field", who);
-  if (const Rows2Plan r = rows2_plan(g); r.ok) {
-    wt ? rows2_launch<true>(g, r, (float*)ws, field, st) : rows2_launch<false>(g, r, (float*)ws, field, st);
-    ce_finish((const float*)ws, g.h * r.nseg, g.n, wt, loss_out, st);
-    return pm_check_launch(who);
-  }
-  const FusedPlan p = fused_plan(g);
-  PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * H <= (1l << 30), PM_EUNSUPPORTED, "%s: logit rows of %d x %d classes do not fit LDS", who, g.w, g.C);
-  if (int e = fused_launch(g, p, wt != nullptr, (float*)ws, field, st)) return e;
-  ce_finish((const float*)ws, H, g.n, wt, loss_out, st);
-  return pm_check_launch(who);
+  PM_REQUIRE(loss_out && (field || !want_field) && ws && ws_bytes >= ce_workspace(form, g.n, H, W), PM_EWORKSPACE,
+             want_field || form == CE_SETS ? "%s: workspace too small / null field" : "%s: workspace too small", who);
+  return ce_run(who, g, form, want_field, loss_out, field, (float*)ws, st);
 }
 
-// wt: only per_image is read (the row pass reads neither labels, logits nor weights)
+// The row pass over a field (the backward proper): reads neither labels, logits nor weights. loss_out: where the divisors sit ([1]; per image from [2] on).
+void ce_row_pass(const CEGeom& g, CEForm form, const float* field, const float* loss_out, const float* gscale, float* dl, long dlp, hipStream_t st) {
+  const long total = (long)g.n * g.h * g.w * g.C;
+  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
+  const bool rows2 = form != CE_SETS && rows2_plan(g).ok;
+  ce_dispatch(0, form, [&](auto, auto fm) {
+    constexpr bool WT = decltype(fm)::weighted;
+    if (rows2) hipLaunchKernelGGL(ce_bwd_rows2_kernel<WT>, grid, dim3(256), 0, st, g, field, field + total, loss_out, gscale, dl, dlp);
+    else hipLaunchKernelGGL(ce_bwd_cols_kernel<WT>, grid, dim3(256), 0, st, g, field, loss_out, gscale, dl, dlp);
+  });
+}
+
+// wt: only per_image is read
 int ce_bwd_field(const char* who, const pm_tensor* logits, float inv_temp, int H, int W, const CEWeights* wt, const float* loss_out, const float* gscale,
                  const float* field, const pm_tensor* dlogits, hipStream_t st) {
   PM_REQUIRE_F32(logits, who);
   PM_REQUIRE_F32(dlogits, who);
   CEGeom g;
   static const int64_t dummy = 0;
-  if (int e = fill(g, logits, inv_temp, &dummy, H, W, who)) return e;
+  if (int e = fill(g, who, wt ? CE_WEIGHTED : CE_HARD, logits, inv_temp, &dummy, H, W)) return e;
   if (wt) {
     PM_REQUIRE(wt->per_image == 0 || wt->per_image == 1, PM_EINVAL, "%s: per_image %d is neither 0 nor 1", who, wt->per_image);
   }
   PM_REQUIRE(loss_out && field && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "%s: bad args", who);
   if (wt) g.per_image = wt->per_image;
-  const long total = (long)g.n * g.h * g.w * g.C;
-  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
-  float* dl = (float*)dlogits->ptr;
-  const bool rows2 = rows2_plan(g).ok;
-  ce_dispatch(0, wt != nullptr, [&](auto, auto w) {
-    constexpr bool WT = decltype(w)::value;
-    if (rows2) hipLaunchKernelGGL(ce_bwd_rows2_kernel<WT>, grid, dim3(256), 0, st, g, field, field + total, loss_out, gscale, dl, (long)dlogits->pitch);
-    else hipLaunchKernelGGL(ce_bwd_cols_kernel<WT>, grid, dim3(256), 0, st, g, field, loss_out, gscale, dl, (long)dlogits->pitch);
-  });
+  ce_row_pass(g, wt ? CE_WEIGHTED : CE_HARD, field, loss_out, gscale, (float*)dlogits->ptr, (long)dlogits->pitch, st);
   return pm_check_launch(who);
 }
 
 }  // namespace
 
-extern "C" size_t pm_upsample_ce_workspace(int n, int H, int W) {   // one (sum, count) pair per block of either forward kernel
-  return pm_align_up((size_t)std::max<long>(fwd_blocks((long)n * H * W), (long)n * H * 2) * 2 * sizeof(float), 256);      // interval form: <= 2 n H blocks (rows2_plan)
-}
-extern "C" size_t pm_upsample_wce_workspace(int n, int H, int W) {      // one (sum w nll, sum w) pair per block of any weighted forward kernel
-  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H * 2) * 2 * sizeof(float), 256);
-}
+extern "C" size_t pm_upsample_ce_workspace(int n, int H, int W) { return ce_workspace(CE_HARD, n, H, W); }
+extern "C" size_t pm_upsample_wce_workspace(int n, int H, int W) { return ce_workspace(CE_WEIGHTED, n, H, W); }
 extern "C" size_t pm_upsample_wce_loss_floats(int n) { return (size_t)2 + (size_t)std::max(n, 0); }
 
 extern "C" size_t pm_upsample_ce_field_bytes(const pm_tensor* logits, int H, int W) {
@@ -786,31 +894,31 @@ extern "C" size_t pm_upsample_ce_field_bytes(const pm_tensor* logits, int H, int
   CEGeom g{};
   g.n = logits->n, g.h = logits->h, g.w = logits->w, g.H = H, g.W = W, g.C = logits->c;
   if (rows2_plan(g).ok) return (size_t)2 * logits->n * logits->h * logits->w * logits->c * sizeof(float);      // interval form: FA | FB
-  if (fused_plan(g).lds > FUSED_MAX_LDS) return 0;
+  if (fused_plan(g, ce_label_bytes(CE_HARD)).lds > FUSED_MAX_LDS) return 0;
   return (size_t)logits->n * H * logits->w * logits->c * sizeof(float);
 }
 
-// The unweighted and the weighted entry points (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180): same kernels (WT), same routing
+// The unweighted and the weighted entry points (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180): same kernels, same routing
 // between them, same field layout. Weighted block partials are (sum w nll, sum w), image-major.
 extern "C" int pm_upsample_ce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, void* ws, size_t ws_bytes,
                                   void* stream) {
-  return ce_fwd("upsample_ce_fwd", logits, inv_temp, labels, H, W, nullptr, loss_out, ws, ws_bytes, (hipStream_t)stream);
+  return ce_fwd("upsample_ce_fwd", CE_HARD, logits, inv_temp, labels, H, W, nullptr, false, loss_out, nullptr, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int pm_upsample_wce_fwd(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
                                    int per_image, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
   const CEWeights wt{weights, weight_stride, per_image};
-  return ce_fwd("upsample_wce_fwd", logits, inv_temp, labels, H, W, &wt, loss_out, ws, ws_bytes, (hipStream_t)stream);
+  return ce_fwd("upsample_wce_fwd", CE_WEIGHTED, logits, inv_temp, labels, H, W, &wt, false, loss_out, nullptr, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // Training forward (the logits carry a graph): the loss and the field the row pass needs, in one sweep over the labels.
 extern "C" int pm_upsample_ce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, float* loss_out, float* field,
                                         void* ws, size_t ws_bytes, void* stream) {
-  return ce_fwd_field("upsample_ce_fwd_field", logits, inv_temp, labels, H, W, nullptr, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
+  return ce_fwd("upsample_ce_fwd_field", CE_HARD, logits, inv_temp, labels, H, W, nullptr, true, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int pm_upsample_wce_fwd_field(const pm_tensor* logits, float inv_temp, const int64_t* labels, int H, int W, const float* weights, int64_t weight_stride,
                                          int per_image, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
   const CEWeights wt{weights, weight_stride, per_image};
-  return ce_fwd_field("upsample_wce_fwd_field", logits, inv_temp, labels, H, W, &wt, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
+  return ce_fwd("upsample_wce_fwd_field", CE_WEIGHTED, logits, inv_temp, labels, H, W, &wt, true, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pm_upsample_ce_bwd_field(const pm_tensor* logits, float inv_temp, int H, int W, const float* loss_out, const float* gscale, const float* field,
@@ -835,19 +943,12 @@ extern "C" int pm_upsample_ce_bwd(const pm_tensor* logits, float inv_temp, const
   PM_REQUIRE_F32(logits, "upsample_ce_bwd");
   PM_REQUIRE_F32(dlogits, "upsample_ce_bwd");
   CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_ce_bwd")) return e;
+  if (int e = fill(g, "upsample_ce_bwd", CE_HARD, logits, inv_temp, labels, H, W)) return e;
   PM_REQUIRE(loss_out && dlogits && dlogits->ptr && pm_same_shape(logits, dlogits), PM_EINVAL, "upsample_ce_bwd: bad args");
   PM_REQUIRE(ws && ws_bytes >= pm_upsample_ce_bwd_workspace(logits, H, W), PM_EWORKSPACE, "upsample_ce_bwd: workspace too small");
   float* field = (float*)ws;
   float* part = (float*)((char*)ws + pm_align_up(pm_upsample_ce_field_bytes(logits, H, W), 256));
-  if (const Rows2Plan r = rows2_plan(g); r.ok) {
-    rows2_launch<false>(g, r, part, field, (hipStream_t)stream);
-    if (int e = pm_check_launch("upsample_ce_bwd")) return e;
-  } else {
-    const FusedPlan p = fused_plan(g);
-    PM_REQUIRE(p.lds <= FUSED_MAX_LDS, PM_EUNSUPPORTED, "upsample_ce_bwd: logit rows of %d x %d classes do not fit LDS", g.w, g.C);
-    if (int e = fused_launch(g, p, false, part, field, (hipStream_t)stream)) return e;
-  }
+  if (int e = ce_run("upsample_ce_bwd", g, CE_HARD, true, nullptr, field, part, (hipStream_t)stream)) return e;      // no loss_out: the partials are not folded
   return pm_upsample_ce_bwd_field(logits, inv_temp, H, W, loss_out, gscale, field, dlogits, stream);
 }
 
@@ -906,7 +1007,7 @@ __global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int r
   int s0 = -1, s1 = -1;      // the low-res rows in L0, L1
   for (int Y = Y0; Y < Y1; ++Y) {
     const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
-    const int64_t* lrow = g.labels + ((long)b * g.H + Y) * g.W;
+    const int64_t* lrow = ce_words<HardForm<false>>(g) + ((long)b * g.H + Y) * g.W;
     int64_t labs[3];
 #pragma unroll
     for (int u = 0; u < 3; ++u) labs[u] = (int)threadIdx.x + 256 * u < g.W ? lrow[threadIdx.x + 256 * u] : 255;   // in flight while the rows are staged
@@ -926,17 +1027,12 @@ __global__ __launch_bounds__(256) void ce_eval_rows_kernel(const CEGeom g, int r
     for (int X = threadIdx.x, u = 0; X < g.W; X += 256, ++u) {
       const int64_t lab = u < 3 ? (u == 0 ? labs[0] : (u == 1 ? labs[1] : labs[2])) : lrow[X];
       if (lab == 255 && !prow) continue;
-      const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
-      const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-      float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, vl = 0.f;
-      int arg = 0;
-#pragma unroll
-      for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-        if (c < C) ce_class_step<true>(v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]), c, lab, mx, vl, arg);
+      float v[C_ > 0 ? C_ : MAXC], mx, vl;
+      int arg;
+      ce_pixel_logits<C_, true>(ly, pm_ac_lerp(g.sx, X, g.w), L0, L1, 0, CP, C, lab, v, mx, vl, arg);
       if (prow) prow[X] = (uint8_t)arg;           // every pixel, ignored ones included
       if (lab == 255) continue;
-      lsum += (mx + logf(ce_exp_sum<C_, false>(v, mx, C))) - vl;
-      lcnt += 1.f;
+      HardForm<false>::term<C_, CE_ROWS>(v, mx, vl, lab, nullptr, C, true, lsum, lcnt);
       if (lab >= 0 && lab < C) atomicAdd(&cnt[(int)lab * C + arg], 1u);      // fast_hist's mask (utils/misc.py:65-70)
     }
     ce_wave_partials(lsum, lcnt, sm[Y - Y0]);
@@ -968,7 +1064,7 @@ extern "C" int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const i
                                 uint8_t* pred, void* ws, size_t ws_bytes, void* stream) {
   PM_REQUIRE_F32(logits, "upsample_eval");
   CEGeom g;
-  if (int e = fill(g, logits, inv_temp, labels, H, W, "upsample_eval")) return e;
+  if (int e = fill(g, "upsample_eval", CE_HARD, logits, inv_temp, labels, H, W)) return e;
   PM_REQUIRE(loss_out && hist, PM_EINVAL, "upsample_eval: null loss_out / hist");
   PM_REQUIRE(accumulate == 0 || accumulate == 1, PM_EINVAL, "upsample_eval: accumulate %d is neither 0 nor 1", accumulate);
   const EvalPlan p = eval_plan(g.n, g.h, g.w, g.C, H, W);
@@ -977,7 +1073,7 @@ extern "C" int pm_upsample_eval(const pm_tensor* logits, float inv_temp, const i
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
   unsigned* counts = (unsigned*)((char*)ws + p.part_bytes);
-  ce_dispatch(g.C, false, [&](auto cc, auto) { eval_launch<decltype(cc)::value>(g, p, part, counts, pred, st); });
+  ce_dispatch(g.C, CE_HARD, [&](auto cc, auto) { eval_launch<decltype(cc)::value>(g, p, part, counts, pred, st); });
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)part, g.n * H, loss_out);
   hipLaunchKernelGGL(pm_hist_fold_kernel, dim3((g.C * g.C + 31) / 32), dim3(PM_HIST_FOLD_T), 0, st, (const unsigned*)counts, g.n * p.chunks, g.C * g.C, accumulate, hist);
   return pm_check_launch("upsample_eval");
@@ -1059,10 +1155,9 @@ extern "C" int pm_label_class_weights(const int64_t* labels, int n, int H, int W
 // With S the real classes of the set, k = |S|, p = softmax(z) and P_S = sum of p over S, the reference's max(p_c, P_S) is P_S for every c in S, so the pixel's term is
 //   - W_S log P_S,  W_S = (sum of w_c over S) / k,        gradient  W_S (p_j - [j in S] p_j / P_S);
 // k = 0 ignores the pixel. Image i: sum of terms / (valid_i + 1); batch: sum over images / n. Classes outside S contribute exactly nothing (the reference multiplies
-// 0 by log p_c there: NaN once p_c underflows). The interpolation is ce_lerp, the row staging ce_stage_rows, the exponentials ce_exp_sum, the field scheme the one of
-// ce_fused_rows_kernel (lane group = low-res column, A / B sums, exchange through LDS, fixed order everywhere) and the row pass ce_bwd_cols_kernel itself.
+// 0 by log p_c there: NaN once p_c underflows). The kernels are the CE ones with Form = SetForm (rx_term is the pixel's term; the set words are staged in LDS, four
+// bytes a pixel, in the place of the label bytes): flat and row-staged forward, the PARTS field kernel, the per-image final fold and the row pass ce_bwd_cols_kernel.
 namespace {
-constexpr int RX_MAXC = 31;            // bit C is the ignore class
 constexpr int RX_MAX_BORDER = 3;
 constexpr int RX_COLS = 1024;          // label columns per block of the border kernel
 
@@ -1133,256 +1228,8 @@ __global__ __launch_bounds__(256) void rx_count_kernel(const uint32_t* __restric
   if (threadIdx.x < MAXC) counts[((long)blockIdx.y * gridDim.x + blockIdx.x) * MAXC + threadIdx.x] = cnt[threadIdx.x];
 }
 
-// One pixel whose set holds the real classes S (not empty), v[0..C) its logits and mx their maximum: v becomes exp(v - mx), se their sum, ps the sum over S, wbar the
-// mean weight over S; returns the pixel's loss term - wbar log P_S.
-template <int C_>
-__device__ __forceinline__ float rx_term(float* v, float mx, unsigned S, const float* wsm, int C, float& se, float& ps, float& wbar) {
-  se = ce_exp_sum<C_, true>(v, mx, C);
-  float ws = 0.f;
-  ps = 0.f;
-#pragma unroll
-  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-    if (c < C && ((S >> c) & 1u)) ps += v[c], ws += wsm[c];
-  wbar = ws / (float)__popc(S);
-  return wbar * (logf(se) - logf(ps));
-}
-// The pixel's logits from the staged rows into v (the expression of interp_logits), returning their maximum
-template <int C_>
-__device__ __forceinline__ float rx_lerp_rows(const pm_lerp& ly, const pm_lerp& lx, const float* L0, const float* L1, int CP, int C, float* v) {
-  const float *p00 = L0 + lx.i0 * CP, *p01 = L0 + lx.i1 * CP, *p10 = L1 + lx.i0 * CP, *p11 = L1 + lx.i1 * CP;
-  float mx = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-    if (c < C) mx = fmaxf(mx, v[c] = ce_lerp(ly, lx, p00[c], p01[c], p10[c], p11[c]));
-  return mx;
-}
-
-// Flat forward (any shape): blockIdx.y = image, the x blocks stride over its pixels, taps from global memory; (sum of terms, valid pixels) per block.
-template <int C_>
-__global__ __launch_bounds__(256) void rx_fwd_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part) {
-  __shared__ float wsm[MAXC];
-  __shared__ float sm[2][4];
-  const int C = C_ > 0 ? C_ : g.C;
-  const int b = blockIdx.y;
-  const long total = (long)g.H * g.W;
-  const uint32_t* src = bits + (long)b * total;
-  const unsigned real = (1u << C) - 1u;
-  ce_stage_weights(g, b, wsm);
-  __syncthreads();
-  float lsum = 0.f, lcnt = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const unsigned S = src[i] & real;
-    if (!S) continue;
-    const int X = (int)(i % g.W), Y = (int)(i / g.W);
-    const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h), lx = pm_ac_lerp(g.sx, X, g.w);
-    float v[C_ > 0 ? C_ : MAXC], mx = -INFINITY, se, ps, wbar;
-    interp_logits<C_>(g, b, ly, lx, v);
-#pragma unroll
-    for (int c = 0; c < (C_ > 0 ? C_ : MAXC); ++c)
-      if (c < C) mx = fmaxf(mx, v[c]);
-    lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
-    lcnt += 1.f;
-  }
-  if (ce_block_partial<4>(lsum, lcnt, sm)) {
-    const long pb = (long)b * gridDim.x + blockIdx.x;
-    part[pb * 2] = lsum, part[pb * 2 + 1] = lcnt;
-  }
-}
-
-// Row-staged forward, the shape of ce_fwd_rows_kernel: block = one hi-res row, its two low-res logit rows in LDS, lane = hi-res pixel.
-template <int C_>
-__global__ __launch_bounds__(256) void rx_fwd_rows_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part) {
-  extern __shared__ float L[];
-  __shared__ float wsm[MAXC];
-  __shared__ float sm[2][4];
-  const int C = C_ > 0 ? C_ : g.C;
-  const int CP = C | 1;
-  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
-  const int Y = bid % g.H, b = bid / g.H;
-  const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
-  float* L0 = L;
-  float* L1 = L + (size_t)g.w * CP;
-  const uint32_t* brow = bits + ((long)b * g.H + Y) * g.W;
-  const unsigned real = (1u << C) - 1u;
-  ce_stage_weights(g, b, wsm);
-  ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, 256, L0, L1);
-  __syncthreads();
-  float lsum = 0.f, lcnt = 0.f;
-  for (int X = threadIdx.x; X < g.W; X += 256) {
-    const unsigned S = brow[X] & real;
-    if (!S) continue;
-    float v[C_ > 0 ? C_ : MAXC], se, ps, wbar;
-    const float mx = rx_lerp_rows<C_>(ly, pm_ac_lerp(g.sx, X, g.w), L0, L1, CP, C, v);
-    lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
-    lcnt += 1.f;
-  }
-  if (ce_block_partial<4>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
-}
-
-// Training forward: the loss and the column-reduced field T[b][Y][x][c] in one sweep -- ce_fused_rows_kernel with the set words (staged in LDS, four bytes a pixel)
-// in the place of the label bytes and W_S (p - [c in S] p / P_S) in the place of w (softmax - onehot).
-template <int C_, int PARTS>
-__global__ __launch_bounds__(256) void rx_fused_rows_kernel(const CEGeom g, const uint32_t* __restrict__ bits, float* __restrict__ part, float* __restrict__ T) {
-  extern __shared__ float L[];
-  __shared__ float carry[MAXC];
-  __shared__ float wsm[MAXC];
-  __shared__ float sm[2][4];
-  constexpr int CR = C_ > 0 ? C_ : MAXC;
-  const int C = C_ > 0 ? C_ : g.C;
-  const int CP = C | 1;
-  const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
-  const int bid = pm_xcd_remap(blockIdx.x, gridDim.x);
-  const int Y = bid % g.H, b = bid / g.H;
-  const pm_lerp ly = pm_ac_lerp(g.sy, Y, g.h);
-  float* L0 = L;
-  float* L1 = L + (size_t)g.w * CP;                                   // (+ C floats of slack behind it: bufB holds one column more than a round)
-  uint32_t* set = reinterpret_cast<uint32_t*>(L1 + (size_t)g.w * CP + C);
-  const uint32_t* brow = bits + ((long)b * g.H + Y) * g.W;
-  const unsigned real = (1u << C) - 1u;
-  ce_stage_weights(g, b, wsm);
-  for (int X = tid; X < g.W; X += nt) set[X] = brow[X] & real;
-  ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1);
-  __syncthreads();
-  float lsum = 0.f, lcnt = 0.f;
-  const int R = nt / PARTS;                       // low-res columns per round
-  const int rounds = (g.w + R - 1) / R;
-  for (int rd = 0; rd < rounds; ++rd) {
-    if (rd > 0) {                                 // the previous round recycled the staged rows as its exchange buffers
-      __syncthreads();
-      ce_stage_rows(g, C, CP, b, ly.i0, ly.i1, 0, g.w, nt, L0, L1);
-      __syncthreads();
-    }
-    const int xr0 = rd * R, xr1 = min(g.w, xr0 + R);
-    const int x = xr0 + tid / PARTS, p = tid % PARTS;
-    const bool live = x < xr1;
-    float A[CR], B[CR];
-#pragma unroll
-    for (int c = 0; c < CR; ++c) A[c] = B[c] = 0.f;
-    if (live) {
-      const int j0 = ce_first_ge(g.sx, x, g.w, g.W), j1 = ce_first_ge(g.sx, x + 1, g.w, g.W);
-      const int per = (j1 - j0 + PARTS - 1) / PARTS;
-      const int ja = j0 + p * per, jb = min(j1, ja + per);
-      for (int X = ja; X < jb; ++X) {
-        const unsigned S = set[X];
-        if (!S) continue;
-        const pm_lerp lx = pm_ac_lerp(g.sx, X, g.w);
-        float v[CR], se, ps, wbar;
-        const float mx = rx_lerp_rows<C_>(ly, lx, L0, L1, CP, C, v);
-        lsum += rx_term<C_>(v, mx, S, wsm, C, se, ps, wbar);
-        lcnt += 1.f;
-        const float inv = 1.f / se, invs = 1.f / ps;
-        const float wa = lx.i1 == lx.i0 ? lx.w0 + lx.w1 : lx.w0, wb = lx.i1 == lx.i0 ? 0.f : lx.w1;
-#pragma unroll
-        for (int c = 0; c < CR; ++c)
-          if (c < C) ce_grad_tap<true>(v[c] * inv, (S >> c) & 1u ? v[c] * invs : 0.f, wbar, wa, wb, A[c], B[c]);
-      }
-    }
-    if constexpr (PARTS > 1) {
-#pragma unroll
-      for (int o = 1; o < PARTS; o <<= 1)
-#pragma unroll
-        for (int c = 0; c < CR; ++c)
-          if (c < C) A[c] += __shfl_xor(A[c], o, 64), B[c] += __shfl_xor(B[c], o, 64);
-    }
-    __syncthreads();                            // every lane is done with the staged rows: they become the exchange buffers
-    float* bufA = L0;                           // A of column x         -> bufA[x - xr0]
-    float* bufB = L1;                           // B of column x (owed to column x + 1) -> bufB[x - xr0 + 1]; bufB[0] = carry of the previous round
-    if (live && p == 0) {
-#pragma unroll
-      for (int c = 0; c < CR; ++c)
-        if (c < C) {
-          bufA[(x - xr0) * C + c] = A[c];
-          bufB[(x - xr0 + 1) * C + c] = B[c];
-        }
-    }
-    if (tid < C) bufB[tid] = rd == 0 ? 0.f : carry[tid];
-    __syncthreads();
-    float* Trow = T + (((long)b * g.H + Y) * g.w + xr0) * C;
-    for (int i = tid; i < (xr1 - xr0) * C; i += nt) Trow[i] = bufB[i] + bufA[i];
-    if (tid < C) carry[tid] = bufB[(xr1 - xr0) * C + tid];
-  }
-  if (ce_block_partial<0>(lsum, lcnt, sm)) part[bid * 2] = lsum, part[bid * 2 + 1] = lcnt;
-}
-
-// n x per (sum of terms, valid pixels) partials, image-major -> out[0] = sum_i loss_i / n, out[1] = valid pixels of the batch, out[2 + i] = loss_i =
-// terms_i / (valid_i + 1), out[2 + n + i] = (valid_i + 1) n: what the row pass divides image i by. One block, the tree of ce_final_kernel per image, in double.
-__global__ __launch_bounds__(CE_FINAL_T) void rx_final_kernel(const float* __restrict__ part, int per, int n, float* __restrict__ out) {
-  __shared__ double s[2][CE_FINAL_T];
-  double loss = 0.0, valid = 0.0;
-  for (int b = 0; b < n; ++b) {
-    ce_fold_pairs(part, (long)b * per, per, s);
-    if (threadIdx.x == 0) {
-      const double li = s[0][0] / (s[1][0] + 1.0);
-      out[2 + b] = (float)li;
-      out[2 + n + b] = (float)((s[1][0] + 1.0) * (double)n);
-      loss += li;
-      valid += s[1][0];
-    }
-    __syncthreads();      // s is rewritten for the next image
-  }
-  if (threadIdx.x == 0) {
-    out[0] = (float)(loss / (double)n);
-    out[1] = (float)valid;
-  }
-}
-
-// the field kernel's plan: fused_plan with four bytes per staged label instead of one
-inline FusedPlan rx_plan(const CEGeom& g) {
-  FusedPlan p = fused_plan(g);
-  p.lds += (size_t)3 * ((size_t)(g.W + 15) / 16 * 16);
-  return p;
-}
-
-int rx_fill(CEGeom& g, const char* who, const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, int H, int W) {
-  PM_REQUIRE(logits && n > 0 && h > 0 && w > 0 && H > 0 && W > 0, PM_EINVAL, "%s: null/empty", who);
-  PM_REQUIRE(C >= 1 && C <= RX_MAXC, PM_EUNSUPPORTED, "%s: classes %d not in 1..%d", who, C, RX_MAXC);
-  PM_REQUIRE(pitch >= C, PM_EINVAL, "%s: pitch %lld < %d classes", who, (long long)pitch, C);
-  g.logits = logits, g.lp = (long)pitch, g.n = n, g.h = h, g.w = w, g.C = C;
-  g.labels = nullptr, g.H = H, g.W = W;
-  g.sy = pm_ac_scale(h, H), g.sx = pm_ac_scale(w, W), g.inv_temp = inv_temp;
-  g.wts = nullptr, g.wstride = 0, g.per_image = 1;
-  return PM_OK;
-}
-
-int rx_fwd(const char* who, CEGeom& g, const uint32_t* bits, const float* weights, int64_t weight_stride, float* loss_out, float* field, bool want_field, void* ws,
-           size_t ws_bytes, hipStream_t st) {
-  const CEWeights wt{weights, weight_stride, 1};
-  PM_REQUIRE(bits, PM_EINVAL, "%s: null bits", who);
-  if (int e = fill_w(g, wt, who)) return e;
-  PM_REQUIRE(loss_out && ws && ws_bytes >= pm_upsample_relax_workspace(g.n, g.H, g.W) && (field || !want_field), PM_EWORKSPACE, "%s: workspace too small / null field", who);
-  PM_REQUIRE(g.n <= 65535, PM_EUNSUPPORTED, "%s: %d images > 65535", who, g.n);
-  int per;
-  if (want_field) {
-    const FusedPlan p = rx_plan(g);
-    PM_REQUIRE(p.lds <= FUSED_MAX_LDS && (long)g.n * g.H <= (1l << 30), PM_EUNSUPPORTED, "%s: logit rows of %d x %d classes do not fit LDS", who, g.w, g.C);
-    per = g.H;
-    auto launch = [&](auto cc, auto pp) {
-      constexpr int CC = decltype(cc)::value, PP = decltype(pp)::value;
-      static pm_lds_optin optin;      // > 64 KB of dynamic LDS needs the opt-in, once per kernel and device
-      (void)optin(reinterpret_cast<const void*>(&rx_fused_rows_kernel<CC, PP>), (int)FUSED_MAX_LDS);
-      hipLaunchKernelGGL((rx_fused_rows_kernel<CC, PP>), dim3(g.n * g.H), dim3(p.threads), p.lds, st, g, bits, (float*)ws, field);
-    };
-    ce_dispatch(g.C, false, [&](auto cc, auto) {
-      switch (p.parts) {
-        case 1: launch(cc, std::integral_constant<int, 1>{}); break;
-        case 2: launch(cc, std::integral_constant<int, 2>{}); break;
-        case 4: launch(cc, std::integral_constant<int, 4>{}); break;
-        case 8: launch(cc, std::integral_constant<int, 8>{}); break;
-        default: launch(cc, std::integral_constant<int, 16>{}); break;
-      }
-    });
-  } else if (const size_t row_lds = 2 * (size_t)g.w * (g.C | 1) * sizeof(float); row_lds <= 48 * 1024 && (long)g.n * g.H <= (1 << 20) && g.W >= 32) {
-    per = g.H;
-    ce_dispatch(g.C, false, [&](auto cc, auto) {
-      hipLaunchKernelGGL((rx_fwd_rows_kernel<decltype(cc)::value>), dim3(g.n * g.H), dim3(256), row_lds, st, g, bits, (float*)ws);
-    });
-  } else {
-    per = wfwd_blocks((long)g.H * g.W);
-    ce_dispatch(g.C, false, [&](auto cc, auto) { hipLaunchKernelGGL((rx_fwd_kernel<decltype(cc)::value>), dim3(per, g.n), dim3(256), 0, st, g, bits, (float*)ws); });
-  }
-  hipLaunchKernelGGL(rx_final_kernel, dim3(1), dim3(CE_FINAL_T), 0, st, (const float*)ws, per, g.n, loss_out);
-  return pm_check_launch(who);
-}
+// The relaxed entry points take their logits as flat arguments: the same view as a pm_tensor
+inline pm_tensor rx_view(const float* p, int n, int h, int w, int C, int64_t pitch) { return pm_tensor{const_cast<float*>(p), n, h, w, C, pitch, PM_F32, 0}; }
 }  // namespace
 
 extern "C" int pm_relax_border_bits(const int64_t* labels, int n, int H, int W, int classes, int border, uint32_t strict_mask, uint32_t* bits, void* stream) {
@@ -1420,40 +1267,37 @@ extern "C" int pm_relax_class_weights(const uint32_t* bits, int n, int H, int W,
   return pm_check_launch("relax_class_weights");
 }
 
-extern "C" size_t pm_upsample_relax_workspace(int n, int H, int W) {      // one (sum of terms, valid pixels) pair per block of any relaxed forward kernel
-  return pm_align_up((size_t)std::max<long>((long)n * wfwd_blocks((long)H * W), (long)n * H) * 2 * sizeof(float), 256);
-}
+extern "C" size_t pm_upsample_relax_workspace(int n, int H, int W) { return ce_workspace(CE_SETS, n, H, W); }
 extern "C" size_t pm_upsample_relax_loss_floats(int n) { return (size_t)2 + (size_t)2 * std::max(n, 0); }
 extern "C" size_t pm_upsample_relax_field_bytes(int n, int h, int w, int C, int H, int W) {
   if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1 || C < 1 || C > RX_MAXC) return 0;
   CEGeom g{};
   g.n = n, g.h = h, g.w = w, g.H = H, g.W = W, g.C = C;
-  if (rx_plan(g).lds > FUSED_MAX_LDS || (long)n * H > (1l << 30)) return 0;
+  if (fused_plan(g, ce_label_bytes(CE_SETS)).lds > FUSED_MAX_LDS || (long)n * H > (1l << 30)) return 0;
   return (size_t)n * H * w * C * sizeof(float);
 }
 
 extern "C" int pm_upsample_relax_fwd(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W,
                                      const float* weights, int64_t weight_stride, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
-  CEGeom g;
-  if (int e = rx_fill(g, "upsample_relax_fwd", logits, n, h, w, C, pitch, inv_temp, H, W)) return e;
-  return rx_fwd("upsample_relax_fwd", g, bits, weights, weight_stride, loss_out, nullptr, false, ws, ws_bytes, (hipStream_t)stream);
+  const pm_tensor lg = rx_view(logits, n, h, w, C, pitch);
+  const CEWeights wt{weights, weight_stride, 1};
+  return ce_fwd("upsample_relax_fwd", CE_SETS, &lg, inv_temp, bits, H, W, &wt, false, loss_out, nullptr, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int pm_upsample_relax_fwd_field(const float* logits, int n, int h, int w, int C, int64_t pitch, float inv_temp, const uint32_t* bits, int H, int W,
                                            const float* weights, int64_t weight_stride, float* loss_out, float* field, void* ws, size_t ws_bytes, void* stream) {
-  CEGeom g;
-  if (int e = rx_fill(g, "upsample_relax_fwd_field", logits, n, h, w, C, pitch, inv_temp, H, W)) return e;
-  return rx_fwd("upsample_relax_fwd_field", g, bits, weights, weight_stride, loss_out, field, true, ws, ws_bytes, (hipStream_t)stream);
+  const pm_tensor lg = rx_view(logits, n, h, w, C, pitch);
+  const CEWeights wt{weights, weight_stride, 1};
+  return ce_fwd("upsample_relax_fwd_field", CE_SETS, &lg, inv_temp, bits, H, W, &wt, true, loss_out, field, ws, ws_bytes, (hipStream_t)stream);
 }
 // The row pass of ce_bwd_cols_kernel, every image divided by its own out[2 + n + i] (its weighted form reads the divisor of image i at [2 + i] of what it is given).
 extern "C" int pm_upsample_relax_bwd_field(int n, int h, int w, int C, float inv_temp, int H, int W, const float* loss_out, const float* gscale, const float* field,
                                            float* dlogits, int64_t dpitch, void* stream) {
   CEGeom g;
   PM_REQUIRE(dlogits, PM_EINVAL, "upsample_relax_bwd_field: null dlogits");
-  if (int e = rx_fill(g, "upsample_relax_bwd_field", dlogits, n, h, w, C, dpitch, inv_temp, H, W)) return e;
+  const pm_tensor dl = rx_view(dlogits, n, h, w, C, dpitch);
+  if (int e = fill(g, "upsample_relax_bwd_field", CE_SETS, &dl, inv_temp, nullptr, H, W)) return e;
   PM_REQUIRE(loss_out && field, PM_EINVAL, "upsample_relax_bwd_field: null loss_out / field");
   PM_REQUIRE(pm_upsample_relax_field_bytes(n, h, w, C, H, W) != 0, PM_EUNSUPPORTED, "upsample_relax_bwd_field: no field for this shape");
-  const long total = (long)n * h * w * C;
-  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
-  hipLaunchKernelGGL(ce_bwd_cols_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, field, loss_out + n, gscale, dlogits, (long)dpitch);
+  ce_row_pass(g, CE_SETS, field, loss_out + n, gscale, dlogits, (long)dpitch, (hipStream_t)stream);
   return pm_check_launch("upsample_relax_bwd_field");
 }

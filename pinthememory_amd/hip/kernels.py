@@ -1066,9 +1066,23 @@ def label_nearest(lab, size):
     return out
 
 
-# ---- fused upsample + cross entropy, plain and weighted (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180) ---------------
-# One private function per operation; `w` is None or (weights, per_image) and picks the pm_upsample_ce_* or the pm_upsample_wce_* entry point. The weighted forms
-# differ in three arguments, in the size of loss_out (2 + n floats: include/pinmem_hip.h) and in the workspace formula.
+# ---- fused upsample + loss: cross entropy plain and weighted (CrossEntropyLoss(weight) / ImageBasedCrossEntropyLoss2d, loss.py:20-43,71-88,120-180) and relaxed ----
+# One private function per operation over the label forms of csrc/loss.hip. A form: the stem of its entry points, whether the logits travel as a descriptor or as
+# flat arguments, the floats of loss_out for n images, and its workspace query. The weighted forms pass (weights, stride) and, 'wce' alone, per_image.
+def _flat(t):
+    """NHWC fp32 tensor whose pixels are `pitch` floats apart -> the flat arguments (ptr, n, h, w, C, pitch) of the pm_upsample_relax_* entry points"""
+    assert t.dtype == torch.float32, 'the relaxed-border loss takes fp32 logits'
+    d = tdesc(t)
+    return d.ptr, d.n, d.h, d.w, d.c, d.pitch
+
+
+_FORMS = {
+    'ce': dict(logits=lambda lg: (byref(tdesc(lg)),), loss_floats=lambda lib, n: 2, workspace='pm_upsample_ce_workspace'),
+    'wce': dict(logits=lambda lg: (byref(tdesc(lg)),), loss_floats=lambda lib, n: lib.pm_upsample_wce_loss_floats(n), workspace='pm_upsample_wce_workspace'),
+    'relax': dict(logits=_flat, loss_floats=lambda lib, n: lib.pm_upsample_relax_loss_floats(n), workspace='pm_upsample_relax_workspace'),
+}
+
+
 def _wce_weights(weights, logits):
     """[C] (one row for the batch: stride 0) or [n, C] float32 weights -> (tensor kept alive, row stride)."""
     n, C = logits.shape[0], logits.shape[3]
@@ -1082,29 +1096,34 @@ def _wce_weights(weights, logits):
     return weights, (weights.stride(0) if n > 1 else C)
 
 
-def _ce_loss_out(n, device, w, out):
-    need = 2 if w is None else _lib().pm_upsample_wce_loss_floats(n)
-    if out is None:
-        return torch.empty(need, dtype=torch.float32, device=device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
-    return out
+def _field_floats(form, logits, H, W):
+    lib = _lib()
+    if form == 'relax':
+        return lib.pm_upsample_relax_field_bytes(*_flat(logits)[1:5], H, W) // 4
+    return lib.pm_upsample_ce_field_bytes(byref(tdesc(logits)), H, W) // 4
 
 
-def _ce_fwd(logits, labels, inv_temp, w, out, want_field):
-    """-> loss_out, or (loss_out, field) for the training forward."""
+def _loss_fwd(form, logits, labels, inv_temp, weights, per_image, out, want_field):
+    """-> loss_out, or (loss_out, field) for the training forward. labels: int64 labels, or ('relax') int32 set words."""
     n, H, W = labels.shape
-    out = _ce_loss_out(n, logits.device, w, out)
-    lib, ld = _lib(), tdesc(logits)
-    field = torch.empty(lib.pm_upsample_ce_field_bytes(byref(ld), H, W) // 4, dtype=torch.float32, device=logits.device) if want_field else None
-    nb = (lib.pm_upsample_ce_workspace if w is None else lib.pm_upsample_wce_workspace)(n, H, W)
+    F, lib = _FORMS[form], _lib()
+    if form == 'relax':
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and n == logits.shape[0]
+    need = F['loss_floats'](lib, n)
+    if out is None:
+        out = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
+    largs = F['logits'](logits)
+    field = torch.empty(_field_floats(form, logits, H, W), dtype=torch.float32, device=logits.device) if want_field else None
+    nb = getattr(lib, F['workspace'])(n, H, W)
     ws = workspace(nb, logits.device)
-    name = 'pm_upsample_%s_fwd%s' % ('ce' if w is None else 'wce', '_field' if want_field else '')
     wargs = ()
-    if w is not None:
-        wt, stride = _wce_weights(w[0], logits)
-        wargs = (wt.data_ptr(), stride, int(bool(w[1])))
+    if weights is not None:
+        wt, stride = _wce_weights(weights, logits)
+        wargs = (wt.data_ptr(), stride) + ((int(bool(per_image)),) if form == 'wce' else ())
+    name = 'pm_upsample_%s_fwd%s' % (form, '_field' if want_field else '')
     fargs = (field.data_ptr(),) if want_field else ()
-    check(getattr(lib, name)(byref(ld), inv_temp, labels.data_ptr(), H, W, *wargs, out.data_ptr(), *fargs, ptr(ws), nb, stream()), name)
+    check(getattr(lib, name)(*largs, inv_temp, labels.data_ptr(), H, W, *wargs, out.data_ptr(), *fargs, ptr(ws), nb, stream()), name)
     return (out, field) if want_field else out
 
 
@@ -1112,17 +1131,22 @@ def _ce_dlogits(logits):
     return new(tuple(logits.shape), logits, pitch_pad=(logits.stride(2) != logits.shape[3]))   # same pitch as the logits
 
 
-def _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp, per_image=None):
+def _loss_bwd_field(form, logits, label_hw, loss_out, field, gscale, inv_temp, per_image=None):
     H, W = label_hw
     dl = _ce_dlogits(logits)
-    name = 'pm_upsample_ce_bwd_field' if per_image is None else 'pm_upsample_wce_bwd_field'
-    wargs = () if per_image is None else (int(bool(per_image)),)
-    check(getattr(_lib(), name)(byref(tdesc(logits)), inv_temp, H, W, *wargs, loss_out.data_ptr(), ptr(gscale), field.data_ptr(), byref(tdesc(dl)), stream()), name)
+    name = 'pm_upsample_%s_bwd_field' % form
+    tail = (loss_out.data_ptr(), ptr(gscale), field.data_ptr())
+    if form == 'relax':      # flat arguments: the shape first, dlogits and its pitch last
+        dptr, n, h, w, C, dpitch = _flat(dl)
+        args = (n, h, w, C, inv_temp, H, W) + tail + (dptr, dpitch)
+    else:
+        args = (byref(tdesc(logits)), inv_temp, H, W) + ((int(bool(per_image)),) if form == 'wce' else ()) + tail + (byref(tdesc(dl)),)
+    check(getattr(_lib(), name)(*args, stream()), name)
     return dl
 
 
 def upsample_ce_fwd(logits, labels, inv_temp=1.0):
-    return _ce_fwd(logits, labels, inv_temp, None, None, False)
+    return _loss_fwd('ce', logits, labels, inv_temp, None, None, None, False)
 
 
 def upsample_ce_bwd(logits, labels, loss_out, gscale, inv_temp=1.0):
@@ -1144,25 +1168,25 @@ def upsample_ce_fused_ok(logits, label_hw):
 
 def upsample_ce_fwd_field(logits, labels, inv_temp=1.0):
     """Training forward: -> (loss_out[2], field). The field is what upsample_ce_bwd_field needs instead of a second sweep over labels and logits."""
-    return _ce_fwd(logits, labels, inv_temp, None, None, True)
+    return _loss_fwd('ce', logits, labels, inv_temp, None, None, None, True)
 
 
 def upsample_ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp=1.0):
-    return _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp)
+    return _loss_bwd_field('ce', logits, label_hw, loss_out, field, gscale, inv_temp)
 
 
 def upsample_wce_fwd(logits, labels, weights, per_image, inv_temp=1.0, out=None):
     """-> loss_out[2 + n]: [0] the loss, [1] the total weight sum, [2 + b] the weight sum of image b (include/pinmem_hip.h)."""
-    return _ce_fwd(logits, labels, inv_temp, (weights, per_image), out, False)
+    return _loss_fwd('wce', logits, labels, inv_temp, weights, per_image, out, False)
 
 
 def upsample_wce_fwd_field(logits, labels, weights, per_image, inv_temp=1.0, out=None):
     """Training forward: -> (loss_out[2 + n], field); the field has the layout and size of upsample_ce_fwd_field's."""
-    return _ce_fwd(logits, labels, inv_temp, (weights, per_image), out, True)
+    return _loss_fwd('wce', logits, labels, inv_temp, weights, per_image, out, True)
 
 
 def upsample_wce_bwd_field(logits, label_hw, loss_out, field, gscale, per_image, inv_temp=1.0):
-    return _ce_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp, per_image)
+    return _loss_bwd_field('wce', logits, label_hw, loss_out, field, gscale, inv_temp, per_image)
 
 
 def label_class_weights(labels, classes, upper_bound=1.0, norm=False, per_batch=False, out=None):
@@ -1223,13 +1247,6 @@ def relax_class_weights(bits, classes, upper_bound=1.0, norm=False, per_batch=Fa
     return out
 
 
-def _relax_logits(logits):
-    """NHWC fp32 logits whose pixels are `pitch` floats apart -> the flat arguments (ptr, n, h, w, C, pitch) of the pm_upsample_relax_* entry points"""
-    assert logits.dtype == torch.float32, 'the relaxed-border loss takes fp32 logits'
-    d = tdesc(logits)
-    return d.ptr, d.n, d.h, d.w, d.c, d.pitch
-
-
 def upsample_relax_ok(logits, label_hw):
     """Can the fused relaxed-loss field kernel take this shape (two low-res logit rows + one row of set words in LDS)?"""
     n, h, w, C = logits.shape
@@ -1238,42 +1255,18 @@ def upsample_relax_ok(logits, label_hw):
     return _sizes(('relax', logits.shape, tuple(label_hw)), lambda: _lib().pm_upsample_relax_field_bytes(n, h, w, C, label_hw[0], label_hw[1])) != 0
 
 
-def _relax_fwd(logits, bits, weights, inv_temp, out, want_field):
-    n, H, W = bits.shape
-    assert bits.dtype == torch.int32 and bits.is_contiguous() and bits.shape[0] == logits.shape[0]
-    lib = _lib()
-    need = lib.pm_upsample_relax_loss_floats(n)
-    if out is None:
-        out = torch.empty(need, dtype=torch.float32, device=logits.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= need
-    largs = _relax_logits(logits)
-    field = torch.empty(lib.pm_upsample_relax_field_bytes(*largs[1:5], H, W) // 4, dtype=torch.float32, device=logits.device) if want_field else None
-    nb = lib.pm_upsample_relax_workspace(n, H, W)
-    ws = workspace(nb, logits.device)
-    wt, stride = _wce_weights(weights, logits)
-    name = 'pm_upsample_relax_fwd' + ('_field' if want_field else '')
-    fargs = (field.data_ptr(),) if want_field else ()
-    check(getattr(lib, name)(*largs, inv_temp, bits.data_ptr(), H, W, wt.data_ptr(), stride, out.data_ptr(), *fargs, ptr(ws), nb, stream()), name)
-    return (out, field) if want_field else out
-
-
 def upsample_relax_fwd(logits, bits, weights, inv_temp=1.0, out=None):
     """-> loss_out[2 + 2n]: [0] the loss, [1] the valid pixels, [2 + i] the loss of image i, [2 + n + i] (valid_i + 1) n (include/pinmem_hip.h)."""
-    return _relax_fwd(logits, bits, weights, inv_temp, out, False)
+    return _loss_fwd('relax', logits, bits, inv_temp, weights, None, out, False)
 
 
 def upsample_relax_fwd_field(logits, bits, weights, inv_temp=1.0, out=None):
     """Training forward: -> (loss_out[2 + 2n], field)."""
-    return _relax_fwd(logits, bits, weights, inv_temp, out, True)
+    return _loss_fwd('relax', logits, bits, inv_temp, weights, None, out, True)
 
 
 def upsample_relax_bwd_field(logits, label_hw, loss_out, field, gscale, inv_temp=1.0):
-    H, W = label_hw
-    dl = _ce_dlogits(logits)
-    dptr, n, h, w, C, dpitch = _relax_logits(dl)
-    check(_lib().pm_upsample_relax_bwd_field(n, h, w, C, inv_temp, H, W, loss_out.data_ptr(), ptr(gscale), field.data_ptr(), dptr, dpitch, stream()),
-          'pm_upsample_relax_bwd_field')
-    return dl
+    return _loss_bwd_field('relax', logits, label_hw, loss_out, field, gscale, inv_temp)
 
 
 # ---- validation sweep: loss + argmax + confusion matrix of the up-sampled logits (train.py:847-939) -------------------------------

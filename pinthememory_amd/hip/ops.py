@@ -702,35 +702,29 @@ def fanout(x, n):
     return _Fanout.apply(x, n)
 
 
-class _UpsampleCE(torch.autograd.Function):
-    """mean CE(ignore 255) of bilinearly up-sampled logits vs full-resolution labels, logits never materialised. With a graph attached the
-    forward also leaves the column-reduced gradient field (K.upsample_ce_fwd_field), so the backward is one short row pass.
-    weights (None: the plain loss): w = weights[label] ([C]) or weights[image][label] ([n, C]); per_image: the sum over images of each image's weighted mean
-    (ImageBasedCrossEntropyLoss2d), else sum w nll / sum w over the batch (CrossEntropyLoss(weight)). The weights carry no gradient."""
+class _UpsampleLoss(torch.autograd.Function):
+    """A loss of bilinearly up-sampled logits against full-resolution labels, logits never materialised; `form` names the label form of csrc/loss.hip. With a graph
+    attached the forward also leaves the column-reduced gradient field (K.upsample_*_fwd_field), so the backward is one short row pass.
+    'ce': mean CE(ignore 255) against int64 labels. 'wce': the same with w = weights[label] ([C]) or weights[image][label] ([n, C]); per_image: the sum over images of
+    each image's weighted mean (ImageBasedCrossEntropyLoss2d), else sum w nll / sum w over the batch (CrossEntropyLoss(weight)). 'relax': the relaxed-border loss
+    (ImgWtLossSoftNLL, loss.py:182-263) against border-set words. The weights carry no gradient."""
 
     @staticmethod
-    def forward(ctx, logits, labels, inv_temp, want_grad, weights=None, per_image=False):
+    def forward(ctx, logits, labels, inv_temp, want_grad, form='ce', weights=None, per_image=None):
         lv = nhwc(logits)
         labels = labels.contiguous()
-        ctx.inv_temp, ctx.hw, ctx.per_image = inv_temp, tuple(labels.shape[1:]), (None if weights is None else per_image)
+        ctx.form, ctx.inv_temp, ctx.hw, ctx.per_image = form, inv_temp, tuple(labels.shape[1:]), per_image
         if not want_grad:
-            return (K.upsample_ce_fwd(lv, labels, inv_temp) if weights is None else K.upsample_wce_fwd(lv, labels, weights, per_image, inv_temp))[0]
-        if weights is None:
-            out, field = K.upsample_ce_fwd_field(lv, labels, inv_temp)
-        else:
-            out, field = K.upsample_wce_fwd_field(lv, labels, weights, per_image, inv_temp)
+            return K._loss_fwd(form, lv, labels, inv_temp, weights, per_image, None, False)[0]
+        out, field = K._loss_fwd(form, lv, labels, inv_temp, weights, per_image, None, True)
         ctx.save_for_backward(lv, out, field)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        gs = g.reshape(1).float().contiguous()
         lv, out, field = ctx.saved_tensors
-        if ctx.per_image is None:
-            dl = K.upsample_ce_bwd_field(lv, ctx.hw, out, field, gs, ctx.inv_temp)
-        else:
-            dl = K.upsample_wce_bwd_field(lv, ctx.hw, out, field, gs, ctx.per_image, ctx.inv_temp)
-        return nchw(dl), None, None, None, None, None
+        dl = K._loss_bwd_field(ctx.form, lv, ctx.hw, out, field, g.reshape(1).float().contiguous(), ctx.inv_temp, ctx.per_image)
+        return nchw(dl), None, None, None, None, None, None
 
 
 class _MemRead(torch.autograd.Function):
@@ -887,7 +881,7 @@ def upsample_ce(logits, labels, inv_temp=1.0):
         # bilinear kernel and torch's cross entropy on the materialised logits -- correct for any size, not tuned
         full = resize(logits, tuple(labels.shape[1:]))
         return torch.nn.functional.cross_entropy(full * float(inv_temp), labels, ignore_index=255, reduction='mean')
-    return _UpsampleCE.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
+    return _UpsampleLoss.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
 
 
 def weighted_ce(full, labels, weights, per_image):
@@ -911,28 +905,7 @@ def upsample_wce(logits, labels, weights, per_image, inv_temp=1.0):
     per_image = bool(per_image)
     if not K.upsample_ce_fused_ok(nhwc(logits), tuple(labels.shape[1:])):      # as upsample_ce: rows too wide for the fused kernels' LDS
         return weighted_ce(resize(logits, tuple(labels.shape[1:])) * float(inv_temp), labels, weights, per_image)
-    return _UpsampleCE.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad), weights.detach(), per_image)
-
-
-class _UpsampleRelax(torch.autograd.Function):
-    """The relaxed-border loss (ImgWtLossSoftNLL, loss.py:182-263) of bilinearly up-sampled logits against border-set words, logits never materialised. As
-    _UpsampleCE: with a graph attached the forward leaves the column-reduced field and the backward is the row pass. The weights carry no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, bits, weights, inv_temp, want_grad):
-        lv = nhwc(logits)
-        ctx.inv_temp, ctx.hw = inv_temp, tuple(bits.shape[1:])
-        if not want_grad:
-            return K.upsample_relax_fwd(lv, bits, weights, inv_temp)[0]
-        out, field = K.upsample_relax_fwd_field(lv, bits, weights, inv_temp)
-        ctx.save_for_backward(lv, out, field)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lv, out, field = ctx.saved_tensors
-        dl = K.upsample_relax_bwd_field(lv, ctx.hw, out, field, g.reshape(1).float().contiguous(), ctx.inv_temp)
-        return nchw(dl), None, None, None, None
+    return _UpsampleLoss.apply(logits, labels, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad), 'wce', weights.detach(), per_image)
 
 
 def relax_sets(target, classes):
@@ -968,7 +941,7 @@ def upsample_relax(logits, bits, weights, inv_temp=1.0):
         return relaxed_soft_nll(torch.nn.functional.interpolate(logits, size=size, mode='bilinear', align_corners=True) * float(inv_temp), bits, weights)
     if not K.upsample_relax_ok(nhwc(logits), size):      # rows too wide for the fused kernel's LDS: as upsample_ce
         return relaxed_soft_nll(resize(logits, size) * float(inv_temp), bits, weights)
-    return _UpsampleRelax.apply(logits, bits.contiguous(), weights.detach(), float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad))
+    return _UpsampleLoss.apply(logits, bits, float(inv_temp), bool(torch.is_grad_enabled() and logits.requires_grad), 'relax', weights.detach())
 
 
 def mem_read(x, mem, noise=None):

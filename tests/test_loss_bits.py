@@ -53,3 +53,29 @@ def test_loss_bits(K, case):
     assert sorted(got) == sorted(want)
     diff = {call: (got[call], want[call]) for call in want if got[call] != want[call]}
     assert not diff, diff
+
+
+# ---- the relaxed-border families: recorded from the commit before their kernels became a third label form of the cross-entropy kernels --------------------------------
+def test_relax_size_queries_answer_what_the_recorded_table_holds():
+    """The four relaxed size queries for the same fifteen shapes; none of the thirteen cases is without a field (the set words fit LDS)."""
+    from pinthememory_amd.hip import lib as L
+    lib = L.load()
+    assert FIXTURE['relax_size_queries'] == TOOL.RELAX_SIZE_NAMES and sorted(FIXTURE['relax_sizes']) == sorted(c[0] for c in TOOL.CASES + TOOL.SIZE_ONLY)
+    for case in TOOL.CASES + TOOL.SIZE_ONLY:
+        assert TOOL.relax_sizes(lib, case) == FIXTURE['relax_sizes'][case[0]], case
+    assert all(FIXTURE['relax_sizes'][c[0]][2] > 0 for c in TOOL.CASES)
+
+
+def test_the_recorded_relax_cases_reach_the_kernels():
+    assert sorted(FIXTURE['relax_digests']) == sorted(c[0] for c in TOOL.CASES)
+    for call in {k for d in FIXTURE['relax_digests'].values() for k in d}:
+        assert sum(d[call] == 'refused' for d in FIXTURE['relax_digests'].values()) <= TOOL.MAX_REFUSED, call
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', TOOL.CASES, ids=[c[0] for c in TOOL.CASES])
+def test_relax_loss_bits(K, case):
+    got, want = TOOL.run_relax_case(K, case), FIXTURE['relax_digests'][case[0]]
+    assert sorted(got) == sorted(want)
+    diff = {call: (got[call], want[call]) for call in want if got[call] != want[call]}
+    assert not diff, diff

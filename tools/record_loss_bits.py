@@ -18,7 +18,7 @@ from ctypes import byref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'loss_bits.json')
-MAX_REFUSED = 2      # cases a call family may refuse (upsample_ce_fused_ok / upsample_eval_ok), of all of CASES
+MAX_REFUSED = 2      # cases a call family may refuse (upsample_ce_fused_ok / upsample_eval_ok / upsample_relax_ok), of all of CASES
 GSCALE = 1.7
 
 CASES = [
@@ -39,6 +39,8 @@ CASES = [
 SIZE_ONLY = [('main-loss', 8, (192, 192), (768, 768), 1.0, 19), ('eval-image', 1, (256, 512), (1024, 2048), 1.0, 19)]
 SIZE_NAMES = ['pm_upsample_ce_workspace', 'pm_upsample_ce_field_bytes', 'pm_upsample_ce_bwd_workspace', 'pm_upsample_wce_workspace', 'pm_upsample_wce_loss_floats',
               'pm_upsample_eval_workspace', 'pm_label_class_weights_workspace']
+RELAX_SIZE_NAMES = ['pm_upsample_relax_workspace', 'pm_upsample_relax_loss_floats', 'pm_upsample_relax_field_bytes', 'pm_relax_class_weights_workspace']
+STRICT_MASK = 0b101      # classes 0 and 2 keep their one-hot in the border-2 sets
 
 
 def sizes(lib, L, case):
@@ -48,6 +50,13 @@ def sizes(lib, L, case):
     return [lib.pm_upsample_ce_workspace(n, H, W), lib.pm_upsample_ce_field_bytes(byref(t), H, W), lib.pm_upsample_ce_bwd_workspace(byref(t), H, W),
             lib.pm_upsample_wce_workspace(n, H, W), lib.pm_upsample_wce_loss_floats(n), lib.pm_upsample_eval_workspace(byref(t), H, W),
             lib.pm_label_class_weights_workspace(n)]
+
+
+def relax_sizes(lib, case):
+    """The four size queries of the relaxed-border family (RELAX_SIZE_NAMES) for a case's shape."""
+    _, n, (h, w), (H, W), _, C = case
+    return [lib.pm_upsample_relax_workspace(n, H, W), lib.pm_upsample_relax_loss_floats(n), lib.pm_upsample_relax_field_bytes(n, h, w, C, H, W),
+            lib.pm_relax_class_weights_workspace(n)]
 
 
 def inputs(K, case):
@@ -113,6 +122,41 @@ def run_case(K, case):
     return out
 
 
+def run_relax_case(K, case):
+    """Every call of the relaxed-border families on the case's inputs -> {call: {output: sha256} or 'refused'}. The sets come from the case's own labels."""
+    import torch
+    _, n, _, HW, inv_temp, C = case
+    lg, lab, vec = inputs(K, case)
+    gs = torch.tensor([GSCALE], device='cuda')
+    out = {}
+    sets = {'border=0': K.relax_border_bits(lab, C, 0), 'border=1': K.relax_border_bits(lab, C, 1), 'border=2,strict': K.relax_border_bits(lab, C, 2, STRICT_MASK)}
+    out['relax_border_bits'] = {k: digest(v) for k, v in sets.items()}
+    bits = sets['border=1']
+    planes = ((bits.unsqueeze(1) >> torch.arange(C + 1, device='cuda').view(1, -1, 1, 1)) & 1).to(torch.uint8)
+    out['multihot_to_bits'] = {'bits': digest(K.multihot_to_bits(planes))}
+    rrows = {(norm, per_batch): K.relax_class_weights(bits, C, norm=norm, per_batch=per_batch) for norm in (False, True) for per_batch in (False, True)}
+    out['relax_class_weights'] = {'norm=%d,per_batch=%d' % k: digest(v) for k, v in rrows.items()}
+    relax = K.upsample_relax_ok(lg, HW)
+    for tag, wts in (('vector', vec), ('rows', rrows[(False, False)])):
+        out['relax_fwd[%s]' % tag] = {'loss_out': digest(K.upsample_relax_fwd(lg, bits, wts, inv_temp))}
+        if relax:
+            lf, field = K.upsample_relax_fwd_field(lg, bits, wts, inv_temp)
+            out['relax_fwd_field[%s]' % tag] = {'loss_out': digest(lf), 'field': digest(field)}
+            out['relax_bwd_field[%s]' % tag] = {'dlogits': digest(K.upsample_relax_bwd_field(lg, HW, lf, field, gs, inv_temp))}
+        else:
+            out['relax_fwd_field[%s]' % tag] = out['relax_bwd_field[%s]' % tag] = 'refused'
+    torch.cuda.synchronize()
+    return out
+
+
+def merge(old, new, what):
+    """Recording only ever adds: a value the fixture already holds has to come out of the parent build again."""
+    if not isinstance(old, dict) or not isinstance(new, dict):
+        assert old == new, 'the parent build no longer reproduces its own record: %s was %r, is %r' % (what, old, new)
+        return old
+    return {k: merge(old[k], new[k], '%s/%s' % (what, k)) if k in old else new[k] for k in list(old) + [k for k in new if k not in old]}
+
+
 def main():
     assert os.environ.get('PM_LIB'), 'set PM_LIB to a library built from the parent commit (tools/build_base_lib.sh)'
     import torch
@@ -122,17 +166,19 @@ def main():
     if os.path.exists(FIXTURE):
         with open(FIXTURE) as f:
             fixture = json.load(f)
-    fixture['size_queries'] = SIZE_NAMES
-    fixture['sizes'] = {c[0]: sizes(lib, L, c) for c in CASES + SIZE_ONLY}
+    fixture['size_queries'], fixture['relax_size_queries'] = SIZE_NAMES, RELAX_SIZE_NAMES
+    fixture['sizes'] = merge(fixture.get('sizes', {}), {c[0]: sizes(lib, L, c) for c in CASES + SIZE_ONLY}, 'sizes')
+    fixture['relax_sizes'] = merge(fixture.get('relax_sizes', {}), {c[0]: relax_sizes(lib, c) for c in CASES + SIZE_ONLY}, 'relax_sizes')
     if torch.cuda.is_available():
         from pinthememory_amd.hip import kernels as K
         version = subprocess.run([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--version'], capture_output=True, text=True).stdout
         fixture['hipcc'] = next((l.strip() for l in version.splitlines() if 'version' in l.lower()), '')      # for information only
-        fixture['digests'] = {c[0]: run_case(K, c) for c in CASES}
-        calls = sorted({k for d in fixture['digests'].values() for k in d})
-        for k in calls:
-            refused = [name for name, d in fixture['digests'].items() if d[k] == 'refused']
-            assert len(refused) <= MAX_REFUSED, 'replace a case: %s is refused for %s' % (k, refused)
+        fixture['digests'] = merge(fixture['digests'], {c[0]: run_case(K, c) for c in CASES}, 'digests')
+        fixture['relax_digests'] = merge(fixture.get('relax_digests', {}), {c[0]: run_relax_case(K, c) for c in CASES}, 'relax_digests')
+        for group in ('digests', 'relax_digests'):
+            for k in sorted({k for d in fixture[group].values() for k in d}):
+                refused = [name for name, d in fixture[group].items() if d[k] == 'refused']
+                assert len(refused) <= MAX_REFUSED, 'replace a case: %s is refused for %s' % (k, refused)
     else:
         print('no GPU: size queries recorded, digests kept as they were')
     with open(FIXTURE, 'w') as f:
