@@ -52,8 +52,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * because the array lives in device memory where the library cannot look at a first member.
  * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS.
  * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8).
- * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace). */
-#define PM_ABI_VERSION 440
+ * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace).
+ * 450: the evaluation input edge (pm_resize_axis_tables, pm_eval_tiles_u8), PM_FILTER_*. */
+#define PM_ABI_VERSION 450
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -432,6 +433,30 @@ int pm_resample_tables(const pm_geo_image* geo_host, int32_t struct_size, int Hs
 int pm_resample_crop_u8(const uint8_t* img, const uint8_t* lab, int n, int Hs, int Ws, const pm_geo_image* geo_dev, int32_t struct_size, const int32_t* bic_rows,
                         const int32_t* bic_cols, const int32_t* near_rows, const int32_t* near_cols, int th, int tw, int ignore_index, uint8_t* out_img, uint8_t* out_lab,
                         void* stream);
+
+/* ---- evaluation input edge: the scaled, mirrored, normalised crops of sliding-window evaluation, from the uint8 image on the device (csrc/resample.hip) ----------
+ * host only, no device involved: PIL's coefficient records (above) of a WHOLE axis resized from `in` to `out`, rec [out][PM_RESAMPLE_REC]: what
+ * img.resize((target_w, target_h), Image.BILINEAR) of eval.py:357-358 computes per axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc). PM_FILTER_BILINEAR:
+ * bilinear_filter, support 1.0; PM_FILTER_BICUBIC: bicubic_filter, support 2.0 -- the un-padded records of pm_resample_tables; either support is stretched by
+ * max(in / out, 1). in == out: one tap of 2^22 per position. PM_EINVAL: an empty size, a null pointer, an unknown filter. PM_EUNSUPPORTED: a position needs more than
+ * PM_RESAMPLE_MAX_TAPS taps (bilinear: in / out > 11.5; what rec holds then is unspecified). */
+#define PM_FILTER_BILINEAR 2      /* the values of PIL's Image.BILINEAR / Image.BICUBIC */
+#define PM_FILTER_BICUBIC 3
+int pm_resize_axis_tables(int in, int out, int filter, int32_t* rec);
+/* One launch per (image, scale) for everything eval.py runs between the decoded image and the network: the resize of eval.py:357-358, the mirror image of :362-364
+ * (transpose(FLIP_LEFT_RIGHT)), ToTensor + Normalize of :366-368 and the crops of sliding_window_cropping, :148-194. img uint8 [H][W][3]; rows_dev [Hs][PM_RESAMPLE_REC],
+ * cols_dev [Ws][PM_RESAMPLE_REC]: the two axis tables of pm_resize_axis_tables (H -> Hs, W -> Ws) in device memory; tiles_xyxy_dev: ntiles x (x1, y1, x2, y2) int32 in
+ * DEVICE memory, windows of the scaled image, all th x tw, which the CALLER has checked to lie inside [0, Ws] x [0, Hs] (the kernel reads x1, y1 alone and clamps them
+ * into [0, Ws - tw] x [0, Hs - th]); mean3 / std3: host floats. out fp32 [flips * ntiles][th][tw][4], 16-byte aligned: pixel (y, x) of tile t holds the scaled image's
+ * bytes at (y1 + y, x1 + x) -- PIL's: the pass along W rounded and clipped to bytes, then the pass along H -- normalised with the arithmetic of pm_image_u8_to_nhwc4
+ * (channel 3 = 0); tile ntiles + t holds the mirrored image's window, the bytes at (y1 + y, Ws - 1 - (x1 + x)). Equal to pm_image_u8_to_nhwc4 of the scaled image (of its
+ * mirror) sliced per tile, bit for bit; neither image is written to memory. Integer arithmetic up to the bytes, no atomics: the same bits on every run. A table that did
+ * not come from pm_resize_axis_tables gives undefined pixels, but its indices are clamped to the image: no access outside img, and nothing is written outside out.
+ * PM_EINVAL (each before any launch): a null pointer, an empty size, th > Hs or tw > Ws, flips not 1 or 2, out not 16-byte aligned or overlapping img or a table, a
+ * table not 4-byte aligned. PM_EUNSUPPORTED: flips * ntiles > 65535; W / Ws so large (beyond about 6.8) that PM_RESAMPLE_MAX_TAPS source rows of a 64-column piece's
+ * footprint do not fit the kernel's staging buffer. ntiles == 0: PM_OK, nothing launched. */
+int pm_eval_tiles_u8(const uint8_t* img_hw3, int H, int W, const int32_t* rows_dev, const int32_t* cols_dev, int Hs, int Ws, const int32_t* tiles_xyxy_dev, int ntiles,
+                     int th, int tw, int flips, const float* mean3, const float* std3, float* out, void* stream);
 
 /* ---- label-decoding input edge: colour- and id-coded masks -> train ids on the device (csrc/resample.hip) ----------------------------------------------------------
  * The per-image host loops of the reference's datasets over their label dicts, as one table lookup per pixel; uint8 in, uint8 out, exact.

@@ -320,10 +320,7 @@ namespace {
 __global__ __launch_bounds__(256) void image_u8_kernel(const uint8_t* __restrict__ img, long pixels, float m0, float m1, float m2, float s0, float s1,
                                                        float s2, float* __restrict__ out) {
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long)gridDim.x * 256) {
-    const uint8_t* q = img + p * 3;
-    // ToTensor: /255 ; Normalize: (x - mean) / std  -- same operation order as torchvision
-    const float4 o = make_float4(((float)q[0] / 255.f - m0) / s0, ((float)q[1] / 255.f - m1) / s1, ((float)q[2] / 255.f - m2) / s2, 0.f);
-    PM_ST4(out + p * 4, o);
+    PM_ST4(out + p * 4, pm_normalise_u8(img + p * 3, m0, m1, m2, s0, s1, s2));
   }
 }
 __global__ __launch_bounds__(256) void labels_u8_kernel(const uint8_t* __restrict__ lab, long n, int64_t* __restrict__ out) {

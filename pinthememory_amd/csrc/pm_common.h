@@ -254,6 +254,13 @@ __device__ __forceinline__ float pm_bn_affine(float v, float mu, float is, float
   return fmaf(v, s, fmaf(-mu, s, be));
 }
 
+// ToTensor + Normalize of one pixel (torchvision's order: / 255, - mean, / std; zero 4th channel), evaluated the same way wherever it appears -- pm_image_u8_to_nhwc4
+// and pm_eval_tiles_u8 -- whatever the translation unit's contraction setting.
+__device__ __forceinline__ float4 pm_normalise_u8(const uint8_t* q, float m0, float m1, float m2, float s0, float s1, float s2) {
+#pragma clang fp contract(off)
+  return make_float4(((float)q[0] / 255.f - m0) / s0, ((float)q[1] / 255.f - m1) / s1, ((float)q[2] / 255.f - m2) / s2, 0.f);
+}
+
 __device__ __forceinline__ float pm_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

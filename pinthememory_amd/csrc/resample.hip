@@ -1,6 +1,8 @@
 // Resampling input edge: RandomSizeAndCrop's antialiased bicubic resize (image) and nearest resize (mask), pad and crop, for the crop window alone, with PIL's
 // bytes (include/pinmem_hip.h, pm_resample_crop_u8). The host writes PIL's coefficient tables for the window (pm_resample_tables: double arithmetic, fixed point
 // 2^22); one kernel stages a tile's source footprint in LDS, filters it along W into bytes in a second LDS buffer, filters those along H and gathers the labels.
+// The evaluation edge (pm_eval_tiles_u8) runs the same passes with the tables of Image.resize(BILINEAR) over the whole scaled image (pm_resize_axis_tables) and
+// stores a piece of a sliding window, mirrored or not, as normalised float4 pixels: neither the scaled image nor its mirror exists in memory.
 #include "pm_common.h"
 
 #include <math.h>
@@ -16,6 +18,7 @@ constexpr int SRC_BYTES = 32768;                   // the staged footprint, rows
 constexpr int STAGE_U = MID_ROWS / NW / 2;         // rows a wave has in flight while staging
 constexpr int TAB_BYTES = (TH + TW) * REC * 4;     // 9 984: the tile's row and column records
 constexpr int LDS_BYTES = TAB_BYTES + MID_ROWS * ROWB + SRC_BYTES;      // 58 112: two blocks per CU
+constexpr int EVAL_LDS_BYTES = LDS_BYTES + TH * ROWB;                   // 64 256 with the tile's bytes in front of their conversion: still two blocks per CU
 
 __device__ __forceinline__ int clip8(int v) { return min(max(v, 0), 255); }
 
@@ -32,6 +35,90 @@ __device__ __forceinline__ void load_records(int* dst, const int32_t* __restrict
     r[0] = x0, r[1] = c;
   }
   __syncthreads();
+}
+
+// Source columns [fx0, fx0 + fw) the tile's columns with taps read (every lane computes the same: broadcast reads); staged rows start on a dword.
+struct Footprint {
+  int fx0, fwb, spb;      // first column, bytes of a footprint row, bytes between staged rows
+};
+__device__ __forceinline__ Footprint column_footprint(const int* ctab, int w_in) {
+  int fx0 = w_in, fx1 = 0;
+  for (int x = 0; x < TW; ++x) {
+    const int a = ctab[x * REC], c = ctab[x * REC + 1];
+    if (c > 0) fx0 = min(fx0, a), fx1 = max(fx1, a + c);
+  }
+  const int fwb = max(fx1 - fx0, 0) * 3;
+  return {fx0, fwb, (fwb + 3) & ~3};
+}
+
+// One pass takes as many of the tile's rows as fit: -> yb, rows [ya, yb) read source rows [fy0, fy0 + fh), which `mid` and `stage` hold. fh == 0 where one row alone
+// does not fit: not a table of this library (the hosts refuse such a geometry); its pixels come out as the rounding constant, 0.
+__device__ __forceinline__ int pass_rows(const int* rtab, int ya, int nr, int h_in, int spb, int& fy0, int& fh) {
+  int lo0 = h_in, hi0 = 0, yb = ya;
+  for (; yb < nr; ++yb) {
+    const int a = rtab[yb * REC], c = rtab[yb * REC + 1];
+    const int lo = c > 0 ? min(lo0, a) : lo0, hi = c > 0 ? max(hi0, a + c) : hi0;
+    if (yb > ya && (hi - lo > MID_ROWS || (hi - lo) * spb > SRC_BYTES)) break;
+    lo0 = lo, hi0 = hi;
+  }
+  fy0 = lo0, fh = max(hi0 - lo0, 0);
+  if (fh > MID_ROWS || fh * spb > SRC_BYTES) fh = 0;
+  return yb;
+}
+
+// Staging of rows [fy0, fy0 + fh) of the footprint from the image `src` with `pitch` pixels per row: a wave takes rows wave, wave + NW, ...; its lanes the dwords of a
+// row (loaded from any byte address), STAGE_U rows in flight; the last 0 .. 3 bytes of a row go one by one, so no byte outside the footprint is read.
+__device__ __forceinline__ void stage_rows(uint8_t* stage, const uint8_t* __restrict__ src, int pitch, int fy0, int fh, Footprint f, int tid) {
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int q = lane; q < (f.fwb >> 2); q += 64) {
+    for (int r0 = wave; r0 < fh; r0 += NW * STAGE_U) {
+      unsigned v[STAGE_U];
+#pragma unroll
+      for (int u = 0; u < STAGE_U; ++u)
+        if (r0 + u * NW < fh) __builtin_memcpy(&v[u], src + ((long)(fy0 + r0 + u * NW) * pitch + f.fx0) * 3 + 4 * q, 4);
+#pragma unroll
+      for (int u = 0; u < STAGE_U; ++u)
+        if (r0 + u * NW < fh) reinterpret_cast<unsigned*>(stage + (r0 + u * NW) * f.spb)[q] = v[u];
+    }
+  }
+  if (lane < (f.fwb & 3))
+    for (int r = wave; r < fh; r += NW) stage[r * f.spb + (f.fwb & ~3) + lane] = src[((long)(fy0 + r) * pitch + f.fx0) * 3 + (f.fwb & ~3) + lane];
+  __syncthreads();
+}
+
+// Along W: one pixel of one staged row per lane, rounded to bytes in `mid`; a pad column (no taps) holds 0, and stays 0 along H.
+__device__ __forceinline__ void filter_w(uint8_t* mid, const uint8_t* stage, const int* ctab, int fh, Footprint f, int tid) {
+  for (int i = tid; i < fh * TW; i += NT) {
+    const int r = i / TW, x = i - r * TW;
+    const int* rec = ctab + x * REC;
+    const int c = rec[1];
+    const uint8_t* p = stage + r * f.spb + (rec[0] - f.fx0) * 3;
+    int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
+    for (int j = 0; j < c; ++j) {
+      const int k = rec[2 + j];
+      s0 += p[3 * j] * k, s1 += p[3 * j + 1] * k, s2 += p[3 * j + 2] * k;
+    }
+    uint8_t* m = mid + r * ROWB + x * 3;
+    m[0] = (uint8_t)clip8(s0 >> PREC), m[1] = (uint8_t)clip8(s1 >> PREC), m[2] = (uint8_t)clip8(s2 >> PREC);
+  }
+  __syncthreads();
+}
+
+// clip8(s >> PREC) with the clamp in front of the shift: the same byte, the shift being monotone. Packing clip8(a >> PREC) | clip8(b >> PREC) << 8 directly makes hipcc
+// (ROCm 7.2) select v_ashr_pk_u8_i32 and OR the other bytes over its result; on gfx950 that instruction keeps bits 16 .. 31 of its destination register, which held
+// one of the sums (seen as bytes 2 and 3 of every packed dword ORed with bits 16 .. 31 of the second sum).
+__device__ __forceinline__ unsigned round8(int s) { return (unsigned)min(max(s, 0), (256 << PREC) - 1) >> PREC; }
+
+// Along H: bytes e .. e + 3 of the output row of record `rec` (`c` of its taps), from the rows of `mid` that start at source row fy0, packed low byte first.
+__device__ __forceinline__ unsigned filter_h4(const uint8_t* mid, const int* rec, int c, int fy0, int e) {
+  const uint8_t* p = mid + (rec[0] - fy0) * ROWB + e;
+  int s[4] = {1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1)};
+  for (int j = 0; j < c; ++j) {
+    const unsigned v = *reinterpret_cast<const unsigned*>(p + j * ROWB);
+    const int k = rec[2 + j];
+    s[0] += (int)(v & 255u) * k, s[1] += (int)((v >> 8) & 255u) * k, s[2] += (int)((v >> 16) & 255u) * k, s[3] += (int)(v >> 24) * k;
+  }
+  return round8(s[0]) | round8(s[1]) << 8 | round8(s[2]) << 16 | round8(s[3]) << 24;
 }
 
 // The decode step of the label-decoding edge (include/pinmem_hip.h, pm_label_table): one label pixel through its image's table, which the block holds in LDS; a null
@@ -112,84 +199,72 @@ __global__ __launch_bounds__(NT) void resample_crop_kernel(const uint8_t* __rest
   load_records(rtab, bic_rows + (long)n * th * REC, y0, TH, th, h_in, tid);
   load_records(ctab, bic_cols + (long)n * tw * REC, x0, TW, tw, w_in, tid);
 
-  // source columns the tile reads: [fx0, fx1) over the columns with taps (every lane computes the same: broadcast reads)
-  int fx0 = w_in, fx1 = 0;
-  for (int x = 0; x < TW; ++x) {
-    const int a = ctab[x * REC], c = ctab[x * REC + 1];
-    if (c > 0) fx0 = min(fx0, a), fx1 = max(fx1, a + c);
-  }
-  const int fw = max(fx1 - fx0, 0), fwb = fw * 3, spb = (fwb + 3) & ~3;      // staged rows start on a dword
+  const Footprint f = column_footprint(ctab, w_in);
   const uint8_t* src = img + (long)n * slab * 3;
   uint8_t* dst = out_img + (((long)n * th + y0) * tw + x0) * 3;
   const bool vec = (((long)tw * 3) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_img) & 3) == 0;      // every tile row starts on a dword and ends on one
-  const int wave = tid >> 6, lane = tid & 63;
 
   // the tile's rows in passes of as many as fit: the source rows of a pass go through `stage` into `mid`
   for (int ya = 0; ya < nr;) {
-    int fy0 = h_in, fy1 = 0, yb = ya;
-    for (; yb < nr; ++yb) {
-      const int a = rtab[yb * REC], c = rtab[yb * REC + 1];
-      const int lo = c > 0 ? min(fy0, a) : fy0, hi = c > 0 ? max(fy1, a + c) : fy1;
-      if (yb > ya && (hi - lo > MID_ROWS || (hi - lo) * spb > SRC_BYTES)) break;
-      fy0 = lo, fy1 = hi;
-    }
-    int fh = max(fy1 - fy0, 0);
-    if (fh > MID_ROWS || fh * spb > SRC_BYTES) fh = 0;      // one row alone does not fit: not a table of pm_resample_tables; its pixels come out as the rounding constant, 0
-
-    // staging: a wave takes rows wave, wave + NW, ...; its lanes the dwords of a row (loaded from any byte address), STAGE_U rows in flight; the last 0 .. 3 bytes of a
-    // row go one by one, so no byte outside the footprint is read
-    for (int q = lane; q < (fwb >> 2); q += 64) {
-      for (int r0 = wave; r0 < fh; r0 += NW * STAGE_U) {
-        unsigned v[STAGE_U];
-#pragma unroll
-        for (int u = 0; u < STAGE_U; ++u)
-          if (r0 + u * NW < fh) __builtin_memcpy(&v[u], src + ((long)(fy0 + r0 + u * NW) * Ws + fx0) * 3 + 4 * q, 4);
-#pragma unroll
-        for (int u = 0; u < STAGE_U; ++u)
-          if (r0 + u * NW < fh) reinterpret_cast<unsigned*>(stage + (r0 + u * NW) * spb)[q] = v[u];
-      }
-    }
-    if (lane < (fwb & 3))
-      for (int r = wave; r < fh; r += NW) stage[r * spb + (fwb & ~3) + lane] = src[((long)(fy0 + r) * Ws + fx0) * 3 + (fwb & ~3) + lane];
-    __syncthreads();
-    for (int i = tid; i < fh * TW; i += NT) {               // along W: one pixel of one staged row per lane
-      const int r = i / TW, x = i - r * TW;
-      const int* rec = ctab + x * REC;
-      const int c = rec[1];
-      const uint8_t* p = stage + r * spb + (rec[0] - fx0) * 3;
-      int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
-      for (int j = 0; j < c; ++j) {
-        const int k = rec[2 + j];
-        s0 += p[3 * j] * k, s1 += p[3 * j + 1] * k, s2 += p[3 * j + 2] * k;
-      }
-      uint8_t* m = mid + r * ROWB + x * 3;                   // a pad column (no taps) holds 0, and stays 0 along H
-      m[0] = (uint8_t)clip8(s0 >> PREC), m[1] = (uint8_t)clip8(s1 >> PREC), m[2] = (uint8_t)clip8(s2 >> PREC);
-    }
-    __syncthreads();
+    int fy0, fh;
+    const int yb = pass_rows(rtab, ya, nr, h_in, f.spb, fy0, fh);
+    stage_rows(stage, src, Ws, fy0, fh, f, tid);
+    filter_w(mid, stage, ctab, fh, f, tid);
     for (int i = tid; i < (yb - ya) * (ROWB / 4); i += NT) {      // along H: four bytes of one output row per lane
       const int ly = ya + i / (ROWB / 4), e = (i % (ROWB / 4)) * 4;
       const int* rec = rtab + ly * REC;
-      const int c = fh > 0 ? rec[1] : 0;
-      const uint8_t* p = mid + (rec[0] - fy0) * ROWB + e;
-      int s[4] = {1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1)};
-      for (int j = 0; j < c; ++j) {
-        const unsigned v = *reinterpret_cast<const unsigned*>(p + j * ROWB);
-        const int k = rec[2 + j];
-        s[0] += (int)(v & 255u) * k, s[1] += (int)((v >> 8) & 255u) * k, s[2] += (int)((v >> 16) & 255u) * k, s[3] += (int)(v >> 24) * k;
-      }
+      const unsigned v = filter_h4(mid, rec, fh > 0 ? rec[1] : 0, fy0, e);
       uint8_t* o = dst + (long)ly * tw * 3 + e;
       if (vec) {
-        if (e < nc * 3)
-          *reinterpret_cast<unsigned*>(o) = (unsigned)clip8(s[0] >> PREC) | (unsigned)clip8(s[1] >> PREC) << 8 | (unsigned)clip8(s[2] >> PREC) << 16 |
-                                            (unsigned)clip8(s[3] >> PREC) << 24;
+        if (e < nc * 3) *reinterpret_cast<unsigned*>(o) = v;
       } else {
 #pragma unroll
         for (int b = 0; b < 4; ++b)
-          if (e + b < nc * 3) o[b] = (uint8_t)clip8(s[b] >> PREC);
+          if (e + b < nc * 3) o[b] = (uint8_t)(v >> (8 * b));
       }
     }
     __syncthreads();      // `stage` and `mid` are free for the next pass
     ya = yb;
+  }
+}
+
+// pm_eval_tiles_u8: blocks (x piece, y piece, flip * T + tile). The piece's rows and columns of the SCALED image go through the passes above; a mirrored window
+// computes the un-mirrored columns [Ws - x2, Ws - x1) and stores them reversed. The tile's origin is clamped so that the window lies inside the scaled image whatever the
+// table holds (the host has checked th <= Hs, tw <= Ws), the records are clamped by load_records, and every store address comes from the block index alone.
+__global__ __launch_bounds__(NT) void eval_tiles_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
+                                                         int Hs, int Ws, const int32_t* __restrict__ tiles, int T, int th, int tw, float m0, float m1, float m2, float s0,
+                                                         float s1, float s2, float* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  int* rtab = reinterpret_cast<int*>(smem);                  // [TH][REC]
+  int* ctab = rtab + TH * REC;                               // [TW][REC]
+  uint8_t* mid = smem + TAB_BYTES;                           // [MID_ROWS][ROWB]
+  uint8_t* stage = mid + MID_ROWS * ROWB;
+  uint8_t* px = stage + SRC_BYTES;                           // [TH][ROWB]: the piece's scaled bytes, un-mirrored
+  const int t = blockIdx.z % T, y0 = blockIdx.y * TH, x0 = blockIdx.x * TW, tid = threadIdx.x;
+  const bool mirror = (int)blockIdx.z >= T;
+  const int nr = min(TH, th - y0), nc = min(TW, tw - x0);
+  const int y1 = min(max(tiles[4 * t + 1], 0), Hs - th) + y0, x1 = min(max(tiles[4 * t], 0), Ws - tw) + x0;      // the piece's origin in the window's own direction
+  const int c0 = mirror ? Ws - x1 - nc : x1;                 // first un-mirrored column: x1 + nc <= Ws
+  load_records(rtab, rows, y1, TH, y1 + nr, H, tid);
+  load_records(ctab, cols, c0, TW, c0 + nc, W, tid);
+  const Footprint f = column_footprint(ctab, W);
+  for (int ya = 0; ya < nr;) {
+    int fy0, fh;
+    const int yb = pass_rows(rtab, ya, nr, H, f.spb, fy0, fh);
+    stage_rows(stage, img, W, fy0, fh, f, tid);
+    filter_w(mid, stage, ctab, fh, f, tid);
+    for (int i = tid; i < (yb - ya) * (ROWB / 4); i += NT) {
+      const int ly = ya + i / (ROWB / 4), e = (i % (ROWB / 4)) * 4;
+      const int* rec = rtab + ly * REC;
+      *reinterpret_cast<unsigned*>(px + ly * ROWB + e) = filter_h4(mid, rec, fh > 0 ? rec[1] : 0, fy0, e);
+    }
+    __syncthreads();
+    ya = yb;
+  }
+  float* dst = out + (((long)blockIdx.z * th + y0) * tw + x0) * 4;
+  for (int i = tid; i < nr * TW; i += NT) {                  // one pixel per lane: a wave stores 1 KiB of a row
+    const int ly = i / TW, lx = i - ly * TW;
+    if (lx < nc) PM_ST4(dst + ((long)ly * tw + lx) * 4, pm_normalise_u8(px + ly * ROWB + (mirror ? nc - 1 - lx : lx) * 3, m0, m1, m2, s0, s1, s2));
   }
 }
 
@@ -202,9 +277,25 @@ double bicubic(double x) {
   return 0.0;
 }
 
+// PIL's triangle (Resample.c bilinear_filter)
+double bilinear(double x) {
+  if (x < 0.0) x = -x;
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+struct Filter {
+  double (*weight)(double);
+  double support;
+};
+// the struct imagingfilter of Resample.c behind a PM_FILTER_* value; null: not one of them
+const Filter* filter_of(int filter) {
+  static const Filter BILINEAR = {bilinear, 1.0}, BICUBIC = {bicubic, 2.0};
+  return filter == PM_FILTER_BILINEAR ? &BILINEAR : filter == PM_FILTER_BICUBIC ? &BICUBIC : nullptr;
+}
+
 // precompute_coeffs + normalize_coeffs_8bpc of Resample.c for output positions [p0 - pad, p0 - pad + cnt) of an axis resized from `in` to `out`; false: over the tap cap
-bool bicubic_axis(int in, int out, int pad, int p0, int cnt, int32_t* rec, int* taps_needed) {
-  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale, support = 2.0 * fs, ss = 1.0 / fs;
+bool filter_axis(const Filter& f, int in, int out, int pad, int p0, int cnt, int32_t* rec, int* taps_needed) {
+  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale, support = f.support * fs, ss = 1.0 / fs;
   for (int i = 0; i < cnt; ++i) {
     int32_t* r = rec + (long)i * REC;
     for (int j = 0; j < REC; ++j) r[j] = 0;
@@ -226,7 +317,7 @@ bool bicubic_axis(int in, int out, int pad, int p0, int cnt, int32_t* rec, int* 
     }
     double w[MAXT], ww = 0.0;
     for (int x = 0; x < xmax; ++x) {
-      w[x] = bicubic((x + xmin - center + 0.5) * ss);
+      w[x] = f.weight((x + xmin - center + 0.5) * ss);
       ww += w[x];
     }
     r[0] = xmin, r[1] = xmax;
@@ -262,11 +353,22 @@ extern "C" int pm_resample_tables(const pm_geo_image* g, int32_t struct_size, in
   PM_REQUIRE(g->y1 >= 0 && g->x1 >= 0 && (long)g->y1 + th <= (long)g->h + 2l * g->pad_h && (long)g->x1 + tw <= (long)g->w + 2l * g->pad_w, PM_EINVAL,
              "resample_tables: crop %d x %d at (%d, %d) outside the padded image %ld x %ld", th, tw, g->y1, g->x1, (long)g->h + 2l * g->pad_h, (long)g->w + 2l * g->pad_w);
   int need = 0;
-  const bool ok = bicubic_axis(g->h_in, g->h, g->pad_h, g->y1, th, bic_rows, &need) && bicubic_axis(g->w_in, g->w, g->pad_w, g->x1, tw, bic_cols, &need);
+  const Filter& f = *filter_of(PM_FILTER_BICUBIC);
+  const bool ok = filter_axis(f, g->h_in, g->h, g->pad_h, g->y1, th, bic_rows, &need) && filter_axis(f, g->w_in, g->w, g->pad_w, g->x1, tw, bic_cols, &need);
   PM_REQUIRE(ok, PM_EUNSUPPORTED, "resample_tables: %d x %d -> %d x %d needs %d taps per output position, more than PM_RESAMPLE_MAX_TAPS = %d", g->h_in, g->w_in, g->h,
              g->w, need, MAXT);
   nearest_axis(g->h_in, g->h, g->pad_h, g->y1, th, near_rows);
   nearest_axis(g->w_in, g->w, g->pad_w, g->x1, tw, near_cols);
+  return PM_OK;
+}
+
+extern "C" int pm_resize_axis_tables(int in, int out, int filter, int32_t* rec) {
+  const Filter* f = filter_of(filter);
+  PM_REQUIRE(rec && f, PM_EINVAL, "resize_axis_tables: null pointer or unknown filter %d", filter);
+  PM_REQUIRE(in > 0 && out > 0, PM_EINVAL, "resize_axis_tables: empty size (%d -> %d)", in, out);
+  int need = 0;
+  PM_REQUIRE(filter_axis(*f, in, out, 0, 0, out, rec, &need), PM_EUNSUPPORTED,
+             "resize_axis_tables: %d -> %d needs %d taps per output position, more than PM_RESAMPLE_MAX_TAPS = %d", in, out, need, MAXT);
   return PM_OK;
 }
 
@@ -367,6 +469,33 @@ extern "C" int pm_resample_crop_decode_u8(const uint8_t* img, const uint8_t* lab
   if (int rc = check_label_tables("resample_crop_decode_u8", lab_c, tables, ntables, struct_size_table, image_table)) return rc;
   return resample_crop<true>("resample_crop_decode_u8", img, lab, n, Hs, Ws, geo, struct_size, bic_rows, bic_cols, near_rows, near_cols, th, tw, ignore_index, lab_c, tables,
                              ntables, image_table, out_img, out_lab, stream);
+}
+
+extern "C" int pm_eval_tiles_u8(const uint8_t* img, int H, int W, const int32_t* rows, const int32_t* cols, int Hs, int Ws, const int32_t* tiles, int ntiles, int th, int tw,
+                                int flips, const float* mean3, const float* std3, float* out, void* stream) {
+  PM_REQUIRE(img && rows && cols && tiles && mean3 && std3 && out, PM_EINVAL, "eval_tiles_u8: null pointer");
+  PM_REQUIRE(H > 0 && W > 0 && Hs > 0 && Ws > 0 && th > 0 && tw > 0 && ntiles >= 0, PM_EINVAL, "eval_tiles_u8: empty size (image %d x %d, scaled %d x %d, %d tiles of %d x %d)", H,
+             W, Hs, Ws, ntiles, th, tw);
+  PM_REQUIRE(th <= Hs && tw <= Ws, PM_EINVAL, "eval_tiles_u8: tiles of %d x %d in a scaled image of %d x %d", th, tw, Hs, Ws);
+  PM_REQUIRE(flips == 1 || flips == 2, PM_EINVAL, "eval_tiles_u8: flips %d (1: the image, 2: and its mirror)", flips);
+  PM_REQUIRE(pm_aligned16(out), PM_EINVAL, "eval_tiles_u8: out must be 16-byte aligned");
+  PM_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(tiles)) & 3) == 0, PM_EINVAL,
+             "eval_tiles_u8: the tables must be 4-byte aligned");
+  const size_t out_b = (size_t)flips * ntiles * th * tw * 16;
+  const uint8_t* o = reinterpret_cast<const uint8_t*>(out);
+  PM_REQUIRE(!(overlap(o, out_b, img, (size_t)H * W * 3) || overlap(o, out_b, reinterpret_cast<const uint8_t*>(rows), (size_t)Hs * REC * 4) ||
+               overlap(o, out_b, reinterpret_cast<const uint8_t*>(cols), (size_t)Ws * REC * 4) || overlap(o, out_b, reinterpret_cast<const uint8_t*>(tiles), (size_t)ntiles * 16)),
+             PM_EINVAL, "eval_tiles_u8: out overlaps the image or a table");
+  PM_REQUIRE((long)flips * ntiles <= 65535 && pm_cdiv(th, TH) <= 65535, PM_EUNSUPPORTED, "eval_tiles_u8: %d tiles x %d flips / tile height %d beyond the launch grid", ntiles,
+             flips, th);
+  // one output row alone must fit the staging buffers: at most MAXT source rows of a piece's columns, which reach over (TW - 1) * W / Ws + MAXT + 2 source pixels at the most
+  const long reach = std::min<long>(W, (long)((TW - 1) * ((double)W / Ws)) + MAXT + 2), rows_most = std::min(H, MAXT);
+  PM_REQUIRE(rows_most * ((reach * 3 + 3) & ~3l) <= SRC_BYTES, PM_EUNSUPPORTED,
+             "eval_tiles_u8: %d -> %d columns: %d source rows of %ld pixels do not fit the %d staged bytes of a %d-column piece", W, Ws, (int)rows_most, reach, SRC_BYTES, TW);
+  if (ntiles == 0) return PM_OK;
+  hipLaunchKernelGGL(eval_tiles_kernel, dim3(pm_cdiv(tw, TW), pm_cdiv(th, TH), flips * ntiles), dim3(NT), EVAL_LDS_BYTES, (hipStream_t)stream, img, H, W, rows, cols, Hs, Ws,
+                     tiles, ntiles, th, tw, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out);
+  return pm_check_launch("eval_tiles_u8");
 }
 
 extern "C" int pm_labels_decode_u8(const uint8_t* lab, int n, int H, int W, int lab_c, const pm_label_table* tables, int ntables, int32_t struct_size,

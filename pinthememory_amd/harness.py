@@ -547,7 +547,8 @@ def tile_stack(parts):
     return low
 
 
-def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3, flips=(False, True), hist=None, want_logits=False, batch_tiles=True):
+def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3, flips=(False, True), hist=None, want_logits=False, batch_tiles=True,
+                     device_tiles=False):
     """eval.py:340-405 (inference_sliding) and :647-653 (mean over the scales, argmax, fast_hist) for ONE image. Per scale: the image is scaled (PIL on the host; scale 1
     is sliced on the device as it is), normalised (K.image_u8_to_nhwc4), cut into sliding_tiles and forwarded -- mirrored too unless flips=(False,) -- with the heads
     returning their LOW-RES logits; one K.sliding_eval launch sequence then up-samples, stitches, un-flips and averages them without writing the up-sampled tiles or
@@ -555,6 +556,10 @@ def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3
     size (cv2.resize INTER_LINEAR) into a float64 accumulator and K.sliding_eval_finish yields the class map and the histogram. Nothing is copied to the host.
     img: uint8 [H, W, 3], host or device; a normalised float [3, H, W] is taken when every scale is 1. gt: [H, W] train ids (255 = ignore) or None. hist: int64
     [C, C] on the device to add into (None: a fresh one when gt is given). batch_tiles=False forwards tile by tile (eval.py:383-390, without --faster).
+    device_tiles=True: the uint8 image, host or device, goes to the device once and every scale, 1.0 included, takes its crops of both flips from ONE
+    K.eval_tiles_u8 launch (PIL's bilinear bytes, the mirror image, the normalisation and the cropping; the tables come from K.eval_tile_plan's cache) instead of
+    PIL on the host + K.image_u8_to_nhwc4 + torch.flip + slices + torch.stack: the same bits, so the same result. A float image raises ValueError with it; a scale
+    the library's tables do not hold raises its PinmemError.
     -> dict(pred uint8 [H, W], hist, logits float64 [C, H, W] with want_logits else None). Leaves the net in eval mode."""
     m = net.module if hasattr(net, 'module') else net
     device = next(m.parameters()).device
@@ -569,6 +574,10 @@ def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3
             raise ValueError('evaluate_sliding: a normalised float image cannot be re-scaled as the reference scales its uint8 image; pass uint8 [H, W, 3]')
         assert img.dim() == 3 and img.shape[0] == 3 and img.is_floating_point(), 'float images are normalised [3, H, W]'
         H, W = img.shape[1:]
+    if device_tiles:
+        if not as_u8:
+            raise ValueError('evaluate_sliding: device_tiles=True scales and normalises the uint8 [H, W, 3] image itself; a normalised float image has no bytes to scale')
+        img = img.to(device).contiguous()
     if gt is not None:
         gt = gt.to(device=device, dtype=torch.int64).reshape(H, W).contiguous()
     single = scales == (1.0,)
@@ -579,15 +588,22 @@ def evaluate_sliding(net, img, gt=None, crop=768, scales=(1.0,), overlap=1.0 / 3
     try:
         with torch.no_grad():
             for i, s in enumerate(scales):
-                if as_u8:
+                if device_tiles:
+                    plan = K.eval_tile_plan(H, W, s, crop, overlap, device)
+                    Hs, Ws, tiles = plan.Hs, plan.Ws, plan.tiles
+                    x = K.eval_tiles_u8(img, plan, len(flips))      # [F * T, th, tw, 4]
+                elif as_u8:
                     x = K.image_u8_to_nhwc4((img if s == 1.0 else _scaled_u8(img, s)).to(device)[None].contiguous())[0]      # [Hs, Ws, 4]
                     Hs, Ws = x.shape[:2]
                 else:
                     x, Hs, Ws = img.to(device), H, W
-                tiles = sliding_tiles(Hs, Ws, crop, overlap, s)
+                if not device_tiles:
+                    tiles = sliding_tiles(Hs, Ws, crop, overlap, s)
                 lows = []
-                for flip in flips:
-                    if as_u8:
+                for k, flip in enumerate(flips):
+                    if device_tiles:
+                        crops = ops.nchw(x[k * len(tiles):(k + 1) * len(tiles)])
+                    elif as_u8:
                         src = torch.flip(x, dims=[1]) if flip else x
                         crops = ops.nchw(torch.stack([src[y1:y2, x1:x2] for (x1, y1, x2, y2) in tiles]))
                     else:
@@ -618,17 +634,17 @@ def eval_metrics(hist):
     return torch.stack([diag.sum() / total, torch.nanmean(diag / rows), torch.nanmean(iu), torch.where(freq > 0, freq * iu, torch.zeros_like(iu)).sum()])
 
 
-def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, classes=19, dump=0):
+def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, classes=19, dump=0, device_tiles=False):
     """The loop of eval.py:756-779 over RunEval.inf (:630-653) and final_dump (:695-702) without the image files: `loader` yields (image, gt, ...) with the image
     uint8 [H, W, 3] (or [1, H, W, 3]) and gt [H, W] (or [1, H, W]); every image goes through evaluate_sliding into ONE histogram on the device, and nothing is
     copied to the host before the last image. -> dict(hist int64 [classes, classes] on the device, acc, acc_cls, mean_iu, fwavacc as evaluate_eval_for_inference
-    computes them, predictions: the uint8 class maps of the first `dump` images)."""
+    computes them, predictions: the uint8 class maps of the first `dump` images). device_tiles: as evaluate_sliding takes it."""
     m = net.module if hasattr(net, 'module') else net
     hist = torch.zeros((classes, classes), dtype=torch.int64, device=next(m.parameters()).device)
     predictions = []
     for idx, data in enumerate(loader):
         img, gt = data[0], data[1]
-        res = evaluate_sliding(net, img[0] if img.dim() == 4 else img, gt, crop, scales, overlap, (False,) if no_flip else (False, True), hist=hist)
+        res = evaluate_sliding(net, img[0] if img.dim() == 4 else img, gt, crop, scales, overlap, (False,) if no_flip else (False, True), hist=hist, device_tiles=device_tiles)
         if idx < dump:
             predictions.append(res['pred'])
     acc, acc_cls, mean_iu, fwavacc = eval_metrics(hist).tolist()

@@ -952,6 +952,110 @@ def resample_crop_u8(img_u8, lab_u8, geo):
     return out, out_lab
 
 
+# ---- evaluation input edge (csrc/resample.hip): scaled, mirrored, normalised sliding-window crops ---------------------------
+def resize_axis_tables(n_in, n_out, filter=L.FILTER_BILINEAR):
+    """PIL's coefficient records of a whole axis resized from n_in to n_out (pm_resize_axis_tables; no device involved): a ctypes int32 array [n_out * REC].
+    Raises PinmemError for what the library refuses (empty sizes, an unknown filter, more taps than the records hold)."""
+    rec = (ctypes.c_int32 * (max(int(n_out), 0) * L.RESAMPLE_REC))()
+    check(_lib().pm_resize_axis_tables(int(n_in), int(n_out), int(filter), ctypes.addressof(rec)), 'pm_resize_axis_tables')
+    return rec
+
+
+class EvalTilePlan:
+    """What eval_tiles_u8 needs for one (image size, scale): the scaled size (Hs, Ws) = (int(H * scale), int(W * scale)) of eval.py:357, tiles =
+    harness.sliding_tiles(Hs, Ws, crop, overlap, scale) with their common size (th, tw), and ONE uint8 device tensor holding the bilinear row table, the column table
+    and the tile table (offsets). The library writes the tables straight into one pinned block, the tiles are checked here (inside the scaled image, equal sizes: the
+    kernel cannot report them) and the block is copied once without blocking on the current stream, as upload_geo does. uploads counts those copies."""
+    uploads = 0
+
+    def __init__(self, H, W, scale, crop, overlap, device, tiles=None):
+        from .. import harness
+        self.H, self.W, self.scale = int(H), int(W), float(scale)
+        self.Hs, self.Ws = int(H * scale), int(W * scale)
+        if self.Hs <= 0 or self.Ws <= 0:
+            raise ValueError('EvalTilePlan: %d x %d at scale %g is empty' % (H, W, scale))
+        # tiles: a caller's own windows (x1, y1, x2, y2) of the scaled image instead (crop and overlap are then not looked at)
+        self.tiles = harness.sliding_tiles(self.Hs, self.Ws, crop, overlap, scale) if tiles is None else [tuple(int(v) for v in t) for t in tiles]
+        x1, y1, x2, y2 = self.tiles[0] if self.tiles else (0, 0, 0, 0)      # eval.py:168-170 yields no tile for an axis shorter than the tile by a stride or more
+        self.th, self.tw = y2 - y1, x2 - x1
+        for t in self.tiles:
+            if not (0 <= t[0] < t[2] <= self.Ws and 0 <= t[1] < t[3] <= self.Hs and (t[3] - t[1], t[2] - t[0]) == (self.th, self.tw)):
+                raise ValueError('EvalTilePlan: tile %s outside the scaled image %d x %d or of another size than %d x %d' % (t, self.Hs, self.Ws, self.th, self.tw))
+        rec, lib = L.RESAMPLE_REC * 4, _lib()
+        self.offsets = (0, self.Hs * rec, (self.Hs + self.Ws) * rec)
+        host = torch.empty(self.offsets[2] + len(self.tiles) * 16, dtype=torch.uint8, pin_memory=torch.device(device).type == 'cuda')
+        base = host.data_ptr()
+        check(lib.pm_resize_axis_tables(self.H, self.Hs, L.FILTER_BILINEAR, base + self.offsets[0]), 'pm_resize_axis_tables (rows)')
+        check(lib.pm_resize_axis_tables(self.W, self.Ws, L.FILTER_BILINEAR, base + self.offsets[1]), 'pm_resize_axis_tables (columns)')
+        staged = _i32([v for t in self.tiles for v in t])
+        ctypes.memmove(base + self.offsets[2], ctypes.addressof(staged), len(self.tiles) * 16)
+        self.buf = host.to(device, non_blocking=True)
+        EvalTilePlan.uploads += 1
+        self.streams = {}                   # raw handle -> every stream that read the block
+        self.stream = self.event = None     # the copy's raw stream and an event behind it, for a reader on another stream
+        if self.buf.is_cuda:
+            self.stream, self.event = stream(), L.stream_obj().record_event()
+
+    def use(self):
+        """Called in front of a launch on the current stream that reads the block."""
+        raw = stream()
+        if raw not in self.streams:
+            self.streams[raw] = L.stream_obj()
+            if raw != self.stream:
+                self.streams[raw].wait_event(self.event)
+
+    def release(self):
+        """The block leaves the cache and goes back to the pool of the stream that allocated it: tell the allocator about every stream whose queued launches may
+        still read it (as _FilterCache._drop does)."""
+        for s in self.streams.values():
+            self.buf.record_stream(s)
+
+
+class _EvalPlanCache(dict):
+    """constructor arguments -> EvalTilePlan, at most EVAL_PLAN_CACHE_MAX of them, evicted in insertion order: the second image of a dataset at a scale does no host
+    table work and uploads nothing."""
+
+    def get_plan(self, H, W, scale, crop, overlap, device):
+        key = (int(H), int(W), float(scale), int(crop), float(overlap), str(torch.device(device)))
+        plan = self.get(key)
+        if plan is None:
+            plan = EvalTilePlan(H, W, scale, crop, overlap, device)      # raises before anything is evicted
+            while len(self) >= EVAL_PLAN_CACHE_MAX:
+                self.pop(next(iter(self))).release()
+            self[key] = plan
+        return plan
+
+    def clear(self):
+        while self:
+            self.pop(next(iter(self))).release()
+
+
+EVAL_PLAN_CACHE_MAX = 8
+_EVAL_PLANS = _EvalPlanCache()
+eval_tile_plan, clear_eval_tile_plans = _EVAL_PLANS.get_plan, _EVAL_PLANS.clear
+
+
+def eval_tiles_u8(img_u8, plan, flips=2, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """uint8 [H, W, 3] on the device -> fp32 NHWC4 [flips * T, th, tw, 4]: the crops of plan.tiles from the image resized to (plan.Hs, plan.Ws) with the bytes of PIL's
+    Image.resize(BILINEAR), normalised as image_u8_to_nhwc4 does; with flips=2 the same windows of the mirrored scaled image follow (pm_eval_tiles_u8). Neither the
+    scaled image nor its mirror is written. out: a contiguous fp32 tensor of that shape to write into."""
+    assert img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.is_cuda, 'a contiguous uint8 [H, W, 3] device image'
+    assert tuple(img_u8.shape[:2]) == (plan.H, plan.W), 'plan for %d x %d, image %d x %d' % (plan.H, plan.W, img_u8.shape[0], img_u8.shape[1])
+    assert plan.buf.device == img_u8.device, 'plan on %s, image on %s' % (plan.buf.device, img_u8.device)
+    T, shape = len(plan.tiles), (int(flips) * len(plan.tiles), plan.th, plan.tw, 4)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=img_u8.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == img_u8.device
+    if T == 0:
+        return out                          # an empty [0, 0, 0, 4]
+    m, s = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    plan.use()
+    p, o = plan.buf.data_ptr(), plan.offsets
+    check(_lib().pm_eval_tiles_u8(img_u8.data_ptr(), plan.H, plan.W, p + o[0], p + o[1], plan.Hs, plan.Ws, p + o[2], T, plan.th, plan.tw, int(flips), m, s, out.data_ptr(),
+                                  stream()), 'pm_eval_tiles_u8')
+    return out
+
+
 # ---- label-decoding input edge (csrc/resample.hip) -------------------------------------------------------------------------
 def _i32(values):
     return (ctypes.c_int32 * max(len(values), 1))(*[int(v) for v in values])

@@ -61,6 +61,7 @@ class PmLabelTable(ctypes.Structure):
 
 RESAMPLE_MAX_TAPS = 24                # include/pinmem_hip.h PM_RESAMPLE_MAX_TAPS
 RESAMPLE_REC = RESAMPLE_MAX_TAPS + 2       # PM_RESAMPLE_REC
+FILTER_BILINEAR, FILTER_BICUBIC = 2, 3     # PM_FILTER_*: PIL's Image.BILINEAR / Image.BICUBIC
 
 
 class PmConvEpilogue(ctypes.Structure):
@@ -76,7 +77,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 440         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 450         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -154,6 +155,8 @@ SIGNATURES = {
     'pm_labels_u8_flip_to_i64': (_i, [_vp, _i, _i, _i, _vp, c_int32, _vp, _vp]),
     'pm_resample_tables': (_i, [_vp, c_int32, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'pm_resample_crop_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, c_int32, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'pm_resize_axis_tables': (_i, [_i, _i, _i, _vp]),
+    'pm_eval_tiles_u8': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, POINTER(c_float), POINTER(c_float), _vp, _vp]),
     'pm_label_table_ids': (_i, [_vp, _vp, _i, _vp, c_int32]),
     'pm_label_table_colors': (_i, [_vp, _vp, _i, _i, _vp, c_int32]),
     'pm_labels_decode_u8': (_i, [_vp, _i, _i, _i, _i, _vp, _i, c_int32, _vp, _vp, _vp]),
