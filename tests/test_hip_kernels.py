@@ -772,7 +772,9 @@ def test_memory_read_pq_at_the_flagship_row_count(K):
 
 def test_memory_read_more_rows_than_resident_tiles(K):
     """> 98 304 rows: the 32-row tiles outnumber the launched blocks (3072), so every block walks several tiles (grid-stride path of the
-    MFMA read kernels, with a ragged last tile); forward and the dx-only backward against torch."""
+    MFMA read kernels, with a ragged last tile); forward and the dx-only backward against torch. Then read + p_query with a noise_q: the read kernel writes its
+    column partials from that grid-stride loop (3 081 tiles on the 3 072-block cap) and the apply kernel merges 3 081 > 768 = 32 x CSA_PER of them, which only
+    its re-reading branch does; p_query against fp64 at 2e-6, its columns sum to 1 within 1e-5, and mem_colsoftmax (771 partials of 128 rows) agrees at 2e-6."""
     n, h, w, d, m = 1, 317, 311, 256, 19                      # 98 587 rows = 3080 tiles + 27 rows
     x = torch.relu(rnd(n, d, h, w, seed=11))
     mem = F.normalize(rnd(m, d, seed=12), dim=1)
@@ -789,6 +791,15 @@ def test_memory_read_more_rows_than_resident_tiles(K):
     dx, _ = K.mem_read_bwd(xg, memg, pmem, dqr.view(n, h, w, 2 * d).cuda(), dsx.cuda())
     live = (x.abs().sum(1, keepdim=True) > 0).expand_as(x)   # rows that are all zero after the ReLU take the eps branch (torch: different sub-gradient)
     assert rel(nchw(dx)[live], xr.grad[live]) < 2e-5
+    # read + p_query on the same rows: the only place where the column partials are WRITTEN from the grid-stride loop (3 081 tiles on 3 072 blocks, colpart at
+    # tile = row0 >> 5) and MERGED by the branch of the apply kernel that re-reads its partials (ceil(3081 / 32) = 97 > 24 per thread). Same q / score / p_mem bits as
+    # the plain read; p_query against the fp64 softmax of the kernel's own score plus the noise (torch's fp32 softmax over 98 587 rows is itself 5.5e-4 off)
+    noise_q = (-torch.empty(n * h * w, m).exponential_(generator=torch.Generator().manual_seed(15)).log()).cuda()
+    qa, sa, pa, pq = K.mem_read_fwd_pq(xg, memg, None, noise_q)
+    assert torch.equal(qa, qr) and torch.equal(sa, score) and torch.equal(pa, pmem)
+    pq_ref = F.softmax(score.double().cpu() + noise_q.double().cpu(), 0)
+    assert rel(pq, pq_ref) < 2e-6 and abs(pq.double().sum(0) - 1).max().item() < 1e-5
+    assert rel(K.mem_colsoftmax(score, noise_q), pq_ref) < 2e-6      # 771 partials of 128 rows: the same branch
 
 
 def test_memory_write(K):
