@@ -53,8 +53,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * 420: pm_geo_image and the resampling input edge (pm_resample_tables, pm_resample_crop_u8), PM_RESAMPLE_MAX_TAPS.
  * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8).
  * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace).
- * 450: the evaluation input edge (pm_resize_axis_tables, pm_eval_tiles_u8), PM_FILTER_*. */
-#define PM_ABI_VERSION 450
+ * 450: the evaluation input edge (pm_resize_axis_tables, pm_eval_tiles_u8), PM_FILTER_*.
+ * 460: per-image normalisation of the IBN trunks (pm_instnorm_workspace, pm_instnorm_fwd, pm_instnorm_bwd). */
+#define PM_ABI_VERSION 460
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
   int32_t struct_size;          /* = sizeof(pm_conv_params) */
@@ -297,6 +298,27 @@ int pm_add_n(const pm_tensor* const* xs, int n, const pm_tensor* y, void* stream
 int pm_copy(const pm_tensor* src, const pm_tensor* dst, void* stream);
 int pm_scale_shift_act(const pm_tensor* x, const float* scale, const float* shift, const pm_tensor* residual, int relu,
                        const pm_tensor* y, void* stream);
+
+/* ---- K4b InstanceNorm2d (Resnet.py:162-167,412-417: nn.InstanceNorm2d(C, affine = False / True), eps 1e-5) of the IBN trunks -------------------------------------
+ * Per-(image, channel) statistics of an NHWC activation -- biased variance, no running moments, the same in train and eval mode -- as raw pointers plus
+ * pitches (ELEMENTS between consecutive pixels; images are h * w pixels apart), dtype PM_F32 or PM_BF16 for every tensor of a call. Statistics are shifted sums
+ * (shift = the first pixel of each image) in fp32 block partials, merged in double in a fixed order: no floating-point atomics, bit-identical from run to run. The
+ * bf16 instantiation yields the mean / invstd the fp32 one yields on the widened tensor, bit for bit. Three launches per call whatever n is.
+ *   fwd: y = (x - mean[n,c]) * invstd[n,c] * gamma[c] + beta[c], then max(., 0) if relu; mean / invstd: float[n][c] outputs. gamma and beta are both NULL
+ *        (affine = False) or both set. y may be x itself (same pitch); any other overlap of y's elements with x's is undefined (not checked: channel slices of one
+ *        slab interleave without overlapping).
+ *   bwd: g = dy * [y > 0] if relu (y is read only then, and may be NULL otherwise); per (n, c) s1 = sum g, s2 = sum g * xhat;
+ *        dx = gamma * invstd * (g - s1 / hw - xhat * s2 / hw); dgamma[c] = sum_n s2, dbeta[c] = sum_n s1 (fp32 [c], each nullable). gamma NULL: 1.
+ *   ws:  pm_instnorm_workspace(n, h, w, c) bytes (the same for both passes and dtypes; 0 for a non-positive size).
+ * Before anything touches the device -- PM_EINVAL: a null required pointer, a non-positive size, a pitch below c or not a multiple of the 16-byte vector width (4 fp32 /
+ * 8 bf16 elements), a tensor or parameter pointer that is not 16-byte aligned, exactly one of gamma / beta, y aliasing x with another pitch.
+ * PM_EUNSUPPORTED: an unknown dtype, c % 8 != 0. PM_EWORKSPACE: a workspace shorter than the query answers. */
+size_t pm_instnorm_workspace(int n, int h, int w, int c);
+int pm_instnorm_fwd(const void* x, void* y, int n, int h, int w, int c, int64_t x_pitch, int64_t y_pitch, int dtype, const float* gamma /*nullable*/,
+                    const float* beta /*nullable*/, float eps, int relu, float* mean, float* invstd, void* ws, size_t ws_bytes, void* stream);
+int pm_instnorm_bwd(const void* dy, const void* x, const void* y /*relu only*/, void* dx, int n, int h, int w, int c, int64_t dy_pitch, int64_t x_pitch, int64_t y_pitch,
+                    int64_t dx_pitch, int dtype, const float* gamma /*nullable*/, const float* mean, const float* invstd, int relu, float* dgamma /*nullable*/,
+                    float* dbeta /*nullable*/, void* ws, size_t ws_bytes, void* stream);
 
 /* dtype conversion between two views of the same shape (PM_F32 <-> PM_BF16, round to nearest even): the edges of the bf16 tier -- the memory module
  * (memory.py:167-239) and the losses stay fp32. Only the c channels of a pixel are written (pad lanes of a wider pitch are left alone). */

@@ -212,6 +212,30 @@ def agg_train_step(net, opt, x, gts, aux_gts=None, sched=None, buckets=None, tru
     return out
 
 
+def plain_train_step(net, opt, x, gts, aux_gts=None, sched=None, buckets=None):
+    """One iteration of train_agg (train.py:634-700, calculate_loss :213-244) for a network WITHOUT memory (the IBN-Net baseline, or the plain trunk): zero_grad,
+    the training forward, loss1 + 0.4 * loss2, backward, step. `buckets` (dist.GradBuckets) replaces DDP's reducer for N > 1. -> dict(loss1, loss2, total)."""
+    aux_gts = gts if aux_gts is None else aux_gts
+    m = net.module if hasattr(net, 'module') else net
+    assert not m.args.memory, 'plain_train_step serves networks without memory; agg_train_step runs the others'
+    set_mode(net, True)
+    if x.is_cuda and x.shape[1] == 3:
+        x = ops.nchw(K.nchw_to_nhwc(x.float(), c_pad=4))
+    if buckets is not None:
+        buckets.zero()
+    else:
+        opt.zero_grad()
+    outputs = net(x, gts=gts, aux_gts=aux_gts)
+    loss = outputs[0] + LOSS_W['aux'] * outputs[1]
+    loss.backward()
+    if buckets is not None:
+        buckets.finish()
+    opt.step()
+    if sched is not None:
+        sched.step()
+    return dict(loss1=outputs[0].detach(), loss2=outputs[1].detach(), total=loss.detach())
+
+
 class GraphedAggStep:
     """One agg train step (train forward + backward + SGD + memory-commit forward) captured in a hipGraph and replayed: ~1 300 kernel launches, their stream forks /
     joins and allocations become ONE graph launch per step. For the regime where the step is launch-bound -- the bf16 tier: 20 ms of Python + HIP enqueue per step

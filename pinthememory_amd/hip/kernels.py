@@ -564,6 +564,46 @@ def bn_bwd_apply(dy, y, x, mean, invstd, gamma, sums, count, relu, want_dres, be
     return dx, dres
 
 
+# ---- instance norm (the IBN trunks) ---------------------------------------------------------------------------------
+def _instnorm_ws(lib, x):
+    n, h, w, c = x.shape
+    nb = _sizes(('in', x.shape), lambda: lib.pm_instnorm_workspace(n, h, w, c))
+    return workspace(nb, x.device), nb
+
+
+def instnorm_fwd(x, gamma, beta, eps, relu=False, out=None):
+    """nn.InstanceNorm2d (+ ReLU) of an NHWC fp32 / bf16 view: per-(image, channel) statistics, biased variance -> (y, mean [n, c], invstd [n, c]). gamma / beta:
+    both None (affine=False) or both float[c]. out: the view to write (may be x itself); include/pinmem_hip.h pm_instnorm_fwd."""
+    d = tdesc(x)
+    y = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    yd = tdesc(y)
+    assert yd.dtype == d.dtype and tuple(y.shape) == tuple(x.shape), 'instnorm_fwd: out has the shape and dtype of x'
+    mean = torch.empty((d.n, d.c), dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    lib = _lib()
+    ws, nb = _instnorm_ws(lib, x)
+    check(lib.pm_instnorm_fwd(d.ptr, yd.ptr, d.n, d.h, d.w, d.c, d.pitch, yd.pitch, d.dtype, ptr(gamma), ptr(beta), float(eps), 1 if relu else 0, mean.data_ptr(),
+                              invstd.data_ptr(), ptr(ws), nb, stream()), 'pm_instnorm_fwd')
+    return y, mean, invstd
+
+
+def instnorm_bwd(dy, x, y, gamma, mean, invstd, relu=False, want_affine=True, out=None):
+    """Backward of instnorm_fwd -> (dx, dgamma, dbeta); y (the forward output) is read only when relu. dgamma / dbeta: float[c], or None when not wanted."""
+    d, gd = tdesc(x), tdesc(dy)
+    dx = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    xd = tdesc(dx)
+    yd = tdesc(y) if relu else None
+    assert gd.dtype == d.dtype == xd.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(dx.shape), 'instnorm_bwd: dy and dx have the shape and dtype of x'
+    assert yd is None or (yd.dtype == d.dtype and tuple(y.shape) == tuple(x.shape)), 'instnorm_bwd: y has the shape and dtype of x'
+    dgamma = torch.empty(d.c, dtype=torch.float32, device=x.device) if want_affine else None
+    dbeta = torch.empty_like(dgamma) if want_affine else None
+    lib = _lib()
+    ws, nb = _instnorm_ws(lib, x)
+    check(lib.pm_instnorm_bwd(gd.ptr, d.ptr, yd.ptr if yd else None, xd.ptr, d.n, d.h, d.w, d.c, gd.pitch, d.pitch, yd.pitch if yd else 0, xd.pitch, d.dtype, ptr(gamma),
+                              mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0, ptr(dgamma), ptr(dbeta), ptr(ws), nb, stream()), 'pm_instnorm_bwd')
+    return dx, dgamma, dbeta
+
+
 def relu_bwd(dy, y):
     dx = torch.empty(y.shape, dtype=torch.float32, device=y.device)
     check(_lib().pm_relu_bwd(byref(tdesc(dy)), byref(tdesc(y)), byref(tdesc(dx)), stream()), 'pm_relu_bwd')

@@ -77,7 +77,7 @@ def conv_epilogue(*fields):
     return PmConvEpilogue(ctypes.sizeof(PmConvEpilogue), *fields)
 
 
-ABI_VERSION = 450         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
+ABI_VERSION = 460         # include/pinmem_hip.h PM_ABI_VERSION this binding was written against
 
 
 class PinmemError(RuntimeError):
@@ -213,6 +213,9 @@ SIGNATURES = {
     'pm_sgd_momentum_multi': (_i, [_vp, _i, _f, _f, _f, _vp]),
     'pm_sgd_momentum_multi_dev': (_i, [_vp, _i, _f, _vp, _f, _f, _vp]),
     'pm_cast': (_i, [_T, _T, _vp]),
+    'pm_instnorm_workspace': (_sz, [_i, _i, _i, _i]),
+    'pm_instnorm_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pm_instnorm_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -615,6 +615,25 @@ class _Conv(torch.autograd.Function):
         return dx, dwk.permute(0, 3, 1, 2), db, None
 
 
+class _InstNormAct(torch.autograd.Function):
+    """nn.InstanceNorm2d(affine = weight is not None) -> ReLU: the tail of an IBN Bottleneck (Resnet.py:205-214: out += residual; out = instance_norm_layer(out);
+    relu) and the IBN stem's bn1 + relu (Resnet.py:471-477). Per-image statistics in train and eval mode alike; no running moments, no cross-rank exchange."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, relu):
+        xv = _grad_view(x)
+        o, mean, invstd = K.instnorm_fwd(xv, weight, bias, eps, relu)
+        ctx.relu, ctx.affine = relu, weight is not None
+        ctx.save_for_backward(xv, o if relu else None, weight, mean, invstd)
+        return nchw(o)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xv, o, weight, mean, invstd = ctx.saved_tensors
+        dx, dgamma, dbeta = K.instnorm_bwd(_grad_view(dout), xv, o, weight, mean, invstd, ctx.relu, want_affine=ctx.affine)
+        return nchw(dx), dgamma, dbeta, None, None
+
+
 class _MaxPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -830,6 +849,18 @@ def conv(x, conv_mod):
 
 def conv_raw(x, weight, bias, geom):
     return _Conv.apply(x, weight, bias, geom)
+
+
+def instance_norm_act(x, weight, bias, eps=1e-5, relu=True):
+    """relu?(instance_norm(x) * weight + bias); weight / bias: both None (nn.InstanceNorm2d(affine=False)) or both parameters."""
+    assert (weight is None) == (bias is None), 'instance_norm_act: weight and bias come together'
+    return _InstNormAct.apply(x, weight, bias, float(eps), bool(relu))
+
+
+def instance_norm_module(x, m, relu=True):
+    """nn.InstanceNorm2d module `m` (no running statistics: the reference never asks for them) applied to x, then ReLU."""
+    assert isinstance(m, torch.nn.InstanceNorm2d) and not m.track_running_stats, 'instance norm with running statistics is not served'
+    return instance_norm_act(x, m.weight, m.bias, m.eps, relu)
 
 
 def maxpool3x3s2(x):

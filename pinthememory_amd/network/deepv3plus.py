@@ -178,7 +178,8 @@ class DeepV3Plus(_Base):
     def __init__(self, num_classes, trunk='resnet-101', criterion=None, criterion_aux=None, variant='D', skip='m1', skip_num=48, args=None):
         super().__init__()
         self.criterion, self.criterion_aux, self.variant, self.args, self.trunk = criterion, criterion_aux, variant, args, trunk
-        assert all(v == 0 for v in args.wt_layer) and not args.use_wtloss, 'whitening is out of scope of the pinmem hot path'
+        Resnet.check_wt_layer(args.wt_layer)           # 0, 3, 4 (plain and IBN trunks); the assertion names what is not served
+        assert not args.use_wtloss, 'whitening is out of scope of the pinmem hot path'
         if trunk != 'resnet-50':
             raise ValueError("Not a valid network arch")   # other trunks (and the reference's broken R101-V3+) are out of scope
         self._adopt_trunk(trunk)
