@@ -1,64 +1,21 @@
 // K4: BatchNorm2d over NHWC activations of both tiers (train statistics, apply + ReLU + residual, backward), HBM-bound.
-// Replaces mynn.Norm2d (/root/reference/network/mynn.py:8-14) == nn.BatchNorm2d / SyncBatchNorm everywhere it is
-// used (Resnet.py:146-151,405,456; deepv3plus.py:73,79,88,399,405,410,413,421; memory.py:76,105).
+// Replaces mynn.Norm2d (the reference's network/mynn.py:8-14) == nn.BatchNorm2d / SyncBatchNorm everywhere it is
+// used (Resnet.py:146-151,429,456; deepv3plus.py:73,79,88,399,405,410,413,421; memory.py:76,105).
 // Statistics are shifted sums (shift = first pixel of each channel) -> (mean, M2, count), combined in double in a
 // fixed order: one pass over the activation, no catastrophic cancellation, deterministic, mergeable across ranks.
-// One body per piece for fp32 and bf16 tensors: a lane moves 16 bytes (pm_elem<T>::V channels), values are widened to fp32 in registers and travel as float[V];
-// every statistic / reduction / accumulator is fp32 (second stages in double); bf16 results are rounded (nearest even) once, on the way out.
-#include <type_traits>
-
-#include "pm_common.h"
+// The reductions, the mask helpers, the dx expression and the fixed-group elementwise driver are norm_parts.h's, shared with instnorm.hip: BatchNorm runs them
+// with one image of P pixels. Its own: the plan, the finishes (float, running moments, the moments exchange format, slab partials, the rank merge), the folds and
+// the functors of its bf16 elementwise passes.
+#include "norm_parts.h"
 
 namespace {
 
-// ---- elementwise expressions ----------------------------------------------------------------------------------------------------------
-// y = (x - mean) * invstd * gamma + beta, evaluated the same way in the forward pass and wherever the backward pass rebuilds the
-// ReLU mask from x (two explicit FMAs: bit-identical in both places whatever the compiler would contract).
-template <int V>
-__device__ __forceinline__ void bn_affine(const float* v, const float* mu, const float* is, const float* ga, const float* be, float* o) {
-#pragma unroll
-  for (int j = 0; j < V; ++j) o[j] = pm_bn_affine(v[j], mu[j], is[j], ga[j], be[j]);
-}
-// the ReLU passes g where the activation o was positive (o: the forward output, or bn_affine of x)
-template <int V>
-__device__ __forceinline__ void relu_mask(const float* o, float* g) {
-#pragma unroll
-  for (int j = 0; j < V; ++j) g[j] = o[j] > 0.f ? g[j] : 0.f;
-}
-// ... or where bit j of the byte bn_apply left for the group is set (positive_bits)
-template <int V>
-__device__ __forceinline__ void relu_mask_bits(unsigned mb, float* g) {
-#pragma unroll
-  for (int j = 0; j < V; ++j) g[j] = ((mb >> j) & 1u) ? g[j] : 0.f;
-}
-template <int V>
-__device__ __forceinline__ unsigned positive_bits(const float* o) {
-  unsigned m = 0;
-#pragma unroll
-  for (int j = 0; j < V; ++j) m |= o[j] > 0.f ? (1u << j) : 0u;
-  return m;
-}
-template <int V>
-__device__ __forceinline__ void relu(float* o) {
-#pragma unroll
-  for (int j = 0; j < V; ++j) o[j] = fmaxf(o[j], 0.f);
-}
 // count <= 0 on the host: the element count lives on the device at sums[2 * C] -- SyncBatchNorm all-reduces it with the two sums, so ranks with
 // different batch sizes normalise by the true global count (torch.nn.SyncBatchNorm gathers the counts the same way)
 __device__ __forceinline__ float bn_inv_n(bool dev_count, const float* sums, int C, float host_inv_n) { return dev_count ? 1.f / sums[2 * C] : host_inv_n; }
-// dx = (g - sum(g) / n - xhat * sum(g xhat) / n) * invstd * gamma, with k1 = s1 * inv_n, k2 = s2 * inv_n, sg = is * ga -- hoisted by the caller or written in place.
-// A macro: as a function the three products are evaluated before the rest, and that order alone costs the bf16 generic pass two VGPRs (64 against 62).
-#define BN_DX(g, v, mu, is, k1, k2, sg) (((g) - (k1) - ((v) - (mu)) * (is) * (k2)) * (sg))
-
 // ---- reductions -------------------------------------------------------------------------------------------------------------------------
-// GPR lane groups per pixel row, RL = 256 / GPR row lanes, CB channels per block
-template <int V, int GPR>
-struct Geo {
-  static constexpr int RL = 256 / GPR, CB = GPR * V;
-};
-struct Plan {
-  int gpr, rows, nb, colblocks;      // rows: pixels per block: >= 2048 blocks over (pixel chunks x channel groups), >= 64 rows each
-};
+// 256-thread blocks: RL = 256 / GPR row lanes, GPR from the element type (pm_elem<T>::gpr) -- the bf16 maps of <= 64 channels would idle half-waves at 16.
+// rows: pixels per block: >= 2048 blocks over (pixel chunks x channel groups), >= 64 rows each
 template <typename T>
 Plan bn_plan(long P, int C) {
   Plan p;
@@ -72,83 +29,11 @@ Plan bn_plan(long P, int C) {
   return p;
 }
 template <typename T>
+constexpr int MIN_GPR = pm_elem<T>::V == 8 ? 8 : 16;      // pm_elem<float>::gpr is always 16
+template <typename T>
 size_t bn_workspace(const pm_tensor* x) {
   return pm_align_up((size_t)bn_plan<T>(pm_pixels(x), x->c).nb * x->c * 2 * sizeof(float), 256);
 }
-// launch(integral_constant<int, GPR>) for the plan's GPR
-template <typename T, typename L>
-void with_gpr(int gpr, L launch) {
-  if constexpr (pm_elem<T>::V == 8) {
-    if (gpr == 8) return launch(std::integral_constant<int, 8>{});
-  }
-  launch(std::integral_constant<int, 16>{});
-}
-
-// block-level reduce of per-thread (s1[V], s2[V]) over the row lanes, in row-lane order -> part[blk][c][2]
-template <int V, int GPR>
-__device__ __forceinline__ void block_reduce_store(const float* s1, const float* s2, int g, int r, int C, float* __restrict__ part) {
-  constexpr int RL = Geo<V, GPR>::RL, CB = Geo<V, GPR>::CB;
-  __shared__ float sm[RL][CB][2];
-#pragma unroll
-  for (int j = 0; j < V; ++j) sm[r][g * V + j][0] = s1[j], sm[r][g * V + j][1] = s2[j];
-  __syncthreads();
-  if (threadIdx.x < CB * 2) {
-    const int cc = threadIdx.x >> 1, w = threadIdx.x & 1;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < RL; ++i) s += sm[i][cc][w];
-    const int ch = blockIdx.y * CB + cc;
-    if (ch < C) part[((long)blockIdx.x * C + ch) * 2 + w] = s;
-  }
-}
-
-// partial[blk][c][2] : sum(x - K[c]), sum((x - K[c])^2) over the block's pixel chunk, K = the first pixel (shifted sums: no cancellation)
-template <typename T, int GPR>
-__global__ __launch_bounds__(256) void bn_stats_partial(const T* __restrict__ x, long pitch, long P, int C, int rows, float* __restrict__ part) {
-  constexpr int V = pm_elem<T>::V;
-  const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
-  const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
-  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
-  float s1[V], s2[V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
-  if (c < C) {
-    float k[V];
-    pm_elem<T>::ld(x + c, k);
-    for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
-      float v[V];
-      pm_elem<T>::ld(x + p * pitch + c, v);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float d = v[j] - k[j];
-        s1[j] += d, s2[j] += d * d;
-      }
-    }
-  }
-  block_reduce_store<V, GPR>(s1, s2, g, r, C, part);
-}
-
-// Second stage: 4 channels x 64 lanes per block; each lane sums a strided subset of the block partials in double, the 64
-// lane sums are combined in fixed order (deterministic; a 512-long serial chain per channel would cost ~100 us of pure latency).
-constexpr int FC = 4, FL = 64;
-__device__ __forceinline__ void final_sums(const float* __restrict__ part, int nb, int C, int c, int lane, double& s1, double& s2) {
-  __shared__ double red[FL][FC][2];
-  double a = 0.0, b = 0.0;
-  if (c < C)
-#pragma unroll 8   // eight independent partial loads in flight per lane (the additions keep their order)
-    for (int i = lane; i < nb; i += FL) {
-      const float2 v = *reinterpret_cast<const float2*>(part + ((long)i * C + c) * 2);
-      a += (double)v.x, b += (double)v.y;
-    }
-  red[lane][threadIdx.x & (FC - 1)][0] = a, red[lane][threadIdx.x & (FC - 1)][1] = b;
-  __syncthreads();
-  s1 = s2 = 0.0;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < FL; ++i) s1 += red[i][threadIdx.x & (FC - 1)][0], s2 += red[i][threadIdx.x & (FC - 1)][1];
-  }
-}
-
 // The tail of every statistics kernel: channel c's (mean m, M2 m2, count n) leave as moments (mean | M2 | count, the SyncBatchNorm exchange format), or (FIN) as
 // mean / invstd plus the running-moment update, on the same float values the moments would hand over (bit-identical), one launch less per BN layer.
 template <bool FIN>
@@ -220,12 +105,6 @@ __global__ __launch_bounds__(256) void bn_partials_final(const float* __restrict
 // The incoming gradient of a backward pass: a tensor, or (the stem) what pm_maxpool3x3s2_bwd would have written, gathered per pixel from the gradient of the
 // 3x3 / s2 max pool that followed the activation and its argmax bytes (pm_maxpool_gather: the same values in the same order), so that the full-resolution
 // gradient is never written.
-template <typename T>
-struct TensorGrad {
-  const T* dy;
-  long pitch;
-  __device__ __forceinline__ void load(long p, int c, float* d) const { pm_elem<T>::ld(dy + p * pitch + c, d); }
-};
 struct PoolGrad {
   const float* dyp;
   long pitch;
@@ -237,46 +116,6 @@ struct PoolGrad {
   }
 };
 
-// backward reductions: partial[blk][c][2] = sum(dyz), sum(dyz * xhat), dyz = dy masked by the ReLU of the forward pass.
-// RELU 0: no activation. 1: mask = y > 0 read from the forward output (needed when a residual was added before the ReLU).
-// 2: mask rebuilt from x (y = relu(bn(x)), no residual) -- one tensor less to read.
-// 3: mask from the byte per 16-byte group bn_apply left behind (bit e = output e of the group was positive): 1 / 16 of the bytes of reading y.
-// GOUT: also store dyz (the gradient of the residual branch), so that the apply pass reads one tensor (dyz) instead of two (dy, y).
-template <typename T, int GPR, int RELU, bool GOUT, typename SRC>
-__global__ __launch_bounds__(256) void bn_bwd_partial(SRC dy, const T* __restrict__ y, long ypitch, const uint8_t* __restrict__ mask, const T* __restrict__ x, long xpitch,
-                                                      const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, T* __restrict__ gout, long gpitch, long P, int C, int rows, float* __restrict__ part) {
-  constexpr int V = pm_elem<T>::V;
-  const int g = threadIdx.x % GPR, r = threadIdx.x / GPR;
-  const int c = blockIdx.y * Geo<V, GPR>::CB + g * V;
-  const long p0 = (long)blockIdx.x * rows, p1 = min(P, p0 + rows);
-  float s1[V], s2[V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
-  if (c < C) {
-    float mu[V], is[V], ga[V], be[V];
-    pm_ldp<V>(mean + c, mu), pm_ldp<V>(invstd + c, is);
-    if (RELU == 2) pm_ldp<V>(gamma + c, ga), pm_ldp<V>(beta + c, be);
-    for (long p = p0 + r; p < p1; p += Geo<V, GPR>::RL) {
-      float d[V], v[V], o[V];
-      dy.load(p, c, d);
-      pm_elem<T>::ld(x + p * xpitch + c, v);
-      if (RELU == 1) {
-        pm_elem<T>::ld(y + p * ypitch + c, o);
-        relu_mask<V>(o, d);
-      } else if (RELU == 3) {
-        relu_mask_bits<V>(mask[p * (C / V) + c / V], d);
-      } else if (RELU == 2) {
-        bn_affine<V>(v, mu, is, ga, be, o);
-        relu_mask<V>(o, d);
-      }
-      if (GOUT) pm_elem<T>::st(gout + p * gpitch + c, d);
-#pragma unroll
-      for (int j = 0; j < V; ++j) s1[j] += d[j], s2[j] += d[j] * ((v[j] - mu[j]) * is[j]);
-    }
-  }
-  block_reduce_store<V, GPR>(s1, s2, g, r, C, part);
-}
 __global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ part, int nb, int C, float* __restrict__ sums) {
   const int c = blockIdx.x * FC + (threadIdx.x & (FC - 1)), lane = threadIdx.x / FC;
   double s1, s2;
@@ -331,62 +170,83 @@ __global__ void bn_fold_kernel(const float* __restrict__ g, const float* __restr
   shift[c] = b[c] - rm[c] * s + (cb ? cb[c] * s : 0.f);
 }
 
-// ---- the bf16 elementwise passes with the per-channel constants in REGISTERS --------------------------------------------------------------
-// thread = one 8-channel group (fixed) x a strided set of pixels. The generic driver re-loads mean / invstd / gamma / beta (/ sums) -- 128-192 bytes of L1
-// traffic -- for every 16-byte group of activations it moves, which held these passes at 4.0-4.4 TB/s where their fp32 twins reach 5.6 (twice the tensor bytes
-// per parameter load). Taken when the channel groups divide the block (C = 64 ... 2048).
+// ---- the bf16 elementwise passes on the fixed-group driver (norm_parts.h), one image ------------------------------------------------------------------------
+// Only the bf16 tier: the fp32 passes stay on pm_ew_launch_as, where they reach 5.6 TB/s. Taken when the channel groups divide the block (C = 64 ... 2048).
 constexpr int V8 = 8;
 template <bool RES, bool MASK, bool RELU>
-__global__ __launch_bounds__(256) void bn16_apply_fixed_kernel(const pm_bf16* __restrict__ x, long xp, const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                               const float* __restrict__ gamma, const float* __restrict__ beta, const pm_bf16* __restrict__ res, long rp,
-                                                               pm_bf16* __restrict__ y, long yp, uint8_t* __restrict__ mask, long pixels, int cg) {
-  const int grp = threadIdx.x % cg, pl = threadIdx.x / cg, ppb = 256 / cg, ch = grp * V8;
-  float sc[V8], sh[V8];
-  {
+struct Bn16Apply {
+  static constexpr int V = V8;
+  static constexpr bool BATCH = false;
+  const pm_bf16* __restrict__ x;
+  long xp;
+  const float *__restrict__ mean, *__restrict__ invstd, *__restrict__ gamma, *__restrict__ beta;
+  const pm_bf16* __restrict__ res;
+  long rp;
+  pm_bf16* __restrict__ y;
+  long yp;
+  uint8_t* __restrict__ mask;
+  int cg;
+  struct K {
+    float sc[V8], sh[V8];
+  };
+  __device__ __forceinline__ void load(long, int ch, K& k) const {
     float mu[V8], is[V8], ga[V8], be[V8];
     pm_ld8f(mean + ch, mu), pm_ld8f(invstd + ch, is), pm_ld8f(gamma + ch, ga), pm_ld8f(beta + ch, be);
 #pragma unroll
-    for (int e = 0; e < V8; ++e) sc[e] = is[e] * ga[e], sh[e] = fmaf(-mu[e], sc[e], be[e]);      // pm_bn_affine(v) == fmaf(v, sc, sh): the same two FMAs
+    for (int e = 0; e < V8; ++e) k.sc[e] = is[e] * ga[e], k.sh[e] = fmaf(-mu[e], k.sc[e], be[e]);      // pm_bn_affine(v) == fmaf(v, sc, sh): the same two FMAs
   }
-  for (long p = (long)blockIdx.x * ppb + pl; p < pixels; p += (long)gridDim.x * ppb) {
+  __device__ __forceinline__ void pixel(long p, int ch, const K& k) const {
     float v[V8], o[V8];
     pm_ld8(x + p * xp + ch, v);
 #pragma unroll
-    for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], sc[e], sh[e]);
+    for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], k.sc[e], k.sh[e]);
     if constexpr (RES) {
       float q[V8];
       pm_ld8(res + p * rp + ch, q);
 #pragma unroll
       for (int e = 0; e < V8; ++e) o[e] += q[e];
     }
-    if constexpr (MASK) mask[p * cg + grp] = (unsigned char)positive_bits<V8>(o);
+    if constexpr (MASK) mask[p * cg + ch / V8] = (unsigned char)positive_bits<V8>(o);
     if constexpr (RELU) relu<V8>(o);
     pm_st8(y + p * yp + ch, o);
   }
-}
+};
 
 // MODE 0: no ReLU (dy is already the masked gradient); 1: mask = forward output > 0; 2: mask rebuilt from x
 template <int MODE, bool DRES>
-__global__ __launch_bounds__(256) void bn16_bwd_apply_fixed_kernel(const pm_bf16* __restrict__ dy, long dp, const pm_bf16* __restrict__ yo, long op, const pm_bf16* __restrict__ x,
-                                                                   long xp, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ beta, const float* __restrict__ sums, float host_inv_n, int dev_count, int C,
-                                                                   pm_bf16* __restrict__ dx, long dxp, pm_bf16* __restrict__ dres, long drp, long pixels, int cg) {
-  const int grp = threadIdx.x % cg, pl = threadIdx.x / cg, ppb = 256 / cg, ch = grp * V8;
-  float mu[V8], is[V8], k1[V8], k2[V8], sg[V8], sc[V8], sh[V8];
-  {
+struct Bn16BwdApply {
+  static constexpr int V = V8;
+  static constexpr bool BATCH = false;
+  const pm_bf16* __restrict__ dy;
+  long dp;
+  const pm_bf16* __restrict__ yo;
+  long op;
+  const pm_bf16* __restrict__ x;
+  long xp;
+  const float *__restrict__ mean, *__restrict__ invstd, *__restrict__ gamma, *__restrict__ beta, *__restrict__ sums;
+  float host_inv_n;
+  int dev_count, C;
+  pm_bf16* __restrict__ dx;
+  long dxp;
+  pm_bf16* __restrict__ dres;
+  long drp;
+  struct K {
+    float mu[V8], is[V8], k1[V8], k2[V8], sg[V8], sh[V8];
+  };
+  __device__ __forceinline__ void load(long, int ch, K& k) const {
     const float inv_n = bn_inv_n(dev_count, sums, C, host_inv_n);
     float ga[V8], s1[V8], s2[V8];
-    pm_ld8f(mean + ch, mu), pm_ld8f(invstd + ch, is), pm_ld8f(gamma + ch, ga), pm_ld8f(sums + ch, s1), pm_ld8f(sums + C + ch, s2);
+    pm_ld8f(mean + ch, k.mu), pm_ld8f(invstd + ch, k.is), pm_ld8f(gamma + ch, ga), pm_ld8f(sums + ch, s1), pm_ld8f(sums + C + ch, s2);
 #pragma unroll
-    for (int e = 0; e < V8; ++e) k1[e] = s1[e] * inv_n, k2[e] = s2[e] * inv_n, sg[e] = is[e] * ga[e];
+    for (int e = 0; e < V8; ++e) k.k1[e] = s1[e] * inv_n, k.k2[e] = s2[e] * inv_n, k.sg[e] = k.is[e] * ga[e];
     if constexpr (MODE == 2) {
       float be[V8];
       pm_ld8f(beta + ch, be);
 #pragma unroll
-      for (int e = 0; e < V8; ++e) sc[e] = sg[e], sh[e] = fmaf(-mu[e], sg[e], be[e]);
+      for (int e = 0; e < V8; ++e) k.sh[e] = fmaf(-k.mu[e], k.sg[e], be[e]);      // the forward pass's scale is sg
     }
   }
-  for (long p = (long)blockIdx.x * ppb + pl; p < pixels; p += (long)gridDim.x * ppb) {
+  __device__ __forceinline__ void pixel(long p, int ch, const K& k) const {
     float g[V8], v[V8], o[V8], r[V8];
     pm_ld8(dy + p * dp + ch, g);
     pm_ld8(x + p * xp + ch, v);
@@ -396,17 +256,21 @@ __global__ __launch_bounds__(256) void bn16_bwd_apply_fixed_kernel(const pm_bf16
     }
     if constexpr (MODE == 2) {
 #pragma unroll
-      for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], sc[e], sh[e]);
+      for (int e = 0; e < V8; ++e) o[e] = fmaf(v[e], k.sg[e], k.sh[e]);
       relu_mask<V8>(o, g);
     }
     if constexpr (DRES) pm_st8(dres + p * drp + ch, g);
 #pragma unroll
-    for (int e = 0; e < V8; ++e) r[e] = BN_DX(g[e], v[e], mu[e], is[e], k1[e], k2[e], sg[e]);      // the generic kernel's expression, constants hoisted
+    for (int e = 0; e < V8; ++e) r[e] = BN_DX(g[e], v[e], k.mu[e], k.is[e], k.k1[e], k.k2[e], k.sg[e]);      // the generic kernel's expression, constants hoisted
     pm_st8(dx + p * dxp + ch, r);
   }
+};
+// one image of P pixels on the fixed driver: ew_bpi(1, ...) blocks
+template <typename F>
+void bn16_launch_fixed(const F& f, long P, int cg, hipStream_t st) {
+  const int bpi = ew_bpi(1, P, cg, true);
+  hipLaunchKernelGGL((norm_ew_kernel<true, F>), dim3(bpi), dim3(256), 0, st, f, P, cg, bpi);
 }
-inline bool fixed_ok(int c) { const int cg = c / V8; return c % V8 == 0 && cg >= 1 && cg <= 256 && 256 % cg == 0; }
-inline int fixed_grid(long pixels, int c) { const int ppb = 256 / (c / V8); return (int)std::min<long>((pixels + ppb - 1) / ppb, 256 * 16); }
 
 // ---- host side: one function per pass, both element types ------------------------------------------------------------------------------------
 #define BN_BY_DTYPE(x, f, ...) (pm_is_bf16(x) ? f<pm_bf16>(__VA_ARGS__) : f<float>(__VA_ARGS__))
@@ -424,8 +288,9 @@ int bn_stats(const char* who, const pm_tensor* x, float* moments, float eps, flo
   PM_REQUIRE(moments || P > 1, PM_EINVAL, "%s: expected more than 1 value per channel when training, got %ld", who, P);
   const Plan pl = bn_plan<T>(P, C);
   const T* px = (const T*)x->ptr;
-  with_gpr<T>(pl.gpr, [&](auto G) {
-    hipLaunchKernelGGL((bn_stats_partial<T, decltype(G)::value>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, px, (long)x->pitch, P, C, pl.rows, (float*)ws);
+  with_gpr<MIN_GPR<T>>(pl.gpr, [&](auto G) {
+    constexpr int GPR = decltype(G)::value;
+    hipLaunchKernelGGL((norm_stats_partial<T, GPR, 256 / GPR, false>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, px, (long)x->pitch, P, C, pl.rows, pl.nb, (float*)ws);
   });
   if (moments)
     hipLaunchKernelGGL((bn_stats_final<T, false>), dim3(pm_cdiv(C, FC)), dim3(256), 0, st, (const float*)ws, pl.nb, px, P, C, moments, 0.f, (float*)nullptr,
@@ -456,18 +321,14 @@ int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float
   const long a = x->pitch, b = res ? res->pitch : 0, c = y->pitch, P = pm_pixels(x);
   const int cg = x->c / V;
   if constexpr (V == V8) {
-    if (fixed_ok(x->c) && P > 0) {
-      const dim3 grid(fixed_grid(P, x->c));
-#define BN16_APPLY(R, M, L) hipLaunchKernelGGL((bn16_apply_fixed_kernel<R, M, L>), grid, dim3(256), 0, st, px, a, mean, invstd, gamma, beta, pr, b, py, c, mask, P, cg)
-      if (pr && mask && relu_on) BN16_APPLY(true, true, true);
-      else if (pr && relu_on) BN16_APPLY(true, false, true);
-      else if (pr && mask) BN16_APPLY(true, true, false);
-      else if (pr) BN16_APPLY(true, false, false);
-      else if (mask && relu_on) BN16_APPLY(false, true, true);
-      else if (relu_on) BN16_APPLY(false, false, true);
-      else if (mask) BN16_APPLY(false, true, false);
-      else BN16_APPLY(false, false, false);
-#undef BN16_APPLY
+    if (x->c % V8 == 0 && fixed_ok(cg) && P > 0) {
+      with_flag(pr != nullptr, [&](auto R) {
+        with_flag(mask != nullptr, [&](auto M) {
+          with_flag(relu_on != 0, [&](auto L) {
+            bn16_launch_fixed(Bn16Apply<decltype(R)::value, decltype(M)::value, decltype(L)::value>{px, a, mean, invstd, gamma, beta, pr, b, py, c, mask, cg}, P, cg, st);
+          });
+        });
+      });
       return pm_check_launch(who);
     }
   }
@@ -493,7 +354,7 @@ int bn_apply(const char* who, const pm_tensor* x, const float* mean, const float
   });
 }
 
-// dy: the incoming gradient (its own checks are the caller's). relu 0 ... 3 as bn_bwd_partial; the pooled gradient always takes mode 2 without gmask.
+// dy: the incoming gradient (its own checks are the caller's). relu 0 ... 3 as norm_bwd_partial; the pooled gradient always takes mode 2 without gmask.
 template <typename T, typename SRC>
 int bn_bwd_reduce(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mask, const pm_tensor* x, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, int relu_mode, const pm_tensor* gmask, float* sums, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -511,10 +372,11 @@ int bn_bwd_reduce(const char* who, SRC dy, const pm_tensor* y, const uint8_t* ma
   const T *py = relu_mode == 1 ? (const T*)y->ptr : nullptr, *px = (const T*)x->ptr;
   const long yp = relu_mode == 1 ? y->pitch : 0, gp = gmask ? gmask->pitch : 0;
   T* pg = gmask ? (T*)gmask->ptr : nullptr;
-  with_gpr<T>(pl.gpr, [&](auto G) {
+  with_gpr<MIN_GPR<T>>(pl.gpr, [&](auto G) {
+    constexpr int GPR = decltype(G)::value;
     auto go = [&](auto R, auto O) {
-      hipLaunchKernelGGL((bn_bwd_partial<T, decltype(G)::value, decltype(R)::value, decltype(O)::value, SRC>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, dy, py, yp, mask, px, (long)x->pitch, mean, invstd, gamma,
-                         beta, pg, gp, P, C, pl.rows, (float*)ws);
+      hipLaunchKernelGGL((norm_bwd_partial<T, GPR, 256 / GPR, false, decltype(R)::value, decltype(O)::value, SRC>), dim3(pl.nb, pl.colblocks), dim3(256), 0, st, dy, py, yp,
+                         mask, px, (long)x->pitch, mean, invstd, gamma, beta, pg, gp, P, C, pl.rows, pl.nb, (float*)ws);
     };
     using std::false_type;
     using std::true_type;
@@ -553,15 +415,17 @@ int bn_bwd_apply(const char* who, SRC dy, const pm_tensor* y, const uint8_t* mas
   const bool dev_count = !(count > 0.f), from_x = relu_mode == 2;
   const float host_inv_n = dev_count ? 0.f : 1.f / count;
   if constexpr (V == V8 && MODE < 0) {
-    if (fixed_ok(C) && P > 0) {
-      const dim3 grid(fixed_grid(P, C));
-#define BN16_BAPPLY(M, D)                                                                                                                                             \
-  hipLaunchKernelGGL((bn16_bwd_apply_fixed_kernel<M, D>), grid, dim3(256), 0, st, dy.dy, dy.pitch, po, b, px, c, mean, invstd, gamma, beta, sums, host_inv_n, dev_count ? 1 : 0, \
-                     C, pdx, d, pdr, e2, P, cg)
-      if (relu_mode == 0) { if (pdr) BN16_BAPPLY(0, true); else BN16_BAPPLY(0, false); }
-      else if (relu_mode == 1) { if (pdr) BN16_BAPPLY(1, true); else BN16_BAPPLY(1, false); }
-      else { if (pdr) BN16_BAPPLY(2, true); else BN16_BAPPLY(2, false); }
-#undef BN16_BAPPLY
+    if (C % V8 == 0 && fixed_ok(cg) && P > 0) {
+      auto go = [&](auto M) {
+        with_flag(pdr != nullptr, [&](auto D) {
+          bn16_launch_fixed(Bn16BwdApply<decltype(M)::value, decltype(D)::value>{dy.dy, dy.pitch, po, b, px, c, mean, invstd, gamma, beta, sums, host_inv_n, dev_count ? 1 : 0, C,
+                                                                                 pdx, d, pdr, e2},
+                            P, cg, st);
+        });
+      };
+      if (relu_mode == 0) go(std::integral_constant<int, 0>{});
+      else if (relu_mode == 1) go(std::integral_constant<int, 1>{});
+      else go(std::integral_constant<int, 2>{});
       return pm_check_launch(who);
     }
   }
