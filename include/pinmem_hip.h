@@ -54,7 +54,9 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * 430: pm_label_table and the label-decoding input edge (pm_label_table_ids, pm_label_table_colors, pm_labels_decode_u8, pm_resample_crop_decode_u8).
  * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace).
  * 450: the evaluation input edge (pm_resize_axis_tables, pm_eval_tiles_u8), PM_FILTER_*.
- * 460: per-image normalisation of the IBN trunks (pm_instnorm_workspace, pm_instnorm_fwd, pm_instnorm_bwd). */
+ * 460: per-image normalisation of the IBN trunks (pm_instnorm_workspace, pm_instnorm_fwd, pm_instnorm_bwd).
+ * The ablation sweep (pm_label_splat, pm_class_sums_workspace, pm_class_sums, pm_mem_actmap) arrived WITHOUT a version step: the number tracks the layouts of the
+ * structs above, those entry points take raw pointers and sizes only and no struct changed; a caller finds out whether a library has them by looking the symbols up. */
 #define PM_ABI_VERSION 460
 
 typedef struct pm_conv_params { /* nn.Conv2d geometry (square kernels/strides as used by the reference) */
@@ -384,6 +386,38 @@ int pm_sliding_eval(const float* logits, int n, int h, int w, int C, int64_t pit
                     double* acc /*nullable*/, int acc_add, void* ws, size_t ws_bytes, void* stream);
 int pm_sliding_eval_finish(const double* acc, int C, int H, int W, int nscales, const int64_t* labels /*nullable*/, int64_t* hist, int accumulate,
                            uint8_t* pred /*nullable*/, double* logits_out /*nullable*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- ablation sweep (ablation.py:292-399 RunAbla.tsne_memact, tsnelib.py:48-74 RunTsne.input2basket; csrc/ablation.hip) ------------------------------------------
+ * The per-class feature sums behind the t-SNE prototypes and the memory activation maps, from LOW-RES tensors: neither the up-sampled feature map ([256][H][W]) nor the
+ * one-hot of the labels ([H W][20]) nor the up-sampled scores are written. Raw pointers, sizes, pitches in ELEMENTS; bilinear arithmetic = align_corners=True with the
+ * coordinates and weights of pm_resize_bilinear_fwd. No floating-point atomics: bit-identical from run to run, independent of the grid.
+ *   pm_label_splat: labels int64 [n][H][W] -> splat float [n][h][w][classes + 1] and counts int64 [n][classes + 1]. Label 255 goes to row `classes` (tsnelib.py:54
+ *     gt[gt == 255] = num_class), a value in 0 .. classes - 1 to its own row, ANY OTHER value is skipped as pm_upsample_eval skips it (the reference's F.one_hot raises
+ *     there). splat[n][i][j][k] = sum over the full-res pixels of row k of the weight with which low-res pixel (i, j) enters that pixel's interpolation (the labels
+ *     pushed through the transpose of the up-sampling; a gather per low-res cell over its support, in a fixed order); counts = exact pixel counts. classes <= 31.
+ *   pm_class_sums: feat NHWC [n][h][w] pixels of c channels (PM_F32 / PM_BF16, feat_pitch elements between pixels), splat as above -> sums float [n][classes + 1][c],
+ *     sums[n][k][:] = sum over low-res pixels q of splat[n][q][k] * feat[n][q][:] / max(|feat[n][q][:]|_2, 1e-12) (F.normalize(dim=1); the norm in fp32 after widening)
+ *     -- what tsnelib.py:51-65 computes as matmul(upsample(normalize(feat)), one_hot), because the up-sampling is linear. sums[k] / counts[k] is the class mean vector.
+ *     Chunks of 32 pixels -> partials in ws (pm_class_sums_workspace bytes; 0 for a non-positive size) -> merged in chunk order in double. c % 8 == 0; pitch and
+ *     alignment rules of pm_instnorm_fwd. One splat serves any number of feature maps of the same size (the sweep has two).
+ *   pm_mem_actmap: p_mem float [n][h][w] rows of `pitch` >= m floats, the soft-max over the m memory slots (pm_mem_read_fwd's p_mem); slots: HOST array of nslots slot
+ *     indices (copied into the launch). Per full-res pixel: all m slots interpolated, lo / hi = min / max over the m slots (ablation.py:309-315 channelwise_minmax, which
+ *     is per PIXEL over the slots despite its name), and per listed slot e, a = (v - lo) / (hi - lo), byte = (uint8)(min(max(a, 0), 1) * 255.f) truncated in fp32
+ *     (np.uint8(np.clip(., 0, 1) * 255), :386-389). hi == lo: the reference divides 0 by 0 and converts NaN to an undefined byte; HERE a = 0 and the byte is 0.
+ *     Outputs, each nullable, any subset (at least one): act float [n][nslots][H][W] = a; bytes uint8 [n][nslots][H][W]; rgb uint8 [n][nslots][H][W][3] =
+ *     palette[byte] (palette: uint8 [256][3] RGB in device memory -- the library ships no colour table); blend uint8 [n][nslots][H][W][3] = Image.blend(image, rgb, alpha)
+ *     per colour channel with PIL's bytes (image: uint8 [n][H][W][3]; the alpha channel of the reference's RGBA blend is constantly 255 and is not written). Slot order
+ *     is the list's. m <= 32, 1 <= nslots <= m.
+ * Before any launch -- PM_EINVAL: a null required pointer, a non-positive size, a bad pitch or alignment, a slot outside 0 .. m - 1, nslots outside 1 .. m, no output, rgb
+ * without palette, blend without palette or image. PM_EUNSUPPORTED: an unknown dtype, c % 8 != 0, classes > 31, m > 32. PM_EWORKSPACE: a workspace shorter than the query
+ * answers. */
+int pm_label_splat(const int64_t* labels, int n, int H, int W, int h, int w, int classes, float* splat, int64_t* counts, void* stream);
+size_t pm_class_sums_workspace(int n, int h, int w, int c, int classes);
+int pm_class_sums(const void* feat, int n, int h, int w, int c, int64_t feat_pitch, int dtype, const float* splat, int classes, float* sums, void* ws, size_t ws_bytes,
+                  void* stream);
+int pm_mem_actmap(const float* p_mem, int n, int h, int w, int m, int64_t pitch, int H, int W, const int32_t* slots, int nslots, float* act /*nullable*/,
+                  uint8_t* bytes /*nullable*/, const uint8_t* palette /*nullable*/, const uint8_t* image /*nullable*/, float alpha, uint8_t* rgb /*nullable*/,
+                  uint8_t* blend /*nullable*/, void* stream);
 
 /* ---- input edge: ToTensor + Normalize(ImageNet) (datasets/gtav.py:284-289) and MaskToTensor
  * (transforms/transforms.py:95-97) on the GPU: uint8 HWC images -> normalised NHWC4 fp32 (zero 4th channel, the stem's layout),

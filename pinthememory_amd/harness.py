@@ -675,6 +675,123 @@ def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=Fals
     return dict(hist=hist, acc=acc, acc_cls=acc_cls, mean_iu=mean_iu, fwavacc=fwavacc, predictions=predictions)
 
 
+# ---- the ablation sweep: ablation.py RunAbla.tsne_memact (:317-399) with tsnelib.py RunTsne (:48-96), without t-SNE, figures and files ------------------------
+class FeatureBasket:
+    """RunTsne's basket (tsnelib.py:48-96) without the plotting: per image and per selected class with at least one pixel, the mean L2-normalised feature vector of
+    the class, with its class and domain labels -- image-major, then in the order of selected_clsid; absent classes are dropped. Nothing is copied to the host while the
+    basket fills (the reference reads 19 counts per image back): the rows of an image are kept with a presence mask and compacted once, when they are read."""
+
+    def __init__(self, selected_clsid, classes=19):
+        self.selected_clsid = [int(c) for c in selected_clsid]
+        assert all(0 <= c < classes for c in self.selected_clsid), 'selected classes lie in [0, %d)' % classes
+        self.classes = classes
+        self.init_basket()
+
+    def init_basket(self):
+        self._means, self._present, self._domains = [], [], []
+        self.mem_vecs = self.mem_vec_labels = None
+
+    def add_sums(self, sums, counts, domain_id):
+        """sums [n, classes + 1, C] and counts [n, classes + 1] of K.class_sums / K.label_splat (any device): the kernel-free half of add()."""
+        assert sums.dim() == 3 and tuple(counts.shape) == tuple(sums.shape[:2]) and sums.shape[1] == self.classes + 1
+        sel = torch.as_tensor(self.selected_clsid, dtype=torch.int64, device=sums.device)
+        cnt = counts.index_select(1, sel)
+        self._means.append(sums.index_select(1, sel) / cnt.clamp(min=1).to(sums.dtype).unsqueeze(-1))      # tsnelib.py:69 nominator[slot] / denominator[slot]
+        self._present.append(cnt != 0)
+        self._domains.append(int(domain_id))
+
+    def add(self, features, labels, domain_id, splat=None):
+        """features: logical-NCHW [n, C, h, w] (fp32 / bf16, channels-last memory), labels int64 [n, H, W]; splat: (splat, counts) of K.label_splat for these labels
+        and this feature size, when the caller already has it (one splat serves both baskets of the sweep)."""
+        splat, counts = splat if splat is not None else K.label_splat(labels, tuple(features.shape[2:]), self.classes)
+        self.add_sums(K.class_sums(features, splat), counts, domain_id)
+
+    def input_memory_item(self, m_items):
+        sel = torch.as_tensor(self.selected_clsid, dtype=torch.int64, device=m_items.device)
+        self.mem_vecs = m_items.detach().index_select(0, sel)
+        self.mem_vec_labels = sel
+
+    def vectors(self):
+        """-> (vectors [rows, C], class labels int64 [rows], domain labels int64 [rows]) as draw_tsne takes them (tsnelib.py:90-92): the rows normalised with
+        F.normalize(dim=1). If memory items were given, the selected items follow the feature rows as they are (draw_tsne(plot_memory=True), :145-147), with their
+        slot as class label and domain -1. The one host synchronisation of the basket happens here (the boolean compaction)."""
+        if not self._means:
+            dev = self.mem_vecs.device if self.mem_vecs is not None else 'cpu'
+            vecs, labels, domains = torch.zeros((0, 0), device=dev), torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+        else:
+            means, present = torch.cat(self._means), torch.cat(self._present)
+            dev, S = means.device, len(self.selected_clsid)
+            keep = present.reshape(-1)
+            vecs = F.normalize(means.reshape(-1, means.shape[-1])[keep].float(), dim=1)
+            labels = torch.as_tensor(self.selected_clsid, dtype=torch.int64, device=dev).repeat(present.shape[0])[keep]
+            per_image = torch.as_tensor([d for d, p in zip(self._domains, self._present) for _ in range(p.shape[0])], dtype=torch.int64, device=dev)
+            domains = per_image.repeat_interleave(S)[keep]
+        if self.mem_vecs is not None:
+            mv = self.mem_vecs.to(vecs.device).float()
+            vecs = torch.cat([vecs, mv]) if vecs.numel() else mv
+            labels = torch.cat([labels, self.mem_vec_labels.to(labels.device)])
+            domains = torch.cat([domains, torch.full((mv.shape[0],), -1, dtype=torch.int64, device=domains.device)])
+        return vecs, labels, domains
+
+
+def memory_activation(mem_output, size, slots, palette=None, image=None, alpha=0.65):
+    """ablation.py:371-399 for one batch: mem_output is the memory entry of a net's eval outputs ([p_query, p_mem, refined features]); its soft-max over the slots,
+    mem_output[1] [n, h, w, m], is up-sampled to size = (H, W), min-max normalised per pixel over the slots and mapped for every slot of `slots` -- in one kernel
+    (K.mem_actmap). -> dict: 'bytes', plus 'rgb' with a palette (uint8 [256, 3] RGB on the device) and 'blend' with palette and image (uint8 [n, H, W, 3])."""
+    pm = mem_output[1]
+    n, h, w, _ = pm.shape
+    want = ('bytes',) + (('rgb',) if palette is not None else ()) + (('blend',) if palette is not None and image is not None else ())
+    return K.mem_actmap(pm, (n, h, w), size, slots, palette=palette, image=image, alpha=alpha, want=want)
+
+
+def ablation_sweep(net, loader, selected_clsid, domain_id, max_images=600, on_maps=None, palette=None):
+    """RunAbla.tsne_memact's loop (ablation.py:317-399) over one domain's loader, on the device. `loader` yields (inputs, gt, ...): inputs either the normalised fp32
+    [b, 3, H, W] batch the net takes, or uint8 [b, H, W, 3] images, which are normalised on the device and are then also the background of the blended maps; gt
+    [b, H, W] train ids. Per batch: one eval forward under no_grad (low-res logits: they are not used), one label splat, the class sums of inter_feature (the last
+    output) into the first basket and, for a memory net, of the refined features (mem_output[-1]) into the second. on_maps (memory nets): called as
+    on_maps(first image index, maps) with memory_activation's dict for the batch, slots = selected_clsid. At most max_images images are taken (--imagenum_dom).
+    -> (basket, basket of the refined features or None). t-SNE, figures and files stay with the caller."""
+    m = net.module if hasattr(net, 'module') else net
+    device = next(m.parameters()).device
+    with_memory = bool(getattr(m.args, 'memory', False))
+    basket = FeatureBasket(selected_clsid)
+    updated = FeatureBasket(selected_clsid) if with_memory else None
+    net.eval()
+    was = m.eval_logits_lowres
+    m.eval_logits_lowres = True
+    count = 0
+    try:
+        with torch.no_grad():
+            for data in loader:
+                if count >= max_images:
+                    break
+                inputs, gt = data[0], data[1]
+                image = None
+                if inputs.dtype == torch.uint8:
+                    image = inputs.reshape(-1, *inputs.shape[-3:])[:max_images - count].to(device).contiguous()
+                    inputs = ops.nchw(K.image_u8_to_nhwc4(image))
+                else:
+                    inputs = inputs.reshape(-1, *inputs.shape[-3:])[:max_images - count].to(device)
+                H, W = inputs.shape[2:]
+                gt = gt.reshape(-1, H, W)[:inputs.shape[0]].to(device).contiguous()
+                outputs = net(inputs)
+                features = outputs[-1]
+                splat = K.label_splat(gt, tuple(features.shape[2:]))
+                basket.add(features, gt, domain_id, splat)
+                if with_memory:
+                    mem_output = outputs[-2]
+                    updated.add(mem_output[-1], gt, domain_id, splat)
+                    if on_maps is not None:
+                        on_maps(count, memory_activation(mem_output, (H, W), selected_clsid, palette=palette, image=image))
+                count += inputs.shape[0]
+    finally:
+        m.eval_logits_lowres = was
+    if with_memory:
+        items = m.memory.m_items.clone().detach()
+        basket.input_memory_item(items), updated.input_memory_item(items)
+    return basket, updated
+
+
 # ---- the meta-learning regime every pinmem script runs: train_memory_mldg (train.py:493-632) ----------------------------
 def put_theta(model, theta):
     """train.py:262-277: rewire every leaf module's _parameters with (non-leaf) tensors; the HIP ops take weights as

@@ -801,6 +801,69 @@ def sliding_eval_finish(acc, nscales, labels=None, hist=None, accumulate=True, p
     return pred, hist, logits_out
 
 
+# ---- ablation sweep (ablation.py / tsnelib.py; include/pinmem_hip.h "ablation sweep") --------------------------------------------------------------------------
+def label_splat(labels, size, classes=19):
+    """int64 labels [n, H, W] -> (splat fp32 [n, h, w, classes + 1], counts int64 [n, classes + 1]) for size = (h, w): the labels pushed through the transpose of the
+    bilinear up-sampling h x w -> H x W (row `classes` = label 255, other values outside [0, classes) skipped) and the exact pixel counts. One splat serves every
+    feature map of that size (class_sums)."""
+    n, H, W = labels.shape
+    h, w = int(size[0]), int(size[1])
+    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous()
+    splat = torch.empty((n, h, w, classes + 1), dtype=torch.float32, device=labels.device)
+    counts = torch.empty((n, classes + 1), dtype=torch.int64, device=labels.device)
+    check(_lib().pm_label_splat(labels.data_ptr(), n, H, W, h, w, int(classes), splat.data_ptr(), counts.data_ptr(), stream()), 'pm_label_splat')
+    return splat, counts
+
+
+def class_sums(feat, splat):
+    """feat: a logical-NCHW [n, C, h, w] tensor in channels-last memory (fp32 or bf16; may be a channel slice of a wider buffer), splat from label_splat ->
+    sums fp32 [n, classes + 1, C]: per class the sum of the L2-normalised feature vectors weighted by the splat, i.e. tsnelib.py:51-65's
+    matmul(upsample(normalize(feat)), one_hot(labels)) without the up-sampled map and the one-hot. sums[k] / counts[k] is the class mean vector."""
+    v = feat.permute(0, 2, 3, 1)
+    if v.stride(3) != 1 and v.shape[3] != 1:
+        v = v.contiguous()
+    d = tdesc(v)
+    assert splat.dtype == torch.float32 and splat.is_cuda and splat.is_contiguous() and tuple(splat.shape[:3]) == (d.n, d.h, d.w), 'class_sums: splat is [n, h, w, classes + 1]'
+    classes = splat.shape[3] - 1
+    sums = torch.empty((d.n, classes + 1, d.c), dtype=torch.float32, device=feat.device)
+    lib = _lib()
+    nb = _sizes(('csum', d.n, d.h, d.w, d.c, classes), lambda: lib.pm_class_sums_workspace(d.n, d.h, d.w, d.c, classes))
+    ws = workspace(nb, feat.device)
+    check(lib.pm_class_sums(d.ptr, d.n, d.h, d.w, d.c, d.pitch, d.dtype, splat.data_ptr(), classes, sums.data_ptr(), ptr(ws), nb, stream()), 'pm_class_sums')
+    return sums
+
+
+ACTMAP_OUTPUTS = ('act', 'bytes', 'rgb', 'blend')
+
+
+def mem_actmap(p_mem, nhw, size, slots, palette=None, image=None, alpha=0.65, want=('bytes',)):
+    """The memory activation maps of ablation.py:371-399 from the LOW-RES soft-max over the memory slots. p_mem: fp32 [n * h * w, m] or [n, h, w, m] rows (row stride
+    >= m), nhw = (n, h, w), size = (H, W), slots: the slot indices to map, in output order. want: any of 'act' (fp32 [n, S, H, W], the per-pixel min-max normalised
+    score), 'bytes' (uint8 [n, S, H, W], np.uint8(clip * 255)), 'rgb' (uint8 [n, S, H, W, 3] = palette[bytes]; palette uint8 [256, 3] RGB) and 'blend' (uint8
+    [n, S, H, W, 3] = Image.blend(image, rgb, alpha); image uint8 [n, H, W, 3]). -> dict name -> tensor."""
+    n, h, w = (int(v) for v in nhw)
+    H, W = int(size[0]), int(size[1])
+    m = p_mem.shape[-1]
+    assert p_mem.dtype == torch.float32 and p_mem.is_cuda and p_mem.numel() == n * h * w * m, 'mem_actmap: p_mem is fp32 [n * h * w, m]'
+    rows = p_mem.reshape(n * h * w, m) if p_mem.dim() != 2 else p_mem
+    pitch = rows.stride(0) if rows.shape[0] > 1 else m
+    assert rows.stride(1) == 1 or m == 1
+    want = tuple(want)
+    assert want and all(k in ACTMAP_OUTPUTS for k in want), 'mem_actmap: want is a non-empty subset of %s' % (ACTMAP_OUTPUTS,)
+    slots = [int(s) for s in slots]
+    S = len(slots)
+    dev = p_mem.device
+    for name, t, shape in (('palette', palette, (256, 3)), ('image', image, (n, H, W, 3))):
+        assert t is None or (t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape), 'mem_actmap: %s is uint8 %s' % (name, shape)
+    res = {}
+    for k in want:
+        res[k] = torch.empty((n, S, H, W, 3) if k in ('rgb', 'blend') else (n, S, H, W), dtype=torch.float32 if k == 'act' else torch.uint8, device=dev)
+    arr = (ctypes.c_int32 * max(S, 1))(*slots)
+    check(_lib().pm_mem_actmap(rows.data_ptr(), n, h, w, m, pitch, H, W, arr, S, ptr(res.get('act')), ptr(res.get('bytes')), ptr(palette), ptr(image), float(alpha),
+                               ptr(res.get('rgb')), ptr(res.get('blend')), stream()), 'pm_mem_actmap')
+    return res
+
+
 def argmax_f64(buffer):
     n, h, w, c = buffer.shape
     cls = torch.empty((n, h, w), dtype=torch.int64, device=buffer.device)

@@ -216,6 +216,10 @@ SIGNATURES = {
     'pm_instnorm_workspace': (_sz, [_i, _i, _i, _i]),
     'pm_instnorm_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     'pm_instnorm_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pm_label_splat': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'pm_class_sums_workspace': (_sz, [_i, _i, _i, _i, _i]),
+    'pm_class_sums': (_i, [_vp, _i, _i, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    'pm_mem_actmap': (_i, [_vp, _i, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
 }
 
 _lib = None
