@@ -673,7 +673,9 @@ int pm_mem_read_bwd(const pm_tensor* x, const float* mem, int m, const float* p_
 /* ---- K8 memory write (memory.py:206-239) -----------------------------------------------------------------------
  * accum: zhat = z/max(|z|,1e-12); 4-tap bilinear(align_corners) soft labels of the H x W mask at each h x w pixel
  * (== one_hot(20) -> F.interpolate, memory.py:220-223, without the one-hot); nomden[(m+1)*(d+1)] =
- * nominator[m+1][d] | denominator[m+1], summed over batch and pixels. Deterministic two-stage reduce. */
+ * nominator[m+1][d] | denominator[m+1], summed over batch and pixels. Deterministic two-stage reduce.
+ * Workspace: one partial nomden per block of the accumulating kernel, align256(min(ceil(rows / 64), 512) * (m+1) * (d+1) * 4) with
+ * rows = n*h*w; query, then allocate. 2^31 rows or more: PM_EUNSUPPORTED (the kernel divides row indices in 32 bits). */
 size_t pm_mem_write_accum_workspace(const pm_tensor* z, int m);
 int pm_mem_write_accum(const pm_tensor* z, const int64_t* labels, int H, int W, int m, int normalize,
                        float* nomden, void* ws, size_t ws_bytes, void* stream);

@@ -5,7 +5,7 @@
 //          (meta-test read through a written memory): one wave per row (d = 256 = 64 lanes x float4), per-slot dot products reduced
 //          with wave shuffles.
 //   write  (memory.py:206-239): 4-tap bilinear(align_corners) soft labels straight from the int64 mask (never the
-//          755 MB one-hot), class-masked accumulation of nominator[20][256] / denominator[20] in per-wave LDS slabs,
+//          755 MB one-hot), class-masked accumulation of nominator[20][256] / denominator[20] as a split-K MFMA product,
 //          fixed-order two-stage reduce; momentum update + renormalise with a device-side `den != 0` predicate
 //          (the reference syncs the host 19 times per step, memory.py:234-237).
 // All reductions are deterministic (no atomics).
@@ -17,8 +17,20 @@ constexpr int D = 256;     // feature dim (mem_dim); one wave = one row of 64 fl
 constexpr int MAXM = 32;   // max slots (+1 for the ignore class in write)
 constexpr float EPS = 1e-12f;
 typedef float mr_f32x16 __attribute__((ext_vector_type(16)));   // one 32x32 fp32 MFMA result tile per wave
+constexpr int mr_slot(int q) { return (q & 3) + 8 * (q >> 2); }      // result row (slot / class) of register q in the lower half-wave; the upper half-wave: + 4
+constexpr bool mr_quad(int q, int mm) { return mr_slot(q) < mm; }    // register q's quad reaches below row mm (compile-time pruning of padding quads)
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// gradient through q = v / max(|v|, eps) for a row held as one float4 per lane (n0 = |v|, nrm = max(n0, eps), both wave-uniform): g -> (g - q (q . g)) / nrm;
+// a row below eps is divided by the constant eps, so its gradient is g / eps (the sub-gradient at n0 == eps is the projected one)
+__device__ __forceinline__ float4 normalize_bwd4(const float4& q, const float4& g, float n0, float nrm) {
+  if (n0 >= EPS) {
+    const float qd = pm_wave_sum(dot4(q, g));
+    return make_float4((g.x - q.x * qd) / nrm, (g.y - q.y * qd) / nrm, (g.z - q.z * qd) / nrm, (g.w - q.w * qd) / nrm);
+  }
+  return make_float4(g.x / nrm, g.y / nrm, g.z / nrm, g.w / nrm);
+}
 
 // softmax over ALL rows per slot column (memory.py:186). Two launches over an L2-resident [N][m]: (1) every block folds its 128 rows
 // into a per-column (max, sum exp) pair with the online-softmax merge, (2) every block merges all partials in block order (fixed,
@@ -108,9 +120,9 @@ __global__ __launch_bounds__(CSA_T) void mem_colsoftmax_apply_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// read backward: dx (and optionally per-block partials of dmem)
+// read backward with dmem: dx and per-block partials of dmem (dx alone: mem_read_bwd_mfma_kernel below)
 // ---------------------------------------------------------------------------------------------------------------
-template <int M_, bool DMEM>
+template <int M_>
 __global__ __launch_bounds__(256) void mem_read_bwd_kernel(const float* __restrict__ x, long xp, long rows, const float* __restrict__ mem, int m_rt,
                                                            const float* __restrict__ pm, const float* __restrict__ dqr, long dqp,
                                                            const float* __restrict__ dsx, float* __restrict__ dx, long dxp, float* __restrict__ dmem_part) {
@@ -119,9 +131,9 @@ __global__ __launch_bounds__(256) void mem_read_bwd_kernel(const float* __restri
   for (int i = threadIdx.x; i < M * D / 4; i += 256) reinterpret_cast<float4*>(smem)[i] = reinterpret_cast<const float4*>(mem)[i];
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float4 dm[DMEM ? (M_ > 0 ? M_ : MAXM) : 1];
+  float4 dm[M_ > 0 ? M_ : MAXM];
 #pragma unroll
-  for (int j = 0; j < (DMEM ? (M_ > 0 ? M_ : MAXM) : 1); ++j) dm[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = 0; j < (M_ > 0 ? M_ : MAXM); ++j) dm[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (long r = (long)blockIdx.x * 4 + wv; r < rows; r += (long)gridDim.x * 4) {
     const float4 v = PM_LD4(x + r * xp + lane * 4);
     const float n0 = sqrtf(pm_wave_sum(dot4(v, v)));
@@ -144,38 +156,27 @@ __global__ __launch_bounds__(256) void mem_read_bwd_kernel(const float* __restri
         const float ds = p[j] * (dp[j] - pdp) + (dsx ? dsx[r * M + j] : 0.f);
         const float4 mv = reinterpret_cast<const float4*>(smem + j * D)[lane];
         dq.x += ds * mv.x, dq.y += ds * mv.y, dq.z += ds * mv.z, dq.w += ds * mv.w;
-        if (DMEM) {
-          dm[j].x += ds * q.x + p[j] * dr.x, dm[j].y += ds * q.y + p[j] * dr.y;
-          dm[j].z += ds * q.z + p[j] * dr.z, dm[j].w += ds * q.w + p[j] * dr.w;
-        }
+        dm[j].x += ds * q.x + p[j] * dr.x, dm[j].y += ds * q.y + p[j] * dr.y;
+        dm[j].z += ds * q.z + p[j] * dr.z, dm[j].w += ds * q.w + p[j] * dr.w;
       }
-    // through qhat = x / max(|x|, eps)
-    float4 o;
-    if (n0 >= EPS) {
-      const float qd = pm_wave_sum(dot4(q, dq));
-      o = make_float4((dq.x - q.x * qd) / nrm, (dq.y - q.y * qd) / nrm, (dq.z - q.z * qd) / nrm, (dq.w - q.w * qd) / nrm);
-    } else {
-      o = make_float4(dq.x / nrm, dq.y / nrm, dq.z / nrm, dq.w / nrm);
-    }
-    PM_ST4(dx + r * dxp + lane * 4, o);
+    PM_ST4(dx + r * dxp + lane * 4, normalize_bwd4(q, dq, n0, nrm));      // through qhat = x / max(|x|, eps)
   }
-  if (DMEM) {  // cross-wave reduce through LDS (memory copy no longer needed), then one partial slab per block
-    __syncthreads();
-    float* red = smem;  // reuse: [4 waves] would need 4*M*D floats > MAXM*D; reduce slot by slot instead
+  // cross-wave reduce through LDS (memory copy no longer needed), then one partial slab per block
+  __syncthreads();
+  float* red = smem;  // reuse: [4 waves] would need 4*M*D floats > MAXM*D; reduce slot by slot instead
 #pragma unroll
-    for (int j = 0; j < (M_ > 0 ? M_ : MAXM); ++j)
-      if (j < M) {
-        reinterpret_cast<float4*>(red + wv * D)[lane] = dm[j];
-        __syncthreads();
-        if (wv == 0) {
-          float4 a = reinterpret_cast<float4*>(red)[lane], b = reinterpret_cast<float4*>(red + D)[lane];
-          float4 c = reinterpret_cast<float4*>(red + 2 * D)[lane], d = reinterpret_cast<float4*>(red + 3 * D)[lane];
-          float4 s = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
-          PM_ST4(dmem_part + ((long)blockIdx.x * M + j) * D + lane * 4, s);
-        }
-        __syncthreads();
+  for (int j = 0; j < (M_ > 0 ? M_ : MAXM); ++j)
+    if (j < M) {
+      reinterpret_cast<float4*>(red + wv * D)[lane] = dm[j];
+      __syncthreads();
+      if (wv == 0) {
+        float4 a = reinterpret_cast<float4*>(red)[lane], b = reinterpret_cast<float4*>(red + D)[lane];
+        float4 c = reinterpret_cast<float4*>(red + 2 * D)[lane], d = reinterpret_cast<float4*>(red + 3 * D)[lane];
+        float4 s = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
+        PM_ST4(dmem_part + ((long)blockIdx.x * M + j) * D + lane * 4, s);
       }
-  }
+      __syncthreads();
+    }
 }
 
 // out[i] = sum_b part[b][i]: 16 elements x 16 partial-lanes per block (lane z sums b = z, z + 16, ...; lanes combined in order)
@@ -231,9 +232,8 @@ struct Taps {
   int cls[4];
   float w[4];
 };
-__device__ __forceinline__ Taps soft_label_taps(const int64_t* __restrict__ lab, int b, int y, int x, int H, int W, int h, int w, float sy, float sx, int m) {
+__device__ __forceinline__ Taps soft_label_taps(const int64_t* __restrict__ lab, int b, int y, int x, int H, int W, float sy, float sx, int m) {
   const pm_lerp ly = pm_ac_lerp(sy, y, H), lx = pm_ac_lerp(sx, x, W);  // downsample: source grid is the H x W mask
-  (void)h, (void)w;
   Taps t;
   const int64_t* base = lab + (long)b * H * W;
   const int ys[2] = {ly.i0, ly.i1}, xs[2] = {lx.i0, lx.i1};
@@ -250,56 +250,10 @@ __device__ __forceinline__ Taps soft_label_taps(const int64_t* __restrict__ lab,
   return t;
 }
 
-constexpr int ACC_W = 4;   // waves per block
-__global__ __launch_bounds__(256) void mem_write_accum_kernel(const float* __restrict__ z, long zp, int n, int h, int w, const int64_t* __restrict__ lab,
-                                                              int H, int W, int m, int normalize, float sy, float sx, float* __restrict__ part) {
-  extern __shared__ __align__(16) float sacc[];   // [ACC_W][(m+1)*D + MAXM]
-  const int slab = (m + 1) * D + MAXM;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* mine = sacc + wv * slab;
-  for (int i = lane; i < slab; i += 64) mine[i] = 0.f;
-  const long rows = (long)n * h * w;
-  const long stride = (long)gridDim.x * ACC_W;
-  long r = (long)blockIdx.x * ACC_W + wv;
-  auto fetch = [&](long rr, float4& v, Taps& t) {
-    v = PM_LD4(z + rr * zp + lane * 4);
-    t = soft_label_taps(lab, (int)(rr / ((long)w * h)), (int)((rr / w) % h), (int)(rr % w), H, W, h, w, sy, sx, m);
-  };
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  Taps t{};
-  if (r < rows) fetch(r, v, t);
-  while (r < rows) {   // the next row's feature vector and label taps are in flight while this one is accumulated
-    const long rn = r + stride;
-    float4 vn = v;
-    Taps tn = t;
-    if (rn < rows) fetch(rn, vn, tn);
-    if (normalize) {
-      const float nrm = fmaxf(sqrtf(pm_wave_sum(dot4(v, v))), EPS);
-      v = make_float4(v.x / nrm, v.y / nrm, v.z / nrm, v.w / nrm);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (t.cls[k] < 0 || t.w[k] == 0.f) continue;   // wave-uniform
-      float4* a = reinterpret_cast<float4*>(mine + t.cls[k] * D) + lane;
-      float4 c = *a;
-      c.x += t.w[k] * v.x, c.y += t.w[k] * v.y, c.z += t.w[k] * v.z, c.w += t.w[k] * v.w;
-      *a = c;
-      if (lane == 0) mine[(m + 1) * D + t.cls[k]] += t.w[k];
-    }
-    v = vn, t = tn, r = rn;
-  }
-  __syncthreads();
-  const int nout = (m + 1) * D + (m + 1);
-  for (int i = threadIdx.x; i < nout; i += 256) {
-    const int src = i < (m + 1) * D ? i : (m + 1) * D + (i - (m + 1) * D);
-    part[(long)blockIdx.x * nout + i] = (sacc[src] + sacc[slab + src]) + (sacc[2 * slab + src] + sacc[3 * slab + src]);
-  }
-}
-
-// The same accumulation as a split-K product on the matrix cores: nominator[c][d] = sum_r Y[r][c] * zhat[r][d] with Y the (<= 4 non-zeros per row)
-// soft-label matrix, i.e. a (32 padded classes) x (64-row chunk) x (256 channels) GEMM per chunk, K split over the blocks. What bounded the slab
-// kernel above was not bytes but its dependent chain -- 18 rows per wave, each a global round trip plus four LDS read-modify-writes (44 us for
-// 19 MB); here every row of a chunk is in flight at once (16 float4 per lane), and the scatter by class becomes the A operand:
+// The accumulation as a split-K product on the matrix cores: nominator[c][d] = sum_r Y[r][c] * zhat[r][d] with Y the (<= 4 non-zeros per row)
+// soft-label matrix, i.e. a (32 padded classes) x (64-row chunk) x (256 channels) GEMM per chunk, K split over the blocks. What bounded the per-wave
+// LDS-slab kernel of rounds 1-3 (DESIGN_HISTORY.md) was not bytes but its dependent chain -- 18 rows per wave, each a global round trip plus four LDS
+// read-modify-writes (44 us for 19 MB); here every row of a chunk is in flight at once (16 float4 per lane), and the scatter by class becomes the A operand:
 //   * wave w = (channel half ch = w & 1, row half rh = w >> 1); lane (l31 = lane & 31, half = lane >> 5) loads, for s = 0..15, the float4 of row
 //     32 rh + 2 s + half at channels 128 ch + 4 l31: half-waves read 512 contiguous bytes;
 //   * row norms: per-lane partial sums of squares parked in LDS, four threads per row fold the 64 partials in fixed order; the 1 / max(norm, eps)
@@ -307,7 +261,7 @@ __global__ __launch_bounds__(256) void mem_write_accum_kernel(const float* __res
 //   * 4 MFMAs (32x32x2 f32) per loaded float4: B = component e of the float4 (output column l31 of tile e = channel 128 ch + 4 l31 + e), so each
 //     lane ends up with float4s of consecutive channels per class -- partial rows leave as 512-byte runs;
 //   * denominators are summed outside the product (plain tap weights, fixed order); the two row halves meet in LDS (fixed order).
-// Deterministic, no atomics; partial layout = the slab kernel's, so reduce_partials_kernel finishes both.
+// Deterministic, no atomics; one partial slab [(m + 1) x 256 nominators | m + 1 denominators] per block, summed by reduce_partials_kernel.
 constexpr int AM_ROWS = 64;                 // rows per chunk
 constexpr int AM_SSP = 65;                  // padded row of partial squared norms
 __global__ __launch_bounds__(256) void mem_write_accum_mfma_kernel(const float* __restrict__ z, long zp, int n, int h, int w, const int64_t* __restrict__ lab,
@@ -339,7 +293,7 @@ __global__ __launch_bounds__(256) void mem_write_accum_mfma_kernel(const float* 
       Taps t;
       if (rr < rows) {
         const unsigned r32 = (unsigned)rr, px = r32 / (unsigned)w;                  // rows < 2^31 (checked by the launcher): 32-bit divisions
-        t = soft_label_taps(lab, (int)(px / (unsigned)h), (int)(px % (unsigned)h), (int)(r32 % (unsigned)w), H, W, h, w, sy, sx, m);
+        t = soft_label_taps(lab, (int)(px / (unsigned)h), (int)(px % (unsigned)h), (int)(r32 % (unsigned)w), H, W, sy, sx, m);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) t.cls[k] = -1, t.w[k] = 0.f;
@@ -394,13 +348,13 @@ __global__ __launch_bounds__(256) void mem_write_accum_mfma_kernel(const float* 
       acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v[s].w, acc[3], 0, 0, 0);
     }
   }
-  // the two row halves meet in LDS: rh = 1 parks, rh = 0 adds and stores. Register q of a lane = class (q & 3) + 8 (q >> 2) + 4 half.
+  // the two row halves meet in LDS: rh = 1 parks, rh = 0 adds and stores. Register q of a lane = class mr_slot(q) + 4 half.
   __syncthreads();
   float* xch = am_ss;                                           // [m + 1][256]
   if (rh == 1) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int c = (q & 3) + 8 * (q >> 2) + 4 * half;
+      const int c = mr_slot(q) + 4 * half;
       if (c <= m) *reinterpret_cast<float4*>(xch + c * D + 128 * ch + 4 * l31) = make_float4(acc[0][q], acc[1][q], acc[2][q], acc[3][q]);
     }
   }
@@ -410,7 +364,7 @@ __global__ __launch_bounds__(256) void mem_write_accum_mfma_kernel(const float* 
   if (rh == 0) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int c = (q & 3) + 8 * (q >> 2) + 4 * half;
+      const int c = mr_slot(q) + 4 * half;
       if (c <= m) {
         const float4 o = *reinterpret_cast<const float4*>(xch + c * D + 128 * ch + 4 * l31);
         float* dst = mine + c * D + 128 * ch + 4 * l31;         // 512-byte runs per half-wave
@@ -430,7 +384,7 @@ __global__ __launch_bounds__(256) void mem_write_accum_bwd_kernel(const float* _
   const long rows = (long)n * h * w;
   for (long r = (long)blockIdx.x * 4 + wv; r < rows; r += (long)gridDim.x * 4) {
     const int x = (int)(r % w), y = (int)((r / w) % h), b = (int)(r / ((long)w * h));
-    const Taps t = soft_label_taps(lab, b, y, x, H, W, h, w, sy, sx, m);
+    const Taps t = soft_label_taps(lab, b, y, x, H, W, sy, sx, m);
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -442,13 +396,7 @@ __global__ __launch_bounds__(256) void mem_write_accum_bwd_kernel(const float* _
       const float4 v = PM_LD4(z + r * zp + lane * 4);
       const float n0 = sqrtf(pm_wave_sum(dot4(v, v)));
       const float nrm = fmaxf(n0, EPS);
-      if (n0 >= EPS) {
-        const float4 q = make_float4(v.x / nrm, v.y / nrm, v.z / nrm, v.w / nrm);
-        const float qd = pm_wave_sum(dot4(q, g));
-        g = make_float4((g.x - q.x * qd) / nrm, (g.y - q.y * qd) / nrm, (g.z - q.z * qd) / nrm, (g.w - q.w * qd) / nrm);
-      } else {
-        g = make_float4(g.x / nrm, g.y / nrm, g.z / nrm, g.w / nrm);
-      }
+      g = normalize_bwd4(make_float4(v.x / nrm, v.y / nrm, v.z / nrm, v.w / nrm), g, n0, nrm);
     }
     PM_ST4(dz + r * dzp + lane * 4, g);
   }
@@ -507,6 +455,74 @@ __global__ __launch_bounds__(256) void mem_write_update_bwd_kernel(const float* 
 // 50 KB of LDS per block: three blocks (12 waves) per CU, the 576 blocks of the flagship (18 432 rows) are resident at once.
 constexpr int MR_LDK = D + 4;     // 1040-byte rows: conflict-free ds_read_b128 fragments (bank step 4 per row)
 constexpr int MR_SP = 17 * 64;    // per wave: 16 partial-score registers + the partial squared norm, one float per lane each
+constexpr size_t MR_LDS_BYTES = (size_t)(32 * MR_LDK + 4 * MR_SP) * sizeof(float);      // the [32][MR_LDK] row tile + Sp[4][17][64]
+
+// The parts of the 32-row tile, shared by the forward and the backward kernel. Everywhere: w = wave, lane = l31 + 32 half.
+// This wave's fragment of the memory, the A operand of S^T = M X^T / dP^T = M dR^T: slot = lane & 31, 4 consecutive channels per 8-channel group of its 64.
+// Lanes beyond the slots read a valid row and multiply by zero.
+__device__ __forceinline__ void mr_load_mf(float4 (&mf)[8], const float* __restrict__ mem, int M, int w, int l31, int half) {
+  const int mslot = min(l31, M - 1);
+  const float mz = l31 < M ? 1.f : 0.f;
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    mf[g] = PM_LD4(mem + (long)mslot * D + 64 * w + 8 * g + 4 * half);
+    mf[g].x *= mz, mf[g].y *= mz, mf[g].z *= mz, mf[g].w *= mz;
+  }
+}
+// One of the eight steps of the partial product over this wave's quarter of the reduction (32 chained MFMAs, operands swapped: [slot][row]):
+// m = mf[g], a = the four channels 64 w + 8 g + 4 half + (0..3) of the lane's own row. The forward kernel reads a from LDS and sums the row's squared
+// norm on the way, the backward kernel holds it in registers. (A whole-product helper taking the fragment as a callable was compiled and not kept: the
+// forward kernel sits at its register cap and spilled 20 bytes per lane at 19 slots.)
+__device__ __forceinline__ mr_f32x16 mr_mfma4(const float4& m, const float4& a, mr_f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(m.x, a.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(m.y, a.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(m.z, a.z, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(m.w, a.w, acc, 0, 0, 0);
+}
+// The four waves' partials (acc and one scalar) are parked in Sp and, after one barrier, added by every wave in the same fixed order: bit-identical in all four.
+__device__ __forceinline__ void mr_sum_waves(float* Sp, int w, int lane, mr_f32x16& acc, float& s) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) Sp[w * MR_SP + q * 64 + lane] = acc[q];
+  Sp[w * MR_SP + 16 * 64 + lane] = s;
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = ((Sp[q * 64 + lane] + Sp[MR_SP + q * 64 + lane]) + Sp[2 * MR_SP + q * 64 + lane]) + Sp[3 * MR_SP + q * 64 + lane];
+  s = ((Sp[16 * 64 + lane] + Sp[MR_SP + 16 * 64 + lane]) + Sp[2 * MR_SP + 16 * 64 + lane]) + Sp[3 * MR_SP + 16 * 64 + lane];
+}
+// A operand of the second product (agg^T = M^T P^T / add^T = M^T dS^T): step q multiplies slot mr_slot(q) [+ 4 in the upper half-wave]; channels
+// 64 w + (lane & 31) at [0] and + 32 at [32]. Padding slots read a valid row and meet a zero in B.
+__device__ __forceinline__ const float* mr_ma_ptr(const float* __restrict__ mem, int q, int M, int w, int l31, int half) {
+  return mem + (long)min(mr_slot(q) + 4 * half, M - 1) * D + 64 * w + l31;
+}
+// ag[n] = the product over the live register quads, for this wave's channels 64 w + 32 n + ..: ma(n, q) = the A operand, b[q] the lane's own row of P / dS
+template <int MM, class Ma>
+__device__ __forceinline__ void mr_second(mr_f32x16 (&ag)[2], const float (&b)[16], Ma ma) {
+#pragma unroll
+  for (int n = 0; n < 2; ++n)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) ag[n][q] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    if (!mr_quad(q, MM)) continue;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) ag[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(ma(n, q), b[q], ag[n], 0, 0, 0);
+  }
+}
+// A [32][MR_LDK] tile in LDS leaves as whole 1 KB rows, one row per wave instruction, 8 rows per wave. SCALED: times the row's scale, which lives in lane (row & 31).
+template <bool SCALED>
+__device__ __forceinline__ void mr_store_rows(const float* tile, float* __restrict__ out, long pitch, long row0, long rows, int w, int lane, float scale = 1.f) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const long r = row0 + 8 * w + u;
+    float4 v = *reinterpret_cast<const float4*>(tile + (8 * w + u) * MR_LDK + lane * 4);
+    if constexpr (SCALED) {
+      const float nr = __shfl(scale, 8 * w + u, 64);
+      v = make_float4(v.x * nr, v.y * nr, v.z * nr, v.w * nr);
+    }
+    if (r < rows) PM_ST4(out + r * pitch + lane * 4, v);
+  }
+}
+
 template <int M_, bool COLPART = false>
 __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* __restrict__ x, long xp, long rows, const float* __restrict__ mem, int m_rt,
                                                                 const float* __restrict__ noise, float* __restrict__ qr, long qp,
@@ -519,22 +535,16 @@ __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* 
   float* Xs = mr_smem;                  // [32][LDK]
   float* Sp = mr_smem + 32 * LDK;       // [4][17][64]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
-  const int mslot = min(l31, M - 1);                       // lanes beyond the slots read a valid row and multiply by zero below
-  const float mz = l31 < M ? 1.f : 0.f;
-  // this wave's fragments of the memory: S^T operand (slot = lane & 31, 4 consecutive channels per 8-channel group of its 64) ...
+  // this wave's fragments of the memory: the S^T operand ...
   float4 mf[8];
-#pragma unroll
-  for (int g = 0; g < 8; ++g) {
-    mf[g] = PM_LD4(mem + (long)mslot * D + 64 * w + 8 * g + 4 * half);
-    mf[g].x *= mz, mf[g].y *= mz, mf[g].z *= mz, mf[g].w *= mz;
-  }
-  // ... and agg^T operand (channel = 64 w + 32 n + (lane & 31); step q multiplies slot (q&3) + 8 (q>>2) [+ 4 in the upper half-wave])
+  mr_load_mf(mf, mem, M, w, l31, half);
+  // ... and the agg^T operand
   float ma[2][16];
   auto load_ma = [&](int opaque) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      if ((q & 3) + 8 * (q >> 2) >= MM) continue;             // both slots of this step are padding
-      const float* bp = mem + (long)min((q & 3) + 8 * (q >> 2) + 4 * half, M - 1) * D + 64 * w + l31 + opaque;
+      if (!mr_quad(q, MM)) continue;                          // both slots of this step are padding
+      const float* bp = mr_ma_ptr(mem, q, M, w, l31, half) + opaque;
       ma[0][q] = bp[0], ma[1][q] = bp[32];
     }
   };
@@ -559,21 +569,12 @@ __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* 
     for (int g = 0; g < 8; ++g) {
       const float4 a = *reinterpret_cast<const float4*>(Xs + l31 * LDK + 64 * w + 8 * g + 4 * half);      // lane & 31 = query row
       n2 += dot4(a, a);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].x, a.x, acc, 0, 0, 0);                              // S^T[slot][row]: operands swapped
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].y, a.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].z, a.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].w, a.w, acc, 0, 0, 0);
+      acc = mr_mfma4(mf[g], a, acc);                                                                       // S^T[slot][row]
     }
     n2 += __shfl_xor(n2, 32, 64);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Sp[w * MR_SP + q * 64 + lane] = acc[q];
-    Sp[w * MR_SP + 16 * 64 + lane] = n2;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = ((Sp[q * 64 + lane] + Sp[MR_SP + q * 64 + lane]) + Sp[2 * MR_SP + q * 64 + lane]) + Sp[3 * MR_SP + q * 64 + lane];
-    n2 = ((Sp[16 * 64 + lane] + Sp[MR_SP + 16 * 64 + lane]) + Sp[2 * MR_SP + 16 * 64 + lane]) + Sp[3 * MR_SP + 16 * 64 + lane];
+    mr_sum_waves(Sp, w, lane, acc, n2);
     const float rnrm = 1.f / fmaxf(sqrtf(n2), EPS);      // one division per row; qhat and the scores multiply by it (<= 1 ulp from x / ||x||)
-    // acc[q] = <x_row, m_slot> for slot s = (q & 3) + 8 (q >> 2) + 4 half of this lane's own row
+    // acc[q] = <x_row, m_slot> for slot s = mr_slot(q) + 4 half of this lane's own row
     if constexpr (COLPART) {
       // per-slot (max, sum exp) of this tile's 32 rows for the softmax over ALL queries (memory.py:186): every wave holds the same scores, wave w takes the
       // register quads q with (q & 3) == w (at most three), rows are the 32 lanes of a half-wave -> butterfly within the half. Replaces the first of the
@@ -605,8 +606,8 @@ __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* 
     float mx = -INFINITY;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int sl = (q & 3) + 8 * (q >> 2) + 4 * half;
-      if ((q & 3) + 8 * (q >> 2) < MM && sl < M) {          // first test: compile-time pruning of register quads beyond the slots
+      const int sl = mr_slot(q) + 4 * half;
+      if (mr_quad(q, MM) && sl < M) {
         float sv = acc[q] * rnrm;
         if (live && w == 0) score[myrow * M + sl] = sv;
         if (noise) sv += noise[myrow * M + sl];
@@ -624,33 +625,17 @@ __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* 
     const float rse = 1.f / se;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int sl = (q & 3) + 8 * (q >> 2) + 4 * half;
+      const int sl = mr_slot(q) + 4 * half;
       pr[q] = pr[q] * rse;
-      if ((q & 3) + 8 * (q >> 2) < MM && sl < M && live && w == 1) pm[myrow * M + sl] = pr[q];
+      if (mr_quad(q, MM) && sl < M && live && w == 1) pm[myrow * M + sl] = pr[q];
     }
-    // qhat = x / ||x|| from the LDS copy, one row (1 KB) per wave instruction; the row's norm lives in lane (row & 31)
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const long r = row0 + 8 * w + u;
-      const float nr = __shfl(rnrm, 8 * w + u, 64);
-      const float4 v = *reinterpret_cast<const float4*>(Xs + (8 * w + u) * LDK + lane * 4);
-      if (r < rows) PM_ST4(qr + r * qp + lane * 4, make_float4(v.x * nr, v.y * nr, v.z * nr, v.w * nr));
-    }
+    mr_store_rows<true>(Xs, qr, qp, row0, rows, w, lane, rnrm);      // qhat = x / ||x|| from the LDS copy
     __syncthreads();                                       // every wave is done with the x rows: Xs becomes the [32][256] staging tile of agg
     // agg^T = M^T P^T for this wave's 64 channels; padding slots carry P = 0. The register quads (4 consecutive channels of the lane's own
     // row) are parked in LDS and leave as whole 1 KB rows, 8 rows per wave: full-line stores instead of 32-byte pieces of 32 rows.
     {
       mr_f32x16 ag[2];
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ag[n][q] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if ((q & 3) + 8 * (q >> 2) >= MM) continue;
-#pragma unroll
-        for (int n = 0; n < 2; ++n) ag[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(ma[n][q], pr[q], ag[n], 0, 0, 0);
-      }
+      mr_second<MM>(ag, pr, [&](int n, int q) { return ma[n][q]; });
       float* dst = Xs + l31 * LDK + 64 * w + 4 * half;
 #pragma unroll
       for (int n = 0; n < 2; ++n)
@@ -659,12 +644,7 @@ __global__ __launch_bounds__(256, 3) void mem_read_fwd_mfma_kernel(const float* 
           *reinterpret_cast<float4*>(dst + n * 32 + 8 * g4) = make_float4(ag[n][4 * g4], ag[n][4 * g4 + 1], ag[n][4 * g4 + 2], ag[n][4 * g4 + 3]);
     }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const long r = row0 + 8 * w + u;
-      const float4 v = *reinterpret_cast<const float4*>(Xs + (8 * w + u) * LDK + lane * 4);
-      if (r < rows) PM_ST4(qr + r * qp + D + lane * 4, v);
-    }
+    mr_store_rows<false>(Xs, qr + D, qp, row0, rows, w, lane);
   }
 }
 
@@ -687,18 +667,11 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
   float* Os = mr_smem;                  // [32][LDK]: dx tile
   float* Sp = mr_smem + 32 * LDK;       // [4][17][64]: partial dP quads + partial squared norm / partial row dot
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
-  const int mslot = min(l31, M - 1);
-  const float mz = l31 < M ? 1.f : 0.f;
   float4 mf[8];
-#pragma unroll
-  for (int g = 0; g < 8; ++g) {
-    mf[g] = PM_LD4(mem + (long)mslot * D + 64 * w + 8 * g + 4 * half);
-    mf[g].x *= mz, mf[g].y *= mz, mf[g].z *= mz, mf[g].w *= mz;
-  }
+  mr_load_mf(mf, mem, M, w, l31, half);
   for (long row0 = (long)blockIdx.x * 32; row0 < rows; row0 += (long)gridDim.x * 32) {
     if (row0 != (long)blockIdx.x * 32) __syncthreads();    // the previous tile's row stores are done with Os / Sp
-    const long myrow = min(row0 + l31, rows - 1);
-    const bool live = row0 + l31 < rows;
+    const long myrow = min(row0 + l31, rows - 1);          // rows past the end: a copy of the last row, never stored
     float4 xv[8], dq[8], dr[8];
     {
       const float* xr = x + myrow * xp + 64 * w + 4 * half;
@@ -714,23 +687,12 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
 #pragma unroll
-    for (int g = 0; g < 8; ++g) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].x, dr[g].x, acc, 0, 0, 0);       // dP^T[slot][row]
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].y, dr[g].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].z, dr[g].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[g].w, dr[g].w, acc, 0, 0, 0);
-    }
+    for (int g = 0; g < 8; ++g) acc = mr_mfma4(mf[g], dr[g], acc);       // dP^T[slot][row]
     float n2 = 0.f;
 #pragma unroll
     for (int g = 0; g < 8; ++g) n2 += dot4(xv[g], xv[g]);
     n2 += __shfl_xor(n2, 32, 64);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Sp[w * MR_SP + q * 64 + lane] = acc[q];
-    Sp[w * MR_SP + 16 * 64 + lane] = n2;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = ((Sp[q * 64 + lane] + Sp[MR_SP + q * 64 + lane]) + Sp[2 * MR_SP + q * 64 + lane]) + Sp[3 * MR_SP + q * 64 + lane];
-    n2 = ((Sp[16 * 64 + lane] + Sp[MR_SP + 16 * 64 + lane]) + Sp[2 * MR_SP + 16 * 64 + lane]) + Sp[3 * MR_SP + 16 * 64 + lane];
+    mr_sum_waves(Sp, w, lane, acc, n2);
     const float n0 = sqrtf(n2);
     const float rn = 1.f / fmaxf(n0, EPS);
     // softmax backward over the slots of the lane's own row: ds = p (dp - sum_j p_j dp_j) + dsx
@@ -738,9 +700,9 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
     float pdp = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int sl = (q & 3) + 8 * (q >> 2) + 4 * half;
+      const int sl = mr_slot(q) + 4 * half;
       pv[q] = 0.f;
-      if ((q & 3) + 8 * (q >> 2) < MM && sl < M) {
+      if (mr_quad(q, MM) && sl < M) {
         pv[q] = pm[myrow * M + sl];
         pdp += pv[q] * acc[q];
       }
@@ -748,26 +710,16 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
     pdp += __shfl_xor(pdp, 32, 64);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int sl = (q & 3) + 8 * (q >> 2) + 4 * half;
+      const int sl = mr_slot(q) + 4 * half;
       ds[q] = 0.f;
-      if ((q & 3) + 8 * (q >> 2) < MM && sl < M) ds[q] = pv[q] * (acc[q] - pdp) + (dsx ? dsx[myrow * M + sl] : 0.f);
+      if (mr_quad(q, MM) && sl < M) ds[q] = pv[q] * (acc[q] - pdp) + (dsx ? dsx[myrow * M + sl] : 0.f);
     }
     __syncthreads();                                       // every wave has read the partials: Sp is free for the row dots
     // dq += dS M for this wave's 64 channels
     float qd = 0.f;
     {
       mr_f32x16 ag[2];
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ag[n][q] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if ((q & 3) + 8 * (q >> 2) >= MM) continue;
-        const float* bp = mem + (long)min((q & 3) + 8 * (q >> 2) + 4 * half, M - 1) * D + 64 * w + l31;
-#pragma unroll
-        for (int n = 0; n < 2; ++n) ag[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(bp[32 * n], ds[q], ag[n], 0, 0, 0);
-      }
+      mr_second<MM>(ag, ds, [&](int n, int q) { return mr_ma_ptr(mem, q, M, w, l31, half)[32 * n]; });
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
         dq[g].x += ag[g >> 2][4 * (g & 3)], dq[g].y += ag[g >> 2][4 * (g & 3) + 1], dq[g].z += ag[g >> 2][4 * (g & 3) + 2], dq[g].w += ag[g >> 2][4 * (g & 3) + 3];
@@ -788,31 +740,21 @@ __global__ __launch_bounds__(256, 2) void mem_read_bwd_mfma_kernel(const float* 
         *reinterpret_cast<float4*>(dst + 8 * g) = make_float4((dq[g].x - xv[g].x * c) * rn, (dq[g].y - xv[g].y * c) * rn, (dq[g].z - xv[g].z * c) * rn, (dq[g].w - xv[g].w * c) * rn);
     }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const long r = row0 + 8 * w + u;
-      const float4 v = *reinterpret_cast<const float4*>(Os + (8 * w + u) * LDK + lane * 4);
-      if (r < rows) PM_ST4(dx + r * dxp + lane * 4, v);
-    }
-    (void)live;
+    mr_store_rows<false>(Os, dx, dxp, row0, rows, w, lane);
   }
 }
 
 inline int row_blocks(long rows) { return (int)std::min<long>((rows + 3) / 4, 256 * 8); }
-inline int accum_blocks(long rows) { return (int)std::min<long>((rows + 15) / 16, 256); }   // slab kernel: one block (4 wave slabs in LDS) per CU
+inline int tile_blocks(long rows) { return (int)std::min<long>((rows + 31) / 32, 256 * 3 * 4); }   // 32-row tiles: three resident blocks per CU, four rounds
 inline int accum_mfma_blocks(long rows) { return (int)std::min<long>((rows + AM_ROWS - 1) / AM_ROWS, 512); }   // MFMA kernel: two resident blocks per CU (141 + 68 registers)
 
-}  // namespace
+// f(std::integral_constant<int, M_>): the instantiation compiled for the 19 slots of the workload, or the generic one (M_ = 0: m at run time, padded to MAXM)
+template <class F>
+inline void with_slots(int m, F f) {
+  if (m == 19) f(std::integral_constant<int, 19>{});
+  else f(std::integral_constant<int, 0>{});
+}
 
-namespace {
-int mem_read_fwd_launch(const pm_tensor* x, const float* mem, int m, const float* noise, const float* noise_q, const pm_tensor* qr, float* score, float* p_mem,
-                        float* colpart, void* stream);
-}
-extern "C" int pm_mem_read_fwd(const pm_tensor* x, const float* mem, int m, const float* noise, const pm_tensor* qr, float* score, float* p_mem,
-                               void* stream) {
-  return mem_read_fwd_launch(x, mem, m, noise, nullptr, qr, score, p_mem, nullptr, stream);
-}
-namespace {
 int mem_read_fwd_launch(const pm_tensor* x, const float* mem, int m, const float* noise, const float* noise_q, const pm_tensor* qr, float* score, float* p_mem,
                         float* colpart, void* stream) {
   PM_REQUIRE_F32(x, "mem_read_fwd");
@@ -822,22 +764,20 @@ int mem_read_fwd_launch(const pm_tensor* x, const float* mem, int m, const float
   PM_REQUIRE(m >= 1 && m <= MAXM && pm_pixels(x) == pm_pixels(qr), PM_EINVAL, "mem_read_fwd: bad slots/rows");
   const long rows = pm_pixels(x);
   hipStream_t st = (hipStream_t)stream;
-  const int nb = (int)std::min<long>((rows + 31) / 32, 256 * 3 * 4);
-  const size_t lds = (size_t)(32 * MR_LDK + 4 * MR_SP) * sizeof(float);
-#define PM_MR_LAUNCH(MM, CP)                                                                                                                              \
-  hipLaunchKernelGGL((mem_read_fwd_mfma_kernel<MM, CP>), dim3(nb), dim3(256), lds, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, noise, (float*)qr->ptr, \
-                     (long)qr->pitch, score, p_mem, noise_q, colpart)
-  if (m == 19) {
-    if (colpart) PM_MR_LAUNCH(19, true);
-    else PM_MR_LAUNCH(19, false);
-  } else {
-    if (colpart) PM_MR_LAUNCH(0, true);
-    else PM_MR_LAUNCH(0, false);
-  }
-#undef PM_MR_LAUNCH
+  with_slots(m, [&](auto slots) {
+    constexpr int M_ = decltype(slots)::value;
+    auto kernel = colpart ? mem_read_fwd_mfma_kernel<M_, true> : mem_read_fwd_mfma_kernel<M_, false>;
+    hipLaunchKernelGGL(kernel, dim3(tile_blocks(rows)), dim3(256), MR_LDS_BYTES, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, noise, (float*)qr->ptr,
+                       (long)qr->pitch, score, p_mem, noise_q, colpart);
+  });
   return pm_check_launch("mem_read_fwd");
 }
 }  // namespace
+
+extern "C" int pm_mem_read_fwd(const pm_tensor* x, const float* mem, int m, const float* noise, const pm_tensor* qr, float* score, float* p_mem,
+                               void* stream) {
+  return mem_read_fwd_launch(x, mem, m, noise, nullptr, qr, score, p_mem, nullptr, stream);
+}
 
 // read + the softmax over all queries in two launches: the read kernel leaves the per-tile column partials, the apply kernel merges them and normalises
 extern "C" size_t pm_mem_read_fwd_pq_workspace(int64_t rows, int m) { return pm_align_up((size_t)pm_cdiv(rows, 32) * m * 2 * sizeof(float), 256); }
@@ -878,30 +818,24 @@ extern "C" int pm_mem_read_bwd(const pm_tensor* x, const float* mem, int m, cons
   hipStream_t st = (hipStream_t)stream;
   if (dmem) {
     PM_REQUIRE(ws && ws_bytes >= pm_mem_read_bwd_workspace(rows, m, D), PM_EWORKSPACE, "mem_read_bwd: workspace too small");
-    if (m == 19)
-      hipLaunchKernelGGL((mem_read_bwd_kernel<19, true>), dim3(nb), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
+    with_slots(m, [&](auto slots) {
+      hipLaunchKernelGGL(mem_read_bwd_kernel<decltype(slots)::value>, dim3(nb), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
                          (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch, (float*)ws);
-    else
-      hipLaunchKernelGGL((mem_read_bwd_kernel<0, true>), dim3(nb), dim3(256), 0, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
-                         (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch, (float*)ws);
+    });
     const long n = (long)m * D;
     launch_reduce_partials((const float*)ws, nb, n, dmem, st);
   } else {
-    const int nt = (int)std::min<long>((rows + 31) / 32, 256 * 3 * 4);
-    const size_t lds = (size_t)(32 * MR_LDK + 4 * MR_SP) * sizeof(float);
-    if (m == 19)
-      hipLaunchKernelGGL(mem_read_bwd_mfma_kernel<19>, dim3(nt), dim3(256), lds, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
-                         (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch);
-    else
-      hipLaunchKernelGGL(mem_read_bwd_mfma_kernel<0>, dim3(nt), dim3(256), lds, st, (const float*)x->ptr, (long)x->pitch, rows, mem, m, p_mem,
-                         (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch);
+    with_slots(m, [&](auto slots) {
+      hipLaunchKernelGGL(mem_read_bwd_mfma_kernel<decltype(slots)::value>, dim3(tile_blocks(rows)), dim3(256), MR_LDS_BYTES, st, (const float*)x->ptr, (long)x->pitch,
+                         rows, mem, m, p_mem, (const float*)dqr->ptr, (long)dqr->pitch, dsx, (float*)dx->ptr, (long)dx->pitch);
+    });
   }
   return pm_check_launch("mem_read_bwd");
 }
 
 extern "C" size_t pm_mem_write_accum_workspace(const pm_tensor* z, int m) {
   if ((z && !pm_is_f32(z))) return 0;      // fp32 tensors only
-  return pm_align_up((size_t)std::max(accum_blocks(pm_pixels(z)), accum_mfma_blocks(pm_pixels(z))) * ((m + 1) * (D + 1)) * sizeof(float), 256);
+  return pm_align_up((size_t)accum_mfma_blocks(pm_pixels(z)) * ((m + 1) * (D + 1)) * sizeof(float), 256);      // one partial slab per block
 }
 extern "C" int pm_mem_write_accum(const pm_tensor* z, const int64_t* labels, int H, int W, int m, int normalize, float* nomden, void* ws, size_t ws_bytes,
                                   void* stream) {
@@ -910,20 +844,11 @@ extern "C" int pm_mem_write_accum(const pm_tensor* z, const int64_t* labels, int
   PM_REQUIRE(z->c == D && pm_vec_ok(z) && m >= 1 && m + 1 <= MAXM, PM_EUNSUPPORTED, "mem_write_accum: needs d == %d and <= %d slots", D, MAXM - 1);
   PM_REQUIRE(ws && ws_bytes >= pm_mem_write_accum_workspace(z, m), PM_EWORKSPACE, "mem_write_accum: workspace too small");
   const long rows = pm_pixels(z);
+  PM_REQUIRE(rows < (1l << 31), PM_EUNSUPPORTED, "mem_write_accum: the kernel divides row indices in 32 bits; needs fewer than 2^31 rows");
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)(m + 1) * (D + 1);
-  if (rows < (1l << 31)) {      // beyond that: the round-2 LDS-slab kernel
-    const int nb = accum_mfma_blocks(rows);
-    hipLaunchKernelGGL(mem_write_accum_mfma_kernel, dim3(nb), dim3(256), 0, st, (const float*)z->ptr, (long)z->pitch, z->n, z->h, z->w, labels, H, W, m, normalize,
-                       pm_ac_scale(H, z->h), pm_ac_scale(W, z->w), (float*)ws);
-    launch_reduce_partials((const float*)ws, nb, n, nomden, st);
-    return pm_check_launch("mem_write_accum");
-  }
-  const int nb = accum_blocks(rows);
-  const size_t lds = (size_t)ACC_W * ((m + 1) * D + MAXM) * sizeof(float);
-  static pm_lds_optin optin;
-  (void)optin(reinterpret_cast<const void*>(&mem_write_accum_kernel), 160 * 1024);
-  hipLaunchKernelGGL(mem_write_accum_kernel, dim3(nb), dim3(256), lds, st, (const float*)z->ptr, (long)z->pitch, z->n, z->h, z->w, labels, H, W, m, normalize,
+  const int nb = accum_mfma_blocks(rows);
+  hipLaunchKernelGGL(mem_write_accum_mfma_kernel, dim3(nb), dim3(256), 0, st, (const float*)z->ptr, (long)z->pitch, z->n, z->h, z->w, labels, H, W, m, normalize,
                      pm_ac_scale(H, z->h), pm_ac_scale(W, z->w), (float*)ws);
   launch_reduce_partials((const float*)ws, nb, n, nomden, st);
   return pm_check_launch("mem_write_accum");
