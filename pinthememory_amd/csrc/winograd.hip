@@ -5,15 +5,23 @@
 //
 // The element-wise product over channels is P = (m+2)^2 independent GEMMs [tiles x Cin] x [Cin x Cout], which run on the
 // implicit-GEMM kernel of conv_igemm.hip as a batched 1x1 convolution (blockIdx.y = transform point): 16 multiplies per 2x2 output
-// tile (2.25x fewer MFMA FLOPs than the direct algorithm) or 36 per 4x4 tile (4x fewer).  The transforms here are pure HBM
-// streaming kernels:
+// tile (2.25x fewer MFMA FLOPs than the direct algorithm) or 36 per 4x4 tile (4x fewer).  The transforms here are HBM streaming
+// kernels:
 //   input   x  [N,H,W,C]        -> V [P][tiles][Kp]   (Kp = C rounded up to 32 so that the GEMM's K-state stays wave-uniform)
-//   filter  w  [Cout,3,3,Cin]   -> U [P][Cout][Kp]    (or the 180-degree-rotated, channel-transposed filter for the data gradient)
+//   filter  w  [Cout,3,3,Cin]   -> U [P][Cout][Kp]    (or the 180-degree-rotated, channel-transposed filter for the data gradient;
+//                                                      staged through LDS; wino_filter_multi_kernel: every kept forward filter in one launch)
 //   output  M  [P][tiles][Cout] -> y [N,H,W,Cout]     (+ the fused epilogue: bias / affine / residual / ReLU)
 //   weight gradient: Z = A dY At [P][tiles][Cout];  dU[p] = Z[p]^T V[p] (batched wgrad GEMM, split-K slabs);  dw = Gt (sum dU) G
+// and, as an opt-in for F(4x4), wino_fused_f4_kernel: the 36 point GEMMs and the output transform in one kernel.
 // A dilated convolution (d > 1) is d*d independent undilated convolutions on the sub-lattices (y % d, x % d); the tile index
-// enumerates (image, sub-lattice, tile row, tile column) and the transforms address pixels as  r + d * (m t + a - 1).
+// enumerates (image, sub-lattice, tile row, tile column) and the transforms address pixels as  r + d * (m t + a + off)  (wino_pixel).
+//
+// Every transform is the same two passes, written once (wino_sandwich); a kernel is its load and its store. The (tile, channel
+// group) walk (wino_walk), the output tile with its epilogue (wino_output_tile, WinoEpilogue: the two-pass output kernel and the fused
+// kernel's tail) and the host's dispatch on m (wino_for_m) are written once as well.
 #include "pm_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -109,6 +117,29 @@ __device__ __forceinline__ void mat_apply(const Vec<W> (&in)[C], Vec<W> (&out)[R
   }
 }
 
+// The two-pass body of every transform, out = T in T^t for an RI x RI patch and the RO x RI matrix T = WHICH: the column pass over load(a, b) into a
+// temporary, then the row pass into store(a, b, v). What a transform reads and writes is its load and its store, each in one place.
+template <int MT, int WHICH, int RI, int RO, int W, class Load, class Store>
+__device__ __forceinline__ void wino_sandwich(Load load, Store store) {
+  Vec<W> t[RO][RI];
+#pragma unroll
+  for (int b = 0; b < RI; ++b) {   // T in, one patch column at a time
+    Vec<W> col[RI], o[RO];
+#pragma unroll
+    for (int a = 0; a < RI; ++a) col[a] = load(a, b);
+    mat_apply<MT, WHICH>(col, o);
+#pragma unroll
+    for (int a = 0; a < RO; ++a) t[a][b] = o[a];
+  }
+#pragma unroll
+  for (int a = 0; a < RO; ++a) {   // (T in) T^t
+    Vec<W> o[RO];
+    mat_apply<MT, WHICH>(t[a], o);
+#pragma unroll
+    for (int b = 0; b < RO; ++b) store(a, b, o[b]);
+  }
+}
+
 struct TileId {
   int n, ry, rx, ty, tx;
 };
@@ -124,103 +155,99 @@ __device__ __forceinline__ TileId decode_tile(unsigned tile, const pm_wino_geom&
   t.n = (int)(q / (unsigned)g.d);
   return t;
 }
-
-// thread -> (tile, W channels); W = 4 floats for m = 2, 2 floats for m = 4 (36 live values per lane)
-template <int MT, int W>
-__global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, long xp, int C, int Kp, const pm_wino_geom g, float* __restrict__ V) {
-  constexpr int A = MT + 2;
-  const unsigned kg = Kp / W;
-  const unsigned total = (unsigned)g.tiles * kg;
-  const long plane = g.tiles * (long)Kp;
+// element (a, b) of tile t's patch on its sub-lattice: the pixel index r + d * (m t + a + off) per axis (off = -1: the input patch with its halo, 0: the
+// m x m output tile) and whether it lies in the image
+template <int MT>
+__device__ __forceinline__ bool wino_pixel(const pm_wino_geom& g, const TileId& t, int a, int b, int off, long& pix) {
+  const int yy = t.ry + g.d * (MT * t.ty + a + off), xx = t.rx + g.d * (MT * t.tx + b + off);
+  pix = (long)(t.n * g.H + yy) * g.W + xx;
+  return (unsigned)yy < (unsigned)g.H && (unsigned)xx < (unsigned)g.W;
+}
+// grid-stride walk, thread -> (tile, W of `ch` channels); W = 4 floats for m = 2, 2 floats for m = 4 (36 live values per lane): body(tile, c)
+template <int W, class Body>
+__device__ __forceinline__ void wino_walk(const pm_wino_geom& g, int ch, Body body) {
+  const unsigned cg = ch / W;
+  const unsigned total = (unsigned)g.tiles * cg;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned tile = i / kg;
-    const int c = (int)(i - tile * kg) * W;
-    const TileId t = decode_tile(tile, g);
-    const bool cok = c < C;
-    Vec<W> tt[A][A];
-#pragma unroll
-    for (int b = 0; b < A; ++b) {   // Bt d, one patch column at a time
-      const int xx = t.rx + g.d * (MT * t.tx + b - 1);
-      const bool xok = cok && (unsigned)xx < (unsigned)g.W;
-      Vec<W> col[A], o[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        const int yy = t.ry + g.d * (MT * t.ty + a - 1);
-        col[a] = (xok && (unsigned)yy < (unsigned)g.H) ? vload<W>(x + ((long)(t.n * g.H + yy) * g.W + xx) * xp + c) : vzero<W>();
-      }
-      mat_apply<MT, W_BT>(col, o);
-#pragma unroll
-      for (int a = 0; a < A; ++a) tt[a][b] = o[a];
-    }
-    float* out = V + (long)tile * Kp + c;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {   // (Bt d) B
-      Vec<W> o[A];
-      mat_apply<MT, W_BT>(tt[a], o);
-#pragma unroll
-      for (int b = 0; b < A; ++b) vstore<W>(out + (a * A + b) * plane, o[b]);
-    }
+    const unsigned tile = i / cg;
+    body(tile, (int)(i - tile * cg) * W);
   }
 }
 
 template <int MT, int W>
-__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, int Cout, const pm_wino_geom g, float* __restrict__ y, long yp,
-                                                          const float* __restrict__ bias, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, const float* __restrict__ residual, long rp, int relu) {
+__global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, long xp, int C, int Kp, const pm_wino_geom g, float* __restrict__ V) {
   constexpr int A = MT + 2;
-  const unsigned cg = Cout / W;
-  const unsigned total = (unsigned)g.tiles * cg;
-  const long plane = g.tiles * (long)Cout;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned tile = i / cg;
-    const int c = (int)(i - tile * cg) * W;
+  const long plane = g.tiles * (long)Kp;
+  wino_walk<W>(g, Kp, [&](unsigned tile, int c) {
     const TileId t = decode_tile(tile, g);
-    const float* in = M + (long)tile * Cout + c;
-    Vec<W> s[MT][A];
-#pragma unroll
-    for (int b = 0; b < A; ++b) {   // At m
-      Vec<W> col[A], o[MT];
-#pragma unroll
-      for (int a = 0; a < A; ++a) col[a] = vload<W>(in + (a * A + b) * plane);
-      mat_apply<MT, W_AT>(col, o);
-#pragma unroll
-      for (int a = 0; a < MT; ++a) s[a][b] = o[a];
-    }
-    Vec<W> bi = vzero<W>(), sc = vzero<W>(), sh = vzero<W>();
-    if (bias) bi = vload<W>(bias + c);
-    if (scale) sc = vload<W>(scale + c), sh = vload<W>(shift + c);
-#pragma unroll
-    for (int a = 0; a < MT; ++a) {
-      const int yy = t.ry + g.d * (MT * t.ty + a);
-      Vec<W> o[MT];
-      mat_apply<MT, W_AT>(s[a], o);   // (At m) A
-#pragma unroll
-      for (int b = 0; b < MT; ++b) {
-        const int xx = t.rx + g.d * (MT * t.tx + b);
-        if (yy >= g.H || xx >= g.W) continue;
-        const long pix = (long)(t.n * g.H + yy) * g.W + xx;
-        Vec<W> v = o[b];
-        if (bias) {
-#pragma unroll
-          for (int q = 0; q < W; ++q) v.v[q] += bi.v[q];
-        }
-        if (scale) {
-#pragma unroll
-          for (int q = 0; q < W; ++q) v.v[q] = v.v[q] * sc.v[q] + sh.v[q];
-        }
-        if (residual) {
-          const Vec<W> rr = vload<W>(residual + pix * rp + c);
-#pragma unroll
-          for (int q = 0; q < W; ++q) v.v[q] += rr.v[q];
-        }
-        if (relu) {
-#pragma unroll
-          for (int q = 0; q < W; ++q) v.v[q] = fmaxf(v.v[q], 0.f);
-        }
-        vstore<W>(y + pix * yp + c, v);
-      }
-    }
+    float* out = V + (long)tile * Kp + c;
+    wino_sandwich<MT, W_BT, A, A, W>(   // Bt d B; the K padding and the halo outside the image read as 0
+        [&](int a, int b) {
+          long pix;
+          return (wino_pixel<MT>(g, t, a, b, -1, pix) && c < C) ? vload<W>(x + pix * xp + c) : vzero<W>();
+        },
+        [&](int a, int b, const Vec<W>& v) { vstore<W>(out + (a * A + b) * plane, v); });
+  });
+}
+
+// The fused epilogue of the output transform: y = relu((v + bias) * scale + shift + residual), every part optional. The per-channel vectors are loaded once per
+// (tile, channel group); residual and ReLU are applied per pixel.
+struct WinoEpilogueArgs {
+  const float* bias;
+  const float* scale;
+  const float* shift;
+  const float* residual;
+  long rp;
+  int relu;
+};
+template <int W>
+struct WinoEpilogue {
+  const WinoEpilogueArgs& e;
+  const int c;
+  Vec<W> bi = vzero<W>(), sc = vzero<W>(), sh = vzero<W>();
+  __device__ __forceinline__ WinoEpilogue(const WinoEpilogueArgs& e_, int c_) : e(e_), c(c_) {
+    if (e.bias) bi = vload<W>(e.bias + c);
+    if (e.scale) sc = vload<W>(e.scale + c), sh = vload<W>(e.shift + c);
   }
+  __device__ __forceinline__ Vec<W> operator()(Vec<W> v, long pix) const {
+    if (e.bias) {
+#pragma unroll
+      for (int q = 0; q < W; ++q) v.v[q] += bi.v[q];
+    }
+    if (e.scale) {
+#pragma unroll
+      for (int q = 0; q < W; ++q) v.v[q] = v.v[q] * sc.v[q] + sh.v[q];
+    }
+    if (e.residual) {
+      const Vec<W> rr = vload<W>(e.residual + pix * e.rp + c);
+#pragma unroll
+      for (int q = 0; q < W; ++q) v.v[q] += rr.v[q];
+    }
+    if (e.relu) {
+#pragma unroll
+      for (int q = 0; q < W; ++q) v.v[q] = fmaxf(v.v[q], 0.f);
+    }
+    return v;
+  }
+};
+// y = At m A + the epilogue for W channels (from c) of one tile, m read through load(a, b); output pixels beyond H / W are skipped
+template <int MT, int W, class Load>
+__device__ __forceinline__ void wino_output_tile(Load load, const pm_wino_geom& g, const TileId& t, int c, float* __restrict__ y, long yp, const WinoEpilogueArgs& e) {
+  const WinoEpilogue<W> ep(e, c);
+  wino_sandwich<MT, W_AT, MT + 2, MT, W>(load, [&](int a, int b, const Vec<W>& v) {
+    long pix;
+    if (wino_pixel<MT>(g, t, a, b, 0, pix)) vstore<W>(y + pix * yp + c, ep(v, pix));
+  });
+}
+
+template <int MT, int W>
+__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, int Cout, const pm_wino_geom g, float* __restrict__ y, long yp, const WinoEpilogueArgs e) {
+  constexpr int A = MT + 2;
+  const long plane = g.tiles * (long)Cout;
+  wino_walk<W>(g, Cout, [&](unsigned tile, int c) {
+    const float* in = M + (long)tile * Cout + c;
+    wino_output_tile<MT, W>([&](int a, int b) { return vload<W>(in + (a * A + b) * plane); }, g, decode_tile(tile, g), c, y, yp, e);
+  });
 }
 
 // U = G g Gt for a 32 (rows of the GEMM's B) x 32 (its K) block of filters, staged through LDS so that both the KRSC read and the
@@ -248,31 +275,20 @@ __device__ __forceinline__ void wino_filter_block(const float* __restrict__ w, i
   const int j = threadIdx.x >> 3, q = threadIdx.x & 7;
   const int row = r0 + j, k = k0 + 4 * q;
   if (row >= R || k >= Kp) return;
-  Vec<4> gg[A][3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) {   // G g
-    Vec<4> col[3], o[A];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) col[ky].v[e] = DGRAD ? sg[(2 - ky) * 3 + (2 - kx)][4 * q + e][j] : sg[ky * 3 + kx][j][4 * q + e];
-    mat_apply<MT, W_G>(col, o);
-#pragma unroll
-    for (int a = 0; a < A; ++a) gg[a][kx] = o[a];
-  }
   float* out = U + (long)row * Kp + k;
+  wino_sandwich<MT, W_G, 3, A, 4>(   // G g Gt
+      [&](int ky, int kx) {
+        Vec<4> v;
 #pragma unroll
-  for (int a = 0; a < A; ++a) {      // (G g) Gt
-    Vec<4> o[A];
-    mat_apply<MT, W_G>(gg[a], o);
+        for (int e = 0; e < 4; ++e) v.v[e] = DGRAD ? sg[(2 - ky) * 3 + (2 - kx)][4 * q + e][j] : sg[ky * 3 + kx][j][4 * q + e];
+        return v;
+      },
+      [&](int a, int b, Vec<4> v) {
 #pragma unroll
-    for (int b = 0; b < A; ++b) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (k + e >= Kr) o[b].v[e] = 0.f;   // zero fill of the K padding
-      vstore<4>(out + (a * A + b) * plane, o[b]);
-    }
-  }
+        for (int e = 0; e < 4; ++e)
+          if (k + e >= Kr) v.v[e] = 0.f;   // zero fill of the K padding
+        vstore<4>(out + (a * A + b) * plane, v);
+      });
 }
 template <int MT, bool DGRAD>
 __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restrict__ w, int Cout, int Cin, int Kp, float* __restrict__ U) {
@@ -307,36 +323,17 @@ __global__ __launch_bounds__(256) void wino_filter_multi_kernel(const WinoRefres
 template <int MT, int W>
 __global__ __launch_bounds__(256) void wino_dy_kernel(const float* __restrict__ dy, long yp, int Cout, const pm_wino_geom g, float* __restrict__ Z) {
   constexpr int A = MT + 2;
-  const unsigned cg = Cout / W;
-  const unsigned total = (unsigned)g.tiles * cg;
   const long plane = g.tiles * (long)Cout;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned tile = i / cg;
-    const int c = (int)(i - tile * cg) * W;
+  wino_walk<W>(g, Cout, [&](unsigned tile, int c) {
     const TileId t = decode_tile(tile, g);
-    Vec<W> r[A][MT];
-#pragma unroll
-    for (int b = 0; b < MT; ++b) {   // A dY
-      const int xx = t.rx + g.d * (MT * t.tx + b);
-      Vec<W> col[MT], o[A];
-#pragma unroll
-      for (int a = 0; a < MT; ++a) {
-        const int yy = t.ry + g.d * (MT * t.ty + a);
-        col[a] = (yy < g.H && xx < g.W) ? vload<W>(dy + ((long)(t.n * g.H + yy) * g.W + xx) * yp + c) : vzero<W>();
-      }
-      mat_apply<MT, W_A>(col, o);
-#pragma unroll
-      for (int a = 0; a < A; ++a) r[a][b] = o[a];
-    }
     float* out = Z + (long)tile * Cout + c;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {   // (A dY) At
-      Vec<W> o[A];
-      mat_apply<MT, W_A>(r[a], o);
-#pragma unroll
-      for (int b = 0; b < A; ++b) vstore<W>(out + (a * A + b) * plane, o[b]);
-    }
-  }
+    wino_sandwich<MT, W_A, MT, A, W>(   // A dY At
+        [&](int a, int b) {
+          long pix;
+          return wino_pixel<MT>(g, t, a, b, 0, pix) ? vload<W>(dy + pix * yp + c) : vzero<W>();
+        },
+        [&](int a, int b, const Vec<W>& v) { vstore<W>(out + (a * A + b) * plane, v); });
+  });
 }
 
 // Weight gradient, step 3: fixed-order sum of the split-K slabs [ks][P][Cout][Kp] and dw = Gt dU G -> KRSC [Cout][3][3][Cin].
@@ -359,24 +356,9 @@ __global__ __launch_bounds__(256) void wino_dw_kernel(const float* __restrict__ 
 #pragma unroll
       for (int q = 0; q < P; ++q) du[q] += ld[q];
     }
-    Vec<1> h[3][A];
-#pragma unroll
-    for (int b = 0; b < A; ++b) {   // Gt dU
-      Vec<1> col[A], o[3];
-#pragma unroll
-      for (int a = 0; a < A; ++a) col[a].v[0] = du[a * A + b];
-      mat_apply<MT, W_GT>(col, o);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) h[k][b] = o[k];
-    }
     float* out = dw + (long)co * 9 * Cin + ci;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {   // (Gt dU) G
-      Vec<1> o[3];
-      mat_apply<MT, W_GT>(h[k], o);
-#pragma unroll
-      for (int l = 0; l < 3; ++l) out[(k * 3 + l) * (long)Cin] = o[l].v[0];
-    }
+    wino_sandwich<MT, W_GT, A, 3, 1>(   // Gt dU G
+        [&](int a, int b) { return Vec<1>{{du[a * A + b]}}; }, [&](int k, int l, const Vec<1>& v) { out[(k * 3 + l) * (long)Cin] = v.v[0]; });
   }
 }
 
@@ -385,8 +367,8 @@ __global__ __launch_bounds__(256) void wino_dw_kernel(const float* __restrict__ 
 // (v_mfma_f32_32x32x2_f32, exact fp32 chain) per point = 48 accumulator registers per lane. K (input channels) runs outermost in slabs of 16:
 // per slab the block stages 36 x (32 tile rows of V + 32 channel rows of U) x 64 B = 144 KB in LDS (16-byte chunks XOR-swizzled by (row >> 2) & 3:
 // conflict-free ds_read_b128 without padding), next slab's rows prefetched to registers under the MFMAs. After the K loop the accumulators are
-// parked in the same LDS as M[36][32][32 (+1)] and every (tile, channel) pair applies y = At M A + the fused epilogue (bias / affine / residual /
-// ReLU, same expressions as wino_output_kernel), stores leave as 128-byte channel runs. Against GEMM + wino_output_kernel this removes the write
+// parked in the same LDS as M[36][32][32 (+1)] and every (tile, channel) pair applies y = At M A + the fused epilogue (wino_output_tile, the body
+// of wino_output_kernel at one channel per thread), stores leave as 128-byte channel runs. Against GEMM + wino_output_kernel this removes the write
 // and the read of M (2.25 x the output each) and one launch; the price is U / V re-read from L2 (Cout / 32 and tiles / 32 times).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -397,13 +379,8 @@ struct WinoFusedArgs {
   long yp;
   int Cout, Kp;
   pm_wino_geom g;
-  const float* bias;
-  const float* scale;
-  const float* shift;
-  const float* residual;
-  long rp;
-  int relu;
-  int ncb;             // channel blocks (Cout / 32, rounded up); gridDim.x = tile blocks * ncb
+  WinoEpilogueArgs ep;
+  int ncb;            // channel blocks (Cout / 32, rounded up); gridDim.x = tile blocks * ncb
 };
 
 constexpr int WF_THREADS = 768, WF_TB = 32, WF_CB = 32, WF_BK = 16, WF_P = 36;
@@ -496,46 +473,24 @@ __global__ __launch_bounds__(WF_THREADS) void wino_fused_f4_kernel(const WinoFus
     for (int q = 0; q < 16; ++q) Ms[(pnt * WF_TB + (q & 3) + 8 * (q >> 2) + 4 * half) * (WF_CB + 1) + l31] = acc[j][q];
   }
   __syncthreads();
-  constexpr int MT = 4, A = 6;
   for (int idx = tid; idx < WF_TB * WF_CB; idx += WF_THREADS) {
     const int t = idx >> 5, c = idx & 31;
     const long tile = tile0 + t;
     const int co = co0 + c;
     if (tile >= a.g.tiles || co >= a.Cout) continue;
-    const TileId ti = decode_tile((unsigned)tile, a.g);
-    Vec<1> sv[MT][A];
-#pragma unroll
-    for (int b = 0; b < A; ++b) {   // At m
-      Vec<1> col[A], o[MT];
-#pragma unroll
-      for (int aa = 0; aa < A; ++aa) col[aa].v[0] = Ms[((aa * A + b) * WF_TB + t) * (WF_CB + 1) + c];
-      mat_apply<MT, W_AT>(col, o);
-#pragma unroll
-      for (int aa = 0; aa < MT; ++aa) sv[aa][b] = o[aa];
-    }
-    const float bi = a.bias ? a.bias[co] : 0.f, sc = a.scale ? a.scale[co] : 0.f, sh = a.scale ? a.shift[co] : 0.f;
-#pragma unroll
-    for (int aa = 0; aa < MT; ++aa) {
-      const int yy = ti.ry + a.g.d * (MT * ti.ty + aa);
-      Vec<1> o[MT];
-      mat_apply<MT, W_AT>(sv[aa], o);   // (At m) A
-#pragma unroll
-      for (int b = 0; b < MT; ++b) {
-        const int xx = ti.rx + a.g.d * (MT * ti.tx + b);
-        if (yy >= a.g.H || xx >= a.g.W) continue;
-        const long pix = (long)(ti.n * a.g.H + yy) * a.g.W + xx;
-        float v = o[b].v[0];
-        if (a.bias) v += bi;
-        if (a.scale) v = v * sc + sh;
-        if (a.residual) v += a.residual[pix * a.rp + co];
-        if (a.relu) v = fmaxf(v, 0.f);
-        a.y[pix * a.yp + co] = v;
-      }
-    }
+    wino_output_tile<4, 1>([&](int aa, int b) { return vload<1>(Ms + ((aa * 6 + b) * WF_TB + t) * (WF_CB + 1) + c); }, a.g, decode_tile((unsigned)tile, a.g), co, a.y,
+                           a.yp, a.ep);
   }
 }
 
 inline unsigned nblocks(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1 << 20); }
+
+// f(MT, W) as compile-time constants for a run-time m: F(4x4) with 2 channels per thread, F(2x2) with 4
+template <class F>
+inline void wino_for_m(int m, F f) {
+  if (m == 4) f(std::integral_constant<int, 4>(), std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 2>(), std::integral_constant<int, 4>());
+}
 
 }  // namespace
 
@@ -548,21 +503,21 @@ pm_wino_geom pm_wino_make_geom(int n, int h, int w, int d, int m) {
 }
 
 int pm_wino_input_xf(const float* x, long pitch, int C, int Kp, const pm_wino_geom& g, float* V, hipStream_t st) {
-  if (g.m == 4) hipLaunchKernelGGL((wino_input_kernel<4, 2>), dim3(nblocks(g.tiles * (Kp / 2))), dim3(256), 0, st, x, pitch, C, Kp, g, V);
-  else hipLaunchKernelGGL((wino_input_kernel<2, 4>), dim3(nblocks(g.tiles * (Kp / 4))), dim3(256), 0, st, x, pitch, C, Kp, g, V);
+  wino_for_m(g.m, [&](auto mt, auto cw) {
+    constexpr int MT = mt, W = cw;
+    hipLaunchKernelGGL((wino_input_kernel<MT, W>), dim3(nblocks(g.tiles * (Kp / W))), dim3(256), 0, st, x, pitch, C, Kp, g, V);
+  });
   return pm_check_launch("wino_input");
 }
 
 int pm_wino_filter_xf(const float* w, int Cout, int Cin, int Kp, bool dgrad, int m, float* U, hipStream_t st) {
   const int R = dgrad ? Cin : Cout;
   dim3 grid(Kp / 32, pm_cdiv(R, 32));
-  if (m == 4) {
-    if (dgrad) hipLaunchKernelGGL((wino_filter_kernel<4, true>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
-    else hipLaunchKernelGGL((wino_filter_kernel<4, false>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
-  } else {
-    if (dgrad) hipLaunchKernelGGL((wino_filter_kernel<2, true>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
-    else hipLaunchKernelGGL((wino_filter_kernel<2, false>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
-  }
+  wino_for_m(m, [&](auto mt, auto) {
+    constexpr int MT = mt;
+    if (dgrad) hipLaunchKernelGGL((wino_filter_kernel<MT, true>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
+    else hipLaunchKernelGGL((wino_filter_kernel<MT, false>), grid, dim3(256), 0, st, w, Cout, Cin, Kp, U);
+  });
   return pm_check_launch("wino_filter");
 }
 
@@ -587,25 +542,28 @@ int pm_wino_filter_xf_multi(const float* const* w, float* const* U, const int* c
 
 int pm_wino_output_xf(const float* M, int Cout, const pm_wino_geom& g, float* y, long ypitch, const float* bias, const float* scale, const float* shift,
                       const float* residual, long res_pitch, int relu, hipStream_t st) {
-  if (g.m == 4)
-    hipLaunchKernelGGL((wino_output_kernel<4, 2>), dim3(nblocks(g.tiles * (Cout / 2))), dim3(256), 0, st, M, Cout, g, y, ypitch, bias, scale, shift, residual,
-                       res_pitch, relu);
-  else
-    hipLaunchKernelGGL((wino_output_kernel<2, 4>), dim3(nblocks(g.tiles * (Cout / 4))), dim3(256), 0, st, M, Cout, g, y, ypitch, bias, scale, shift, residual,
-                       res_pitch, relu);
+  const WinoEpilogueArgs e = {bias, scale, shift, residual, res_pitch, relu};
+  wino_for_m(g.m, [&](auto mt, auto cw) {
+    constexpr int MT = mt, W = cw;
+    hipLaunchKernelGGL((wino_output_kernel<MT, W>), dim3(nblocks(g.tiles * (Cout / W))), dim3(256), 0, st, M, Cout, g, y, ypitch, e);
+  });
   return pm_check_launch("wino_output");
 }
 
 int pm_wino_dy_xf(const float* dy, long pitch, int Cout, const pm_wino_geom& g, float* Z, hipStream_t st) {
-  if (g.m == 4) hipLaunchKernelGGL((wino_dy_kernel<4, 2>), dim3(nblocks(g.tiles * (Cout / 2))), dim3(256), 0, st, dy, pitch, Cout, g, Z);
-  else hipLaunchKernelGGL((wino_dy_kernel<2, 4>), dim3(nblocks(g.tiles * (Cout / 4))), dim3(256), 0, st, dy, pitch, Cout, g, Z);
+  wino_for_m(g.m, [&](auto mt, auto cw) {
+    constexpr int MT = mt, W = cw;
+    hipLaunchKernelGGL((wino_dy_kernel<MT, W>), dim3(nblocks(g.tiles * (Cout / W))), dim3(256), 0, st, dy, pitch, Cout, g, Z);
+  });
   return pm_check_launch("wino_dy");
 }
 
 int pm_wino_dw_xf(const float* slab, int ks, int Cout, int Cin, int Kp, int m, float* dw, hipStream_t st) {
   const unsigned nb = (unsigned)std::min<long>(((long)Cout * Cin + 255) / 256, 1 << 16);
-  if (m == 4) hipLaunchKernelGGL(wino_dw_kernel<4>, dim3(nb), dim3(256), 0, st, slab, ks, Cout, Cin, Kp, dw);
-  else hipLaunchKernelGGL(wino_dw_kernel<2>, dim3(nb), dim3(256), 0, st, slab, ks, Cout, Cin, Kp, dw);
+  wino_for_m(m, [&](auto mt, auto) {
+    constexpr int MT = mt;
+    hipLaunchKernelGGL(wino_dw_kernel<MT>, dim3(nb), dim3(256), 0, st, slab, ks, Cout, Cin, Kp, dw);
+  });
   return pm_check_launch("wino_dw");
 }
 
@@ -616,7 +574,7 @@ int pm_wino_fused_f4(const float* V, const float* U, int Cout, int Kp, const pm_
   (void)optin(reinterpret_cast<const void*>(&wino_fused_f4_kernel), (int)WF_LDS);
   WinoFusedArgs a;
   a.V = V, a.U = U, a.y = y, a.yp = ypitch, a.Cout = Cout, a.Kp = Kp, a.g = g;
-  a.bias = bias, a.scale = scale, a.shift = shift, a.residual = residual, a.rp = res_pitch, a.relu = relu;
+  a.ep = {bias, scale, shift, residual, res_pitch, relu};
   a.ncb = (Cout + WF_CB - 1) / WF_CB;
   const long ntb = (g.tiles + WF_TB - 1) / WF_TB;
   hipLaunchKernelGGL(wino_fused_f4_kernel, dim3((unsigned)(ntb * a.ncb)), dim3(WF_THREADS), WF_LDS, st, a);

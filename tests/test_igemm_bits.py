@@ -1,8 +1,11 @@
 """Every output bit of the implicit-GEMM convolution kernel (csrc/conv_igemm_kernel.h and the pieces it is put together from, through conv_igemm.hip and
 conv_split.hip), of the streaming pointwise kernel (csrc/pwstream.hip) and of the split-K reduce, through pm_conv_fwd / pm_conv_bwd_data(_masked) /
 pm_conv_bwd_weight, against tests/golden/igemm_bits.json: recorded by tools/record_igemm_bits.py from the commit BEFORE the kernel's tile map, LDS layouts, window
-gather and epilogues were written once (csrc/conv_igemm_parts.h). The inputs are built by the recorder's own functions; the kernels are deterministic (fixed-order
-split-K reduce), so the digests have to be equal -- and the launches each case makes have to be the ones that were recorded."""
+gather and epilogues were written once (csrc/conv_igemm_parts.h). The 'wino-*' cases hold the Winograd transforms (csrc/winograd.hip) the same way, on maps that do
+not tile -- ragged edge tiles, dilation sub-lattices of unequal size, zero-filled K padding, every fused epilogue, the split-K slab sum of the weight gradient, F(4 x 4),
+F(2 x 2) and the fused kernel: recorded from the commit BEFORE the transforms' two-pass body and the output epilogue were written once (wino_sandwich,
+wino_epilogue). The inputs are built by the recorder's own functions; the kernels are deterministic (fixed-order split-K reduce), so the digests have to be equal --
+and the launches each case makes have to be the ones that were recorded."""
 import importlib.util
 import json
 import os

@@ -10,7 +10,9 @@ Record against a library built from the PARENT of the change under test (tools/b
 The calls go through conv_fwd / conv_bwd_data / conv_bwd_weight (hip/kernels.py) under five configurations (CONFIGS below): the fp32 tier with default routing
 (operands split into three bf16 pieces where the reduction allows: PREC 5) and with routing(split=0) (fp32 MFMA: PREC 0), fp32 tensors rounded per fragment
 ('bf16_staged': PREC 1), bf16 operands over fp32 activations ('bf16_operands': PREC 2, weight gradient PREC 3) and the bf16 tier with the LDS-DMA kernels
-switched off (PREC 2 with bf16 output, weight gradients PREC 4 / 3, the parity-class data gradient on a widened dy). Inputs come from CPU generators with fixed
+switched off (PREC 2 with bf16 output, weight gradients PREC 4 / 3, the parity-class data gradient on a widened dy). Two more take the fp32 tier through the Winograd
+transforms (csrc/winograd.hip) on maps that do not tile: 'wino2' (routing(winograd=2): F(2 x 2) where the default takes F(4 x 4)) and 'fused' (routing(winograd_fused=1):
+wino_fused_f4_kernel, recorded as mode 3) -- their digests hold every transform's bits, epilogue, ragged edges, K padding and slab sum included. Inputs come from CPU generators with fixed
 seeds. Beside the digests the in-library profile's record of each call is kept ('reach': mode/bm/bn/km/nst/prec/batch/ksplit per launch) and check_reach holds
 it to the form the case is named for -- the planner rules the cases were laid out by are proven by that, not assumed."""
 import hashlib
@@ -31,6 +33,8 @@ CONFIGS = {
     'operands': ('bf16_operands', dict(conv16=0)),
     'bf16': ('bf16', dict(conv16=0)),
     'bf16-small': ('bf16', dict()),      # default routing: fewer than 256 output pixels stay with the register-staged kernel
+    'wino2': ('f32', dict(winograd=2)),      # F(2 x 2) wherever the Winograd route is taken
+    'fused': ('f32', dict(winograd_fused=1)),      # F(4 x 4): point products and output transform in one kernel (wino_fused_f4_kernel)
 }
 REACH_KEYS = ('mode', 'bm', 'bn', 'km', 'nst', 'prec', 'batch', 'ksplit')
 FAST, MID, SMALL, PW, STREAM = 0, 1, 2, 3, 4      # the km column (K_FAST ... K_PW of the kernel; 4: the streaming pointwise kernel's records)
@@ -130,6 +134,27 @@ PWS = dict(bm=32, bn=64, km=STREAM, nst=0, prec=5, batch=1, ksplit=1)
 fwd('stream-64-64', 'split', (1, 64, 256, 256), 64, expect=dict(mode=0, **PWS))
 fwd('stream-128-256', 'split', (1, 128, 256, 256), 256, 'affine', expect=dict(mode=0, **PWS))
 dgrad('stream-64-64', 'split', (1, 64, 256, 256), 64, 'mask', expect=dict(mode=1, **PWS))
+
+# ---- the Winograd transforms (csrc/winograd.hip) where a map does not tile: F(4 x 4) under default routing, F(2 x 2) under routing(winograd=2) ----
+# 132 -> 140 channels on 13 x 15: ragged edge tiles in both axes, K padded 132 -> 160 (zero-filled in V and U), a ragged column tile, output rows beyond H / W
+# skipped. Dilation 2: sub-lattices of 7 / 6 rows and 8 / 7 columns, so the edge tiles differ per sub-lattice (multiplies ratio 0.328 for F(4 x 4), 0.583 for F(2 x 2)).
+# The weight gradient takes the route from 256 x 256 channels up (260 -> Kp 288): one slab on 13 x 15, and on 63 x 65 the fixed-order slab sum of wino_dw_kernel
+# (F(4 x 4): 544 tiles, 17 K-steps, two slabs; F(2 x 2): 2112 tiles, 66 K-steps, five).
+WX = (2, 132, 13, 15)
+D2 = dict(k=3, pad=2, dil=2)
+for cfg, batch, ks in (('split', 36, 2), ('wino2', 16, 5)):
+    for ep in ('plain', 'bias', 'affine'):
+        fwd('wino-132-140', cfg, WX, 140, ep, expect=E(0, batch=batch), **C3)
+    for add in ('none', 'add'):
+        dgrad('wino-132-140', cfg, WX, 140, add, expect=E(0, batch=batch), **C3)
+    fwd('wino-132-140-d2', cfg, WX, 140, 'affine', expect=E(0, batch=batch), **D2)
+    dgrad('wino-132-140-d2', cfg, WX, 140, expect=E(0, batch=batch), **D2)
+    wgrad('wino-260-256', cfg, (1, 260, 13, 15), 256, dbias=True, expect=E(2, batch=batch, ksplit=1), **C3)
+    wgrad('wino-260-256-slabs', cfg, (2, 260, 63, 65), 256, expect=E(2, batch=batch, ksplit=ks), **C3)
+# the fused kernel (recorded as mode 3): 48 tiles are one full and one half tile block; 140 channels are five channel blocks, the last 12 wide, the data gradient's 132
+# leave it 4 wide
+fwd('wino-132-140', 'fused', (3, 132, 13, 15), 140, 'affine', expect=E(3, batch=36), **C3)
+dgrad('wino-132-140', 'fused', (3, 132, 13, 15), 140, expect=E(3, batch=36), **C3)
 
 # ---- fp32 tiles rounded to bf16 per fragment (PREC 1) ----
 fwd('3x3-64-64', 'staged', S(64), 64, 'affine', expect=E(0, prec=1), **C3)
