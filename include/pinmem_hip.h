@@ -55,7 +55,7 @@ typedef struct pm_tensor {      /* NHWC activation view */
  * 440: sliding-window evaluation (pm_sliding_eval, pm_sliding_eval_finish, pm_sliding_eval_workspace).
  * 450: the evaluation input edge (pm_resize_axis_tables, pm_eval_tiles_u8), PM_FILTER_*.
  * 460: per-image normalisation of the IBN trunks (pm_instnorm_workspace, pm_instnorm_fwd, pm_instnorm_bwd).
- * The ablation sweep (pm_label_splat, pm_class_sums_workspace, pm_class_sums, pm_mem_actmap) arrived WITHOUT a version step: the number tracks the layouts of the
+ * The ablation sweep (pm_label_splat, pm_class_sums_workspace, pm_class_sums, pm_mem_actmap) and the evaluation image dumps (pm_eval_dump) arrived WITHOUT a version step: the number tracks the layouts of the
  * structs above, those entry points take raw pointers and sizes only and no struct changed; a caller finds out whether a library has them by looking the symbols up. */
 #define PM_ABI_VERSION 460
 
@@ -386,6 +386,24 @@ int pm_sliding_eval(const float* logits, int n, int h, int w, int C, int64_t pit
                     double* acc /*nullable*/, int acc_add, void* ws, size_t ws_bytes, void* stream);
 int pm_sliding_eval_finish(const double* acc, int C, int H, int W, int nscales, const int64_t* labels /*nullable*/, int64_t* hist, int accumulate,
                            uint8_t* pred /*nullable*/, double* logits_out /*nullable*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- evaluation image dumps (eval.py:664-693 RunEval.inf under --dump_images; csrc/eval_dump.hip) -----------------------------------------------------------------
+ * The four images the reference writes per evaluated image, from the uint8 class map the evaluation kernels leave on the device (pm_sliding_eval's pred), in one
+ * streaming pass over pixels = n * H * W dense pixels; no geometry, no workspace, no atomics: the same bytes from run to run. All pointers are device memory.
+ *   color   uint8 [pixels][3] = palette[pred] (colorize_mask; palette: uint8 [256][3] RGB, all 256 rows are read -- the library ships no colour table).
+ *   compose uint8 [pixels][3] = Image.blend(image, color, alpha) per colour channel with PIL's bytes, (uint8)((float)i + alpha * (float)(c - i)) in fp32, truncated
+ *           (pm_mem_actmap's blend); image: uint8 [pixels][3]. The reference's alpha is 0.5; an alpha outside [0, 1] clips as PIL does.
+ *   diff    uint8 [pixels][3] = ImageChops.lighter(compose, invert(diff mask)): the compose pixel where labels != 255 and labels != pred, else (255, 255, 255).
+ *           labels: int64 [pixels] train ids; a value that is neither a class nor 255 counts as a difference, as in the reference.
+ *   ids     uint8 [pixels] = id_table[pred] (the reference's loop over id_to_trainid; id_table: uint8 [256]).
+ * The alpha channel of the reference's RGBA images is constantly 255 and is not written. Each output is nullable, any non-empty subset; an input is read only where a
+ * requested output needs it. A thread moves 4 pixels as aligned dwords; a pred or ids pointer that is not 4-byte aligned sends the call to the one-pixel path
+ * (same bytes, slower).
+ * Before any launch -- PM_EINVAL: null pred, pixels <= 0, no output, color / compose / diff without palette, compose / diff without image, diff without labels, ids
+ * without id_table, a non-finite alpha, image / color / compose / diff not 4-byte aligned, labels not 8-byte aligned. */
+int pm_eval_dump(const uint8_t* pred, int64_t pixels, const uint8_t* palette /*[256][3], nullable*/, const uint8_t* image /*[pixels][3], nullable*/,
+                 const int64_t* labels /*nullable*/, const uint8_t* id_table /*[256], nullable*/, float alpha, uint8_t* color /*nullable*/, uint8_t* compose /*nullable*/,
+                 uint8_t* diff /*nullable*/, uint8_t* ids /*nullable*/, void* stream);
 
 /* ---- ablation sweep (ablation.py:292-399 RunAbla.tsne_memact, tsnelib.py:48-74 RunTsne.input2basket; csrc/ablation.hip) ------------------------------------------
  * The per-class feature sums behind the t-SNE prototypes and the memory activation maps, from LOW-RES tensors: neither the up-sampled feature map ([256][H][W]) nor the

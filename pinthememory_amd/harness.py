@@ -658,21 +658,82 @@ def eval_metrics(hist):
     return torch.stack([diag.sum() / total, torch.nanmean(diag / rows), torch.nanmean(iu), torch.where(freq > 0, freq * iu, torch.zeros_like(iu)).sum()])
 
 
-def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, classes=19, dump=0, device_tiles=False):
-    """The loop of eval.py:756-779 over RunEval.inf (:630-653) and final_dump (:695-702) without the image files: `loader` yields (image, gt, ...) with the image
+def _dump_tables(who, palette, id_to_trainid):
+    """The host halves of what K.eval_dump reads per call: the checked palette and the label-id table (None without id_to_trainid). No device involved."""
+    if palette is None:
+        raise ValueError('%s: on_images needs the palette (uint8 [256, 3] RGB) -- the library ships no colour table' % who)
+    palette = torch.as_tensor(palette)
+    if palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3):
+        raise ValueError('%s: the palette is uint8 [256, 3] (got %s %s)' % (who, palette.dtype, tuple(palette.shape)))
+    return palette, None if id_to_trainid is None else K.trainid_table(id_to_trainid)
+
+
+def _dump_source(who, img):
+    """One loader image -> uint8 [H, W, 3]: the bytes the composed image blends with."""
+    img = img[0] if img.dim() == 4 else img
+    if img.dtype != torch.uint8:
+        raise ValueError('%s: image dumps blend the uint8 [H, W, 3] source image; a normalised float image has no bytes to blend' % who)
+    assert img.dim() == 3 and img.shape[2] == 3, 'uint8 images are [H, W, 3]'
+    return img
+
+
+def evaluate(net, loader, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, classes=19, dump=0, device_tiles=False, on_images=None, palette=None,
+             id_to_trainid=None, alpha=0.5):
+    """The loop of eval.py:756-779 over RunEval.inf (:630-653) and final_dump (:695-702); the image files of --dump_images are the caller's, from what on_images hands out: `loader` yields (image, gt, ...) with the image
     uint8 [H, W, 3] (or [1, H, W, 3]) and gt [H, W] (or [1, H, W]); every image goes through evaluate_sliding into ONE histogram on the device, and nothing is
     copied to the host before the last image. -> dict(hist int64 [classes, classes] on the device, acc, acc_cls, mean_iu, fwavacc as evaluate_eval_for_inference
-    computes them, predictions: the uint8 class maps of the first `dump` images). device_tiles: as evaluate_sliding takes it."""
+    computes them, predictions: the uint8 class maps of the first `dump` images). device_tiles: as evaluate_sliding takes it.
+    on_images (--dump_images, eval.py:664-693): called as on_images(idx, data, images) per image, `data` the loader's item and `images` K.eval_dump's dict of device
+    tensors for the image's class map, source image and gt -- 'color', 'compose', 'diff' [H, W, 3] and, with id_to_trainid (the dataset's dict), 'ids' [H, W].
+    palette: uint8 [256, 3] RGB, required with on_images; alpha: the blend's. Palette and id table go to the device once; the harness copies nothing to the host,
+    encoding and files stay with the caller. A float image raises ValueError with on_images."""
+    if on_images is not None:
+        palette, id_table = _dump_tables('evaluate', palette, id_to_trainid)
     m = net.module if hasattr(net, 'module') else net
-    hist = torch.zeros((classes, classes), dtype=torch.int64, device=next(m.parameters()).device)
+    device = next(m.parameters()).device
+    if on_images is not None:
+        palette, id_table = palette.to(device).contiguous(), None if id_table is None else id_table.to(device)
+    hist = torch.zeros((classes, classes), dtype=torch.int64, device=device)
     predictions = []
     for idx, data in enumerate(loader):
         img, gt = data[0], data[1]
-        res = evaluate_sliding(net, img[0] if img.dim() == 4 else img, gt, crop, scales, overlap, (False,) if no_flip else (False, True), hist=hist, device_tiles=device_tiles)
+        img = img[0] if img.dim() == 4 else img
+        if on_images is not None:
+            src = _dump_source('evaluate', img).to(device).contiguous()
+            if device_tiles:
+                img = src      # one upload serves the tiles and the blend
+        res = evaluate_sliding(net, img, gt, crop, scales, overlap, (False,) if no_flip else (False, True), hist=hist, device_tiles=device_tiles)
         if idx < dump:
             predictions.append(res['pred'])
+        if on_images is not None:
+            labels = gt.to(device=device, dtype=torch.int64).reshape(src.shape[:2]).contiguous()
+            want = ('color', 'compose', 'diff') + (('ids',) if id_table is not None else ())
+            on_images(idx, data, K.eval_dump(res['pred'], palette=palette, image=src, labels=labels, id_table=id_table, alpha=alpha, want=want))
     acc, acc_cls, mean_iu, fwavacc = eval_metrics(hist).tolist()
     return dict(hist=hist, acc=acc, acc_cls=acc_cls, mean_iu=mean_iu, fwavacc=fwavacc, predictions=predictions)
+
+
+def segment_folder(net, loader, on_images, palette, id_to_trainid=None, crop=768, scales=(1.0,), overlap=1.0 / 3, no_flip=False, alpha=0.5, device_tiles=False):
+    """The `video_folder` loop of eval.py:757-779 (eval_custumfolder_pinmem_DR50V3P.sh): images without ground truth, so no histogram, no metrics and no diff image --
+    the colourised frames and overlays are the whole product. `loader` yields a uint8 [H, W, 3] (or [1, H, W, 3]) image, or a tuple / list whose first item is one
+    (the reference's (imgs, img_names)). Every image goes through evaluate_sliding(gt=None) and K.eval_dump, and on_images(idx, data, images) receives the loader's
+    item and the device tensors 'color', 'compose' [H, W, 3] and, with id_to_trainid, 'ids' [H, W]. palette, alpha, device_tiles: as evaluate takes them.
+    -> the number of images."""
+    palette, id_table = _dump_tables('segment_folder', palette, id_to_trainid)
+    if on_images is None:
+        raise ValueError('segment_folder: on_images is the only product of this loop')
+    m = net.module if hasattr(net, 'module') else net
+    device = next(m.parameters()).device
+    palette, id_table = palette.to(device).contiguous(), None if id_table is None else id_table.to(device)
+    want = ('color', 'compose') + (('ids',) if id_table is not None else ())
+    count = 0
+    for idx, data in enumerate(loader):
+        img = _dump_source('segment_folder', data[0] if isinstance(data, (tuple, list)) else data)
+        src = img.to(device).contiguous()
+        res = evaluate_sliding(net, src if device_tiles else img, None, crop, scales, overlap, (False,) if no_flip else (False, True), device_tiles=device_tiles)
+        on_images(idx, data, K.eval_dump(res['pred'], palette=palette, image=src, id_table=id_table, alpha=alpha, want=want))
+        count += 1
+    return count
 
 
 # ---- the ablation sweep: ablation.py RunAbla.tsne_memact (:317-399) with tsnelib.py RunTsne (:48-96), without t-SNE, figures and files ------------------------

@@ -864,6 +864,47 @@ def mem_actmap(p_mem, nhw, size, slots, palette=None, image=None, alpha=0.65, wa
     return res
 
 
+DUMP_OUTPUTS = ('color', 'compose', 'diff', 'ids')
+
+
+def trainid_table(id_to_trainid):
+    """The label-id map of eval.py:690-692 as a table: uint8 [256] on the host with table[train_id] = label_id, 0 where no entry names the value; where several
+    ids share a train id the LAST one in the dict's order wins, as in the reference's loop. An entry whose train id lies outside 0 .. 255 is skipped (the reference's
+    `pred == -1` never matches); one inside that range whose label id does not fit a byte raises ValueError."""
+    table = torch.zeros(256, dtype=torch.uint8)
+    for label_id, train_id in id_to_trainid.items():
+        label_id, train_id = int(label_id), int(train_id)
+        if not 0 <= train_id <= 255:
+            continue
+        if not 0 <= label_id <= 255:
+            raise ValueError('trainid_table: label id %d (train id %d) does not fit a byte' % (label_id, train_id))
+        table[train_id] = label_id
+    return table
+
+
+def eval_dump(pred, palette=None, image=None, labels=None, id_table=None, alpha=0.5, want=('color',)):
+    """The images RunEval.inf writes under --dump_images (eval.py:664-693) from the class map of an evaluation, in one launch. pred: uint8 [H, W] or [n, H, W] on the
+    device. want: any of 'color' (uint8 [..., 3] = palette[pred]; palette uint8 [256, 3] RGB), 'compose' (uint8 [..., 3] = Image.blend(image, color, alpha); image
+    uint8 [..., 3]), 'diff' (uint8 [..., 3]: the compose pixel where labels != 255 and labels != pred, else white; labels int64 [...] train ids) and 'ids' (uint8
+    [...] = id_table[pred]; id_table uint8 [256], see trainid_table). -> dict name -> tensor."""
+    assert pred.dtype == torch.uint8 and pred.is_cuda and pred.is_contiguous() and pred.dim() in (2, 3) and pred.numel() > 0, 'eval_dump: pred is uint8 [H, W] or [n, H, W]'
+    shape = tuple(pred.shape)
+    want = tuple(want)
+    assert want and all(k in DUMP_OUTPUTS for k in want), 'eval_dump: want is a non-empty subset of %s' % (DUMP_OUTPUTS,)
+    for name, t, dtype, shp in (('palette', palette, torch.uint8, (256, 3)), ('image', image, torch.uint8, shape + (3,)), ('labels', labels, torch.int64, shape),
+                                ('id_table', id_table, torch.uint8, (256,))):
+        assert t is None or (t.dtype == dtype and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp), 'eval_dump: %s is %s %s' % (name, dtype, shp)
+    need = dict(color=('palette',), compose=('palette', 'image'), diff=('palette', 'image', 'labels'), ids=('id_table',))
+    given = dict(palette=palette, image=image, labels=labels, id_table=id_table)
+    for k in want:
+        for name in need[k]:
+            assert given[name] is not None, 'eval_dump: %s needs %s' % (k, name)
+    res = {k: torch.empty(shape if k == 'ids' else shape + (3,), dtype=torch.uint8, device=pred.device) for k in want}
+    check(_lib().pm_eval_dump(pred.data_ptr(), pred.numel(), ptr(palette), ptr(image), ptr(labels), ptr(id_table), float(alpha), ptr(res.get('color')),
+                              ptr(res.get('compose')), ptr(res.get('diff')), ptr(res.get('ids')), stream()), 'pm_eval_dump')
+    return res
+
+
 def argmax_f64(buffer):
     n, h, w, c = buffer.shape
     cls = torch.empty((n, h, w), dtype=torch.int64, device=buffer.device)

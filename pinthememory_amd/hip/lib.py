@@ -220,6 +220,7 @@ SIGNATURES = {
     'pm_class_sums_workspace': (_sz, [_i, _i, _i, _i, _i]),
     'pm_class_sums': (_i, [_vp, _i, _i, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     'pm_mem_actmap': (_i, [_vp, _i, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    'pm_eval_dump': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
